@@ -2,6 +2,7 @@
 """bench.py -- EGNN.forward throughput on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1 without a launcher: spawns the N ranks itself)
+    python bench.py ... --dump-outputs DIR                        (also writes the last timed step's outputs, rank 0's, to DIR/*.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -283,6 +284,37 @@ def make_inputs(kwargs, b, n, device, seed):
     return feats.to(device), coors.to(device), mask.to(device)
 
 
+DUMP_BYTES = 60 * 10 ** 6                                # --dump-outputs: array data of one run (files and headers stay under 64 MB)
+DUMP_SEED = 0
+
+
+def dump_outputs(outputs, out_dir, budget=DUMP_BYTES):
+    """Writes {name: tensor} as out_dir/<name>.npy in float32 (float64 stays float64).  An output that does not fit its share of
+    `budget` (the smaller outputs are written first, whole, and leave the rest to the larger ones) is written as a fixed, seeded
+    sample of its rows -- all dimensions but the last flattened, rows in ascending order, the same rows in every run of the same
+    workload.  Returns {name: {"shape", "dtype", "rows", "rows_written"}} for the result line."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(outputs.items(), key=lambda kv: kv[1].numel())
+    left, info = budget, {}
+    for i, (name, t) in enumerate(items):
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        rows = t.reshape(-1, t.shape[-1]) if t.dim() > 1 else t.reshape(-1, 1)
+        n_rows = rows.shape[0]
+        keep = min(n_rows, (left // (len(items) - i)) // (rows.shape[1] * rows.element_size()))
+        if keep < n_rows:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            pick = torch.randperm(n_rows, generator=g)[:keep].sort().values
+            arr = rows[pick.to(rows.device)].cpu().numpy()
+        else:
+            arr = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr))
+        left -= arr.nbytes
+        info[name] = {"shape": list(t.shape), "dtype": str(arr.dtype), "rows": n_rows, "rows_written": keep}
+    return info
+
+
 LAST_LOCAL_ELAPSED = [None]
 
 
@@ -461,6 +493,9 @@ def main():
                     help="also time the step as a captured HIP graph (egnn_pytorch_amd.graphed), after everything else (secondary figure)")
     ap.add_argument("--reference-eager", action="store_true",
                     help="also time the reference module on the MI355X through PyTorch eager (secondary baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32; at most 64 MB in all, larger outputs as a "
+                         "fixed seeded sample of their rows), so that two builds can be compared output for output")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -588,12 +623,14 @@ def main():
         i = torch.arange(n, device=device)
         adj = (i[:, None] - i[None, :]).abs() <= 1                              # README chain adjacency incl. diagonal
 
+    last_out = [None]                                    # what the most recent step returned (--dump-outputs)
+
     @torch.no_grad()                                     # the metric is inference (eval, no_grad): BASELINE.md §2
     def step():
         if is_net:
-            layer(feats, coors, adj_mat=adj, edges=edges, mask=mask)
+            last_out[0] = layer(feats, coors, adj_mat=adj, edges=edges, mask=mask)
         else:
-            layer(feats, coors, edges, mask, adj)
+            last_out[0] = layer(feats, coors, edges, mask, adj)
 
     # Priming, before the W warm-up steps of the contract (untimed, reported as `priming_steps`): on most boxes a one-off stall of ~35 ms
     # lands somewhere in a process's first few dozen forwards of the network workloads, and with 20 short steps it dominated whichever
@@ -614,6 +651,9 @@ def main():
     elapsed = timed_region(step, args.steps, args.warmup, torch.cuda.synchronize, barrier, reduce_max)
     rank_ms = per_rank_ms(args.steps)                    # (a collective: every rank calls it)
     check_range()                                        # raises if any timed step left the representable range
+    dumped = None
+    if args.dump_outputs and rank == 0:                  # the last timed step's outputs, before any later run can touch them
+        dumped = dump_outputs(dict(zip(("feats", "coors"), last_out[0])), args.dump_outputs)
 
     # the same K steps in the other mode of the range check, so that the line shows what the per-forward synchronisation costs
     value_other, other_mode = None, ("deferred" if _ops.RANGE_CHECK == "sync" else "sync")
@@ -700,6 +740,8 @@ def main():
             "other_kernels_ms_per_step": other,
             "sum_kernel_ms": round(sum(per_kernel[k] * launches[k] for k in per_kernel), 4),
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if world == 1 and PRIME_STEPS > 0 and not args.no_live_traffic and os.environ.get("EGNN_BENCH_TRAFFIC_CHILD") != "1" and not under_profiler:
             uv, why = unprimed_value(args)
             out["value_unprimed"] = round(uv, 2) if uv is not None else None

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests._reference import case_key, check_state, pack_grads, reference_result, state_digest, unpack_grads
 from tests._util import golden_names, layer_kwargs, load_golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -76,27 +77,30 @@ def _grads(module, call, inputs, seed=0):
 
 @pytest.mark.parametrize("name", ["knn8_mask", "all_flags", "c1_dense_dim32", "dense_edges_mask", "fourier2_knn",
                                   "mean_pool_nomask", "sparse_chain_edges_mask", "knn8_coor_dim5_normcoors_mask"])
-def test_restatement_gradients_match_reference_autograd(ref, name):
+def test_restatement_gradients_match_reference_autograd(name):
     from egnn_pytorch_amd.autograd import layer_given_neighbors
     # In float64: with norm_coors the self pair (rel = 0, a neighbour of every node) goes through x / clamp(|x|, 1e-8), whose
     # Jacobian is scale / 1e-8 = O(1e7); the +/- contributions cancel exactly in exact arithmetic but leave O(1) rounding
     # noise in fp32 -- in the reference's own gradient as much as in ours.  fp64 checks the mathematics.
     meta, kw, layer, params, d = _case(name)
     layer = layer.double()
-    rlayer = ref.EGNN(**meta["kwargs"])
-    rlayer.load_state_dict({k: torch.from_numpy(v) for k, v in params.items()}, strict=True)
-    rlayer = rlayer.double()
     idx, rank = _t(d, "topk_indices.0", torch.int64), _t(d, "topk_values.0")
     radius = 0.0 if (layer.only_sparse_neighbors and "adj_mat" in d) else layer.valid_radius
     mk = lambda k: None if k not in d else _t(d, k).double().clone().requires_grad_(True)
     f1, c1, e1 = mk("feats"), mk("coors"), mk("edges")
-    f2, c2, e2 = mk("feats"), mk("coors"), mk("edges")
     mask, adj = _t(d, "mask"), _t(d, "adj_mat")
-    want, shapes2 = _grads(rlayer, lambda: rlayer(f2, c2, e2, mask, adj), (f2, c2, e2))
+
+    def reference(ref):                                  # the reference's autograd, float64, same weights (the golden file's)
+        rlayer = ref.EGNN(**meta["kwargs"])
+        rlayer.load_state_dict({k: torch.from_numpy(v) for k, v in params.items()}, strict=True)
+        rlayer = rlayer.double()
+        f2, c2, e2 = mk("feats"), mk("coors"), mk("edges")
+        return pack_grads(_grads(rlayer, lambda: rlayer(f2, c2, e2, mask, adj), (f2, c2, e2))[0])
+    want = unpack_grads(reference_result(f"restatement_grads_{name}", reference))
     for factorised in (True, False):                     # node-level projections (what the backward runs) / literal cat + Linear
         got, shapes = _grads(layer, lambda: layer_given_neighbors(layer, f1, c1, e1, mask, idx, rank, radius, factorised),
                              (f1, c1, e1))
-        assert shapes == shapes2
+        assert len(got) == len(want)
         for g, w in zip(got, want):
             assert (g is None) == (w is None)
             if g is not None:
@@ -114,17 +118,17 @@ def test_restatement_gradients_match_reference_autograd(ref, name):
     (dict(dim=24, only_sparse_neighbors=True, edge_dim=2), 40, dict(mask=True, edges=True, adj=True)),
     (dict(dim=16, update_feats=False, num_nearest_neighbors=6), 30, dict(mask=True)),
 ])
-def test_hip_forward_with_recompute_backward_matches_reference(ref, kw, n, flags):
+def test_hip_forward_with_recompute_backward_matches_reference(kw, n, flags, request):
     """loss.backward() through the drop-in layer on the MI355X == the reference's autograd on the CPU (1e-4 of each gradient's scale)."""
     from egnn_pytorch_amd import EGNN
-    torch.manual_seed(5)
-    rlayer = ref.EGNN(**kw)
-    with torch.no_grad():
-        for p in rlayer.parameters():
-            p.mul_(60.0)                                    # away from the vacuous default init (std 1e-3)
-    layer = EGNN(**kw)
-    layer.load_state_dict(rlayer.state_dict(), strict=True)
-    layer = layer.cuda()
+
+    def scaled(cls):
+        torch.manual_seed(5)
+        m = cls(**kw)
+        with torch.no_grad():
+            for p in m.parameters():
+                p.mul_(60.0)                                # away from the vacuous default init (std 1e-3)
+        return m
     g = torch.Generator().manual_seed(2)
     b = 3
     feats, coors = torch.randn(b, n, kw["dim"], generator=g), torch.randn(b, n, 3, generator=g)
@@ -136,11 +140,19 @@ def test_hip_forward_with_recompute_backward_matches_reference(ref, kw, n, flags
         adj = (i[:, None] - i[None, :]).abs() <= 2
     mk = lambda t, dev: None if t is None else t.clone().to(dev).requires_grad_(True)
     dv = lambda t: None if t is None else t.cuda()
+
+    def reference(ref):
+        rlayer = scaled(ref.EGNN)
+        f2, c2, e2 = mk(feats, "cpu"), mk(coors, "cpu"), mk(edges, "cpu")
+        return dict(pack_grads(_grads(rlayer, lambda: rlayer(f2, c2, e2, mask, adj), (f2, c2, e2))[0]), state_sha256=state_digest(rlayer))
+    stored = reference_result(case_key(request), reference, gpu=True)
+    layer = scaled(EGNN)
+    check_state(layer, stored)
+    layer = layer.cuda()
     f1, c1, e1 = mk(feats, "cuda"), mk(coors, "cuda"), mk(edges, "cuda")
-    f2, c2, e2 = mk(feats, "cpu"), mk(coors, "cpu"), mk(edges, "cpu")
     got, s1 = _grads(layer, lambda: layer(f1, c1, e1, dv(mask), dv(adj)), (f1, c1, e1))
-    want, s2 = _grads(rlayer, lambda: rlayer(f2, c2, e2, mask, adj), (f2, c2, e2))
-    assert s1 == s2
+    want = unpack_grads(stored)
+    assert len(got) == len(want)
     for pos, (gg, ww) in enumerate(zip(got, want)):
         assert (gg is None) == (ww is None)
         if gg is not None:
@@ -618,7 +630,7 @@ def test_backward_at_baseline_widths_matches_the_reference_autograd(ref, name, k
 @pytest.mark.gpu
 @pytest.mark.parametrize("kw,cdim", [(dict(dim=24, num_nearest_neighbors=6), 12), (dict(dim=24, m_dim=80, num_nearest_neighbors=6), 3),
                                      (dict(dim=16, fourier_features=10, num_nearest_neighbors=5), 3)])
-def test_shapes_of_the_plain_kernels_train_on_their_own_backward_kernels(ref, kw, cdim, monkeypatch):
+def test_shapes_of_the_plain_kernels_train_on_their_own_backward_kernels(kw, cdim, monkeypatch, request):
     """More than 8 coordinates, heads wider than 64 channels, more than 16 per-edge scalars: the forward runs on the plain kernels and
     -- round 5 -- the backward's E x H work on csrc/edge_exact_bwd.hip with the exact-fp32 GEMMs (`_backward_exact`), never on the ATen
     recompute: gradients against the reference's float64 autograd."""
@@ -627,22 +639,33 @@ def test_shapes_of_the_plain_kernels_train_on_their_own_backward_kernels(ref, kw
     def no_recompute(*a, **k):
         raise AssertionError("the ATen recompute backward ran")
     monkeypatch.setattr(A, "_backward_recompute", no_recompute)
-    torch.manual_seed(12)
-    rlayer = ref.EGNN(**kw)
-    for mod in rlayer.modules():
-        if isinstance(mod, torch.nn.Linear):
-            torch.nn.init.xavier_normal_(mod.weight)
-    layer = EGNN(**kw)
-    layer.load_state_dict(rlayer.state_dict(), strict=True)
-    layer, rlayer = layer.cuda(), rlayer.double().cuda()
+
+    def xavier(cls):
+        torch.manual_seed(12)
+        m = cls(**kw)
+        for mod in m.modules():
+            if isinstance(mod, torch.nn.Linear):
+                torch.nn.init.xavier_normal_(mod.weight)
+        return m
     g = torch.Generator().manual_seed(13)
-    feats, coors = torch.randn(2, 30, kw["dim"], generator=g).cuda(), torch.randn(2, 30, cdim, generator=g).cuda()
-    f1, c1 = feats.clone().requires_grad_(True), coors.clone().requires_grad_(True)
-    f2, c2 = feats.double().requires_grad_(True), coors.double().requires_grad_(True)
+    feats, coors = torch.randn(2, 30, kw["dim"], generator=g), torch.randn(2, 30, cdim, generator=g)
+
+    def reference(ref):
+        rlayer = xavier(ref.EGNN)
+        digest = state_digest(rlayer)
+        rlayer = rlayer.double()
+        f2, c2 = feats.double().requires_grad_(True), coors.double().requires_grad_(True)
+        return dict(pack_grads(_grads(rlayer, lambda: rlayer(f2, c2), (f2, c2))[0]), state_sha256=digest)
+    stored = reference_result(case_key(request), reference, gpu=True)
+    layer = xavier(EGNN)
+    check_state(layer, stored)
+    layer = layer.cuda()
+    f1, c1 = feats.cuda().requires_grad_(True), coors.cuda().requires_grad_(True)
     with _ops.phase_timer() as pt:
         got, _ = _grads(layer, lambda: layer(f1, c1), (f1, c1))
     assert {"edge_exact", "edge_exact_bwd", "edge_exact_node_sums", "bwd_exact_dw2", "bwd_exact_dfeats"} <= set(pt.summary()), set(pt.summary())
-    want, _ = _grads(rlayer, lambda: rlayer(f2, c2), (f2, c2))
+    want = unpack_grads(stored)
+    assert len(got) == len(want)
     for gg, ww in zip(got, want):
         assert (gg is None) == (ww is None)
         if gg is not None:
@@ -650,7 +673,7 @@ def test_shapes_of_the_plain_kernels_train_on_their_own_backward_kernels(ref, kw
 
 
 @pytest.mark.gpu
-def test_the_reference_training_recipe_trains_on_the_float64_kernels(ref, monkeypatch):
+def test_the_reference_training_recipe_trains_on_the_float64_kernels(monkeypatch, request):
     """denoise_sparse.py:11, 23-32, 45-78 -- what SURVEY.md section 8f-2 cites as the reason for a backward: a FLOAT64
     EGNN_Network(num_tokens=21, num_positions=600, depth=5, dim=8, num_nearest_neighbors=16, fourier_features=2, norm_coors,
     coor_weights_clamp_value=2) on a chain adjacency with a mask, MSE of the denoised coordinates, Adam.  Forward: the float64
@@ -664,45 +687,57 @@ def test_the_reference_training_recipe_trains_on_the_float64_kernels(ref, monkey
     monkeypatch.setattr(A, "_backward_recompute", no_recompute)
     kw = dict(num_tokens=21, num_positions=600, depth=5, dim=8, num_nearest_neighbors=16, fourier_features=2, norm_coors=True,
               coor_weights_clamp_value=2.0)
-    torch.manual_seed(5)
-    rnet = ref.EGNN_Network(**kw).double()
-    net = EGNN_Network(**kw).double()
-    net.load_state_dict(rnet.state_dict(), strict=True)
-    net, rnet = net.cuda(), rnet.cuda()
     g = torch.Generator().manual_seed(6)
     n = 3 * 40                                               # 40 residues x 3 backbone atoms (the script's repeat(... c = 3))
-    seq = torch.randint(0, 21, (1, n // 3), generator=g).repeat_interleave(3, dim=1).cuda()
-    coords = (torch.randn(1, n, 3, generator=g, dtype=torch.float64) * 3.0).cuda()
-    masks = (torch.arange(n)[None] < n - 6).cuda()
+    seq = torch.randint(0, 21, (1, n // 3), generator=g).repeat_interleave(3, dim=1)
+    coords = torch.randn(1, n, 3, generator=g, dtype=torch.float64) * 3.0
+    masks = torch.arange(n)[None] < n - 6
     i = torch.arange(n)
-    adj = ((i[:, None] >= (i[None, :] - 1)) & (i[:, None] <= (i[None, :] + 1))).cuda()
-    noise = torch.randn(1, n, 3, generator=g, dtype=torch.float64).cuda()
+    adj = (i[:, None] >= (i[None, :] - 1)) & (i[:, None] <= (i[None, :] + 1))
+    noise = torch.randn(1, n, 3, generator=g, dtype=torch.float64)
 
-    def loss_of(model):
-        feats, den = model(seq, coords + noise, adj_mat=adj, mask=masks)
-        return torch.nn.functional.mse_loss(den[masks], coords[masks])
+    def loss_of(model, dev):
+        feats, den = model(seq.to(dev), (coords + noise).to(dev), adj_mat=adj.to(dev), mask=masks.to(dev))
+        return torch.nn.functional.mse_loss(den[masks.to(dev)], coords.to(dev)[masks.to(dev)])
 
+    def train(model, dev):
+        """Loss and gradients of the first step, then the losses of three Adam steps."""
+        loss = loss_of(model, dev)
+        grads = torch.autograd.grad(loss, list(model.parameters()), allow_unused=True)
+        opt, losses = torch.optim.Adam(model.parameters(), lr=1e-3), []
+        for _ in range(3):
+            opt.zero_grad()
+            l_ = loss_of(model, dev)
+            l_.backward()
+            opt.step()
+            losses.append(float(l_))
+        return float(loss), grads, losses
+
+    def reference(ref):
+        torch.manual_seed(5)
+        rnet = ref.EGNN_Network(**kw).double()
+        digest = state_digest(rnet)
+        rloss, want, rlosses = train(rnet, "cpu")
+        return dict(pack_grads(want), loss=rloss, adam_losses=rlosses, state_sha256=digest)
+    stored = reference_result(case_key(request), reference, gpu=True)
+    torch.manual_seed(5)
+    net = EGNN_Network(**kw).double()
+    check_state(net, stored)
+    net = net.cuda()
     with _ops.phase_timer() as pt:
-        loss = loss_of(net)
-        got = torch.autograd.grad(loss, list(net.parameters()), allow_unused=True)
+        loss, got, losses = train(net, "cuda")
     launched = set(pt.summary())
     assert {"edge_exact", "edge_exact_bwd", "edge_exact_node_sums", "bwd_exact_dw2", "bwd_exact_dws", "bwd_exact_dw1"} <= launched, launched
-    rloss = loss_of(rnet)
-    want = torch.autograd.grad(rloss, list(rnet.parameters()), allow_unused=True)
-    assert abs(float(loss) - float(rloss)) <= 1e-9 * max(1.0, abs(float(rloss)))
+    rloss, want = float(stored["loss"]), unpack_grads(stored)
+    assert abs(loss - rloss) <= 1e-9 * max(1.0, abs(rloss))
+    assert len(got) == len(want)
     for (nm, _), gg, ww in zip(net.named_parameters(), got, want):
         assert (gg is None) == (ww is None), nm
         if gg is not None and float(ww.abs().max()) > 0:
+            gg = gg.cpu()
             assert float((gg - ww).abs().max()) <= 1e-7 * float(ww.abs().max()), (nm, float((gg - ww).abs().max()), float(ww.abs().max()))
-    opt, ropt = torch.optim.Adam(net.parameters(), lr=1e-3), torch.optim.Adam(rnet.parameters(), lr=1e-3)
-    for _ in range(3):
-        for model, o in ((net, opt), (rnet, ropt)):
-            o.zero_grad()
-            l_ = loss_of(model)
-            l_.backward()
-            o.step()
-            model.last_loss = float(l_)
-        assert abs(net.last_loss - rnet.last_loss) <= 1e-7 * max(1.0, abs(rnet.last_loss))
+    for l_, rl in zip(losses, stored["adam_losses"]):
+        assert abs(l_ - float(rl)) <= 1e-7 * max(1.0, abs(float(rl)))
 
 
 @pytest.mark.gpu
