@@ -293,6 +293,16 @@ def check_range(device=None, wait=True):
 def knn_select(coors, mask, adj_mat, k, out=None):
     """(idx int32 (B,N,K), rank (B,N,K) in the coordinates' dtype) -- egnn_knn_select_f32; float64 coordinates (a float64 module):
     egnn_knn_select_f64.  out = (idx, rank): caller-allocated outputs (the side-stream fork allocates them on the launch stream)."""
+    return _knn_select(coors, mask, adj_mat, k, out, "egnn_knn_select")
+
+
+def knn_select_stream(coors, mask, adj_mat, k, out=None):
+    """knn_select on the streaming kernel (egnn_knn_select_stream_f32 / _f64) whatever the graph's size: the kernel the two entries
+    above take for graphs whose keys do not fit in LDS; the same outputs bit for bit."""
+    return _knn_select(coors, mask, adj_mat, k, out, "egnn_knn_select_stream")
+
+
+def _knn_select(coors, mask, adj_mat, k, out, entry):
     b, n, cdim = coors.shape
     f64 = coors.dtype == torch.float64
     if out is not None:
@@ -310,10 +320,10 @@ def knn_select(coors, mask, adj_mat, k, out=None):
             stride = n * n
         elif a8.shape != (n, n):
             raise ValueError(f"adj_mat shape {tuple(a8.shape)} != {(n, n)}")
+    name = entry + ("_f64" if f64 else "_f32")
     with _timed("knn_select"):
-        fn = _abi.load().egnn_knn_select_f64 if f64 else _abi.load().egnn_knn_select_f32
-        rc = fn(_ptr(coors), _ptr(m8), _ptr(a8), stride, b, n, k, cdim, _ptr(idx), _ptr(rank), _stream())
-    _abi.check(rc, "egnn_knn_select_f64" if f64 else "egnn_knn_select_f32")
+        rc = getattr(_abi.load(), name)(_ptr(coors), _ptr(m8), _ptr(a8), stride, b, n, k, cdim, _ptr(idx), _ptr(rank), _stream())
+    _abi.check(rc, name)
     return idx, rank
 
 

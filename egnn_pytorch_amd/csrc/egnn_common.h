@@ -258,6 +258,36 @@ __device__ __forceinline__ T egnn_sqdist_any(const T* __restrict__ a, const T* _
     return acc;
 }
 
+// ---- k-NN ranking (egnn_pytorch.py:237-256), shared by every selection kernel.  The ranking value of pair (i, j) from its squared
+// distance: 1e5 where either node is masked (:240-242); with an adjacency matrix -1 on the diagonal (:255) and 0 for adjacent nodes
+// (:256).  adjrow = row i of the adjacency, or NULL.
+template <typename T>
+__device__ __forceinline__ T egnn_knn_rank(T d, bool mi, bool mj, const uint8_t* __restrict__ adjrow, int i, int j) {
+    if (!(mi && mj)) d = (T)1e5;
+    if (adjrow) {
+        if (j == i) d = (T)-1;
+        else if (adjrow[j]) d = (T)0;
+    }
+    return d;
+}
+// order-preserving unsigned images of the ranking values (selection compares keys; ties by ascending index)
+__device__ __forceinline__ uint32_t egnn_rank_key(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return (u >> 31) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ uint64_t egnn_rank_key(double f) {
+    const uint64_t u = (uint64_t)__double_as_longlong(f);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ float egnn_rank_from_key(uint32_t k) {
+    const uint32_t u = (k >> 31) ? (k & 0x7fffffffu) : ~k;
+    return __uint_as_float(u);
+}
+__device__ __forceinline__ double egnn_rank_from_key(uint64_t k) {
+    const uint64_t u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+    return __longlong_as_double((long long)u);
+}
+
 // Packed ("tile-major") layout of the fp16 GEMM operands: an (R x Kp) matrix, R padded to 32 rows, Kp % 32 == 0, is
 // stored as [R/32][Kp/16][32 rows][2 chunks][8 halves]; the chunk index is XOR-swizzled by ((row >> 3) & 1) so that the
 // 1 KB (row block, K-tile) piece is exactly the bank-conflict-free LDS image the GEMM wants.  nkt = Kp / 16.

@@ -149,26 +149,6 @@ __global__ __launch_bounds__(256) void node_prep_f64_kernel(const double* __rest
 // than 8 coordinates (egnn_knn_select_f32 hands those over: knn_select.hip keeps a row's coordinates in registers up to 8).
 constexpr int KN_THREADS = 256, KN_WAVES = 4;
 
-__device__ __forceinline__ uint64_t to_key(double f)
-{
-    const uint64_t u = (uint64_t)__double_as_longlong(f);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ uint32_t to_key(float f)
-{
-    const uint32_t u = __float_as_uint(f);
-    return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ double from_key(uint64_t k)
-{
-    const uint64_t u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    return __longlong_as_double((long long)u);
-}
-__device__ __forceinline__ float from_key(uint32_t k)
-{
-    const uint32_t u = (k >> 31) ? (k & 0x7fffffffu) : ~k;
-    return __uint_as_float(u);
-}
 template <typename T> struct KnnKey;
 template <> struct KnnKey<double> { typedef uint64_t type; static constexpr int V = 4; };
 template <> struct KnnKey<float> { typedef uint32_t type; static constexpr int V = 8; };
@@ -198,13 +178,8 @@ __global__ __launch_bounds__(KN_THREADS) void knn_select_any_kernel(
         return;
     }
     for (int j = tid; j < N; j += KN_THREADS) {
-        T rk = egnn_sqdist_any<T, KnnKey<T>::V>(cb + (size_t)i * C, cb + (size_t)j * C, C);
-        if (!(mi && (mb ? mb[j] != 0 : true))) rk = (T)1e5;              // :240-242
-        if (adjrow) {
-            if (j == i) rk = (T)-1;                                      // :255
-            else if (adjrow[j]) rk = (T)0;                               // :256
-        }
-        keys[j] = to_key(rk);
+        const T rk = egnn_sqdist_any<T, KnnKey<T>::V>(cb + (size_t)i * C, cb + (size_t)j * C, C);
+        keys[j] = egnn_rank_key(egnn_knn_rank<T>(rk, mi, mb ? mb[j] != 0 : true, adjrow, i, j));
     }
     __syncthreads();
     auto block_sum = [&](int v, int slot) {
@@ -259,7 +234,7 @@ __global__ __launch_bounds__(KN_THREADS) void knn_select_any_kernel(
         int rnk = 0;
         for (int u = 0; u < K; ++u) rnk += (selk[u] < mk || (selk[u] == mk && selj[u] < mj)) ? 1 : 0;
         idx_out[obase + rnk] = mj;
-        rank_out[obase + rnk] = from_key(mk);
+        rank_out[obase + rnk] = egnn_rank_from_key(mk);
     }
 }
 
@@ -274,7 +249,12 @@ int knn_select_any(const T* coors, const uint8_t* mask, const uint8_t* adj, int6
     if (K > 1024 || B > 65535) return EGNN_E_UNSUPPORTED;
     typedef typename KnnKey<T>::type key_t;
     const size_t lds = ((size_t)N * sizeof(key_t) + 7) / 8 * 8 + (size_t)K * (sizeof(key_t) + 4) + 2 * KN_WAVES * sizeof(int) + 8;
-    if (lds > 160 * 1024) return EGNN_E_UNSUPPORTED;                      // N <= ~ 20 000 (double) / 40 000 (float)
+    if (lds > 160 * 1024) {                                               // N > ~ 20 000 (double) / 40 000 (float): keys recomputed per pass
+        if constexpr (sizeof(T) == 8)
+            return egnn_knn_select_stream_f64(coors, mask, adj, adj_batch_stride, B, N, K, coor_dim, idx_out, rank_out, stream);
+        else
+            return egnn_knn_select_stream_f32(coors, mask, adj, adj_batch_stride, B, N, K, coor_dim, idx_out, rank_out, stream);
+    }
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(knn_select_any_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;

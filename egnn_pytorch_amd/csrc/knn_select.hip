@@ -17,14 +17,8 @@
 
 namespace {
 
-__device__ __forceinline__ uint32_t f2key(float f) {
-    uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(uint32_t k) {
-    uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-    return __uint_as_float(u);
-}
+__device__ __forceinline__ uint32_t f2key(float f) { return egnn_rank_key(f); }
+__device__ __forceinline__ float key2f(uint32_t k) { return egnn_rank_from_key(k); }
 __device__ __forceinline__ void wave_lds_sync() {
     // same-wave LDS hand-off: DS operations of one wave execute in issue order; the explicit wait makes the
     // store -> other-lane load dependency independent of that, the wave barrier pins the compiler's ordering.
@@ -336,12 +330,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(
                     for (int c = 0; c < CDM; ++c) cj[c] = c < C ? xs[c * Npad + j] : 0.f;
                     rk = egnn_sqdist_n<CDM>(ci, cj, C, rel);
                 }
-                if (!(mi && ms[j] != 0)) rk = 1e5f;                 // :240-242
-                if (adjrow) {
-                    if (j == i) rk = -1.0f;                         // :255
-                    else if (adjrow[j]) rk = 0.0f;                  // :256
-                }
-                k = f2key(rk);
+                k = f2key(egnn_knn_rank<float>(rk, mi, ms[j] != 0, adjrow, i, j));     // :240-256
             }
             key[c] = k;
         }
@@ -507,12 +496,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_select_large_kernel(
             for (int c = 0; c < CDM; ++c) cj[c] = c < C ? cb[(size_t)j * C + c] : 0.f;
             rk = egnn_sqdist_n<CDM>(ci, cj, C, rel);
         }
-        if (!(mi && (mb ? mb[j] != 0 : true))) rk = 1e5f;                // :240-242
-        if (adjrow) {
-            if (j == i) rk = -1.0f;                                      // :255
-            else if (adjrow[j]) rk = 0.0f;                               // :256
-        }
-        keys[j] = f2key(rk);
+        keys[j] = f2key(egnn_knn_rank<float>(rk, mi, mb ? mb[j] != 0 : true, adjrow, i, j));       // :240-256
     }
     __syncthreads();
 
@@ -665,9 +649,10 @@ extern "C" int egnn_knn_select_f32(const float* coors, const uint8_t* mask, cons
     if (K > 1024 || B > 65535) return EGNN_E_UNSUPPORTED;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // candidate keys live in registers (ceil(N / 64) per lane) and the graph's coordinates in LDS: N <= 8192 for 3-D coordinates
-    // (128 keys per lane, 104 KB), N <= 4096 otherwise; larger graphs: one workgroup per row with the keys in LDS, up to 32 768 nodes
+    // (128 keys per lane, 104 KB), N <= 4096 otherwise; larger graphs: one workgroup per row with the keys in LDS, up to 32 768 nodes;
+    // beyond that the streaming kernel (knn_stream.hip), which recomputes the keys on every pass
     if (N > (C == 3 ? 8192 : 4096)) {
-        if (N > 32768) return EGNN_E_UNSUPPORTED;
+        if (N > 32768) return egnn_knn_select_stream_f32(coors, mask, adj, adj_batch_stride, B, N, K, C, idx_out, rank_out, stream);
         return C == 3 ? launch_knn_large<3>(coors, mask, adj, adj_batch_stride, B, N, K, C, idx_out, rank_out, s)
                       : launch_knn_large<8>(coors, mask, adj, adj_batch_stride, B, N, K, C, idx_out, rank_out, s);
     }

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define EGNN_ABI_VERSION 37
+#define EGNN_ABI_VERSION 38
 
 enum {
     EGNN_OK = 0,
@@ -83,12 +83,21 @@ int egnn_padded_hidden(int H);
  *          The diagonal is ignored (the reference clears it, :254).
  *   idx_out  (B,N,K) int32   neighbour indices, ascending rank; ties broken by ascending index
  *   rank_out (B,N,K) fp32    the ranking values of the selected neighbours (reference `nbhd_ranking`)
- * Limits: 1 <= K <= min(N, 1024), N <= 32 768 (up to 8192 nodes with 3-D coordinates, 4096 otherwise, a wave keeps a row's candidate
- * keys in registers; beyond that one workgroup per row keeps them in LDS: ~10 us per row).
+ * Limits: 1 <= K <= min(N, 1024), B <= 65 535; N has no bound of its own.  Up to 8192 nodes with 3-D coordinates (4096 otherwise) a
+ * wave keeps a row's candidate keys in registers; up to 32 768 nodes (C <= 8; ~40 000 for C > 8) one workgroup per row keeps them in
+ * LDS (~10 us per row); larger graphs take egnn_knn_select_stream_f32.
  */
 int egnn_knn_select_f32(const float* coors, const uint8_t* mask, const uint8_t* adj,
                         int64_t adj_batch_stride, int B, int N, int K, int coor_dim,
                         int32_t* idx_out, float* rank_out, void* stream);
+/* The streaming selection behind egnn_knn_select_f32 / _f64 on graphs whose keys do not fit in LDS (csrc/knn_stream.hip), callable
+ * on any graph: same arguments, same limits except N, outputs bit-identical to those entries.  No key is stored -- every pass
+ * recomputes a row's ranking values from coors, mask and adj (the coordinates stay in L2) -- and the top-K is a radix select over
+ * 8-bit digits of (key, index), 16 rows per workgroup sharing each pass (fewer for large K).  Deterministic. */
+int egnn_knn_select_stream_f32(const float* coors, const uint8_t* mask, const uint8_t* adj, int64_t adj_batch_stride,
+                               int B, int N, int K, int coor_dim, int32_t* idx_out, float* rank_out, void* stream);
+int egnn_knn_select_stream_f64(const double* coors, const uint8_t* mask, const uint8_t* adj, int64_t adj_batch_stride,
+                               int B, int N, int K, int coor_dim, int32_t* idx_out, double* rank_out, void* stream);
 
 /* Replaces `int(adj_mat.float().sum(dim=-1).max().item())` (egnn_pytorch.py:249; the diagonal is
  * counted when set).  adj: (rows, N) bytes.  *out_dev (device int32) receives the maximum row sum;
@@ -111,7 +120,9 @@ int egnn_spatial_order_masked_f32(const float* coors, const uint8_t* mask, int B
  *         tiles [tile_seg[n], tile_seg[n+1]) -- and -1 behind the last tile: the entry list of egnn_edge_bwd_pass_f32 (by_dest = 1),
  *         of which the caller uses the first (tile_seg[B N] * 16 rounded up to 128) entries
  * ent_capacity >= egnn_dest_lists_capacity(B, N, K) entries; tiles_per_graph: (B) int64 scratch.  Counting sort per graph (the
- * destinations of one source row are distinct), two launches, deterministic.  Limits: B N K < 2^31, N <= 20 415 (the per-wave histograms live in LDS). */
+ * destinations of one source row are distinct), deterministic.  Up to N = 20 415 one workgroup per graph (two launches, the per-wave
+ * histograms of all N destinations in LDS); larger graphs: degrees and offsets by three launches, then one workgroup per band of
+ * 1024 destinations places the graph's edges in the same stable order.  Limits: B N K < 2^31. */
 size_t egnn_dest_lists_capacity(int B, int N, int K);
 int egnn_dest_lists_i32(const int32_t* idx, int B, int N, int K, int32_t* ent, size_t ent_capacity, int64_t* tile_seg,
                         int64_t* csr_order, int64_t* csr_seg, int64_t* tiles_per_graph, void* stream);
@@ -798,7 +809,8 @@ int egnn_edge_tail_exact_bwd_f64(const egnn_edge_tail_exact_args* args, void* st
  * significant bits per product.  A binding routes a module whose parameters are float64 through the entries below (the shipped one
  * does: egnn_pytorch_amd/layer.py) -- the same plain kernels as the wide-range path, instantiated for double:
  *   egnn_knn_select_f64   as egnn_knn_select_f32 (squared distances in the same operation order, ranking edits, exact top-K, ties
- *                         towards the lowest index), coor_dim <= 64; rank_out in float64.  One workgroup per row, keys in LDS: N <= 20 000, K <= 1024
+ *                         towards the lowest index), coor_dim <= 64; rank_out in float64.  One workgroup per row, keys in LDS, up to N ~ 20 000;
+ *                         larger graphs: egnn_knn_select_stream_f64.  K <= 1024
  *   egnn_linear_f64       as egnn_linear_f32, on v_mfma_f64_16x16x4_f64
  *   egnn_node_prep_f64    as egnn_node_prep_f32
  *   egnn_edge_exact_f64   as egnn_edge_exact_f32 with every data pointer of egnn_edge_exact_args a double*; workspace twice
