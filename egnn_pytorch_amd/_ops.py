@@ -356,6 +356,16 @@ def slot_prep(coors, mask8, idx, rank, order, valid_radius, out=None):
 def adj_expand(adj_mat, b, num_adj_degrees):
     """N-degree adjacency expansion (egnn_pytorch.py:414-427) -- egnn_adj_expand_u8.
     Returns (expanded adjacency (B,N,N) bool, adj_indices (B,N,N) uint8)."""
+    return _adj_expand(adj_mat, b, num_adj_degrees, "egnn_adj_expand_u8")
+
+
+def adj_expand_wide(adj_mat, b, num_adj_degrees):
+    """adj_expand on the any-N kernel (egnn_adj_expand_wide_u8) whatever the graph's size: the kernel adj_expand takes above 4 096
+    nodes; the same outputs bit for bit."""
+    return _adj_expand(adj_mat, b, num_adj_degrees, "egnn_adj_expand_wide_u8")
+
+
+def _adj_expand(adj_mat, b, num_adj_degrees, entry):
     a8 = _u8(adj_mat)
     n = a8.shape[-1]
     stride = n * n if a8.dim() == 3 else 0
@@ -366,9 +376,8 @@ def adj_expand(adj_mat, b, num_adj_degrees):
     deg = empty(b, n, n, dtype=torch.uint8, device=dev)
     ws = empty(_abi.load().egnn_adj_expand_workspace_bytes(b, n), dtype=torch.uint8, device=dev)
     with _timed("adj_expand"):
-        rc = _abi.load().egnn_adj_expand_u8(_ptr(a8), stride, b, n, num_adj_degrees, _ptr(adj_out), _ptr(deg), _ptr(ws),
-                                            _stream())
-    _abi.check(rc, "egnn_adj_expand_u8")
+        rc = getattr(_abi.load(), entry)(_ptr(a8), stride, b, n, num_adj_degrees, _ptr(adj_out), _ptr(deg), _ptr(ws), _stream())
+    _abi.check(rc, entry)
     return adj_out.view(torch.bool), deg
 
 

@@ -729,6 +729,18 @@ class EGNN(nn.Module):
 _FP64_WARNED = False
 
 
+def _embed_pairs(emb, idx):
+    """emb(idx) for a (B,N,N) index tensor of any size.  torch's device embedding fails to launch (invalid configuration) on
+    (1, 8192, 8192) indices on the MI355X; up to 2^24 indices it is one call, as before, beyond that chunks of at most 2^24 indices
+    and 2^26 outputs (the sizes it handles), concatenated.  Under autograd: the weight's gradient sums the chunks' in turn."""
+    n = idx.numel()
+    if n <= 1 << 24:
+        return emb(idx)
+    step = max(1, min(1 << 24, (1 << 26) // max(1, emb.embedding_dim)))
+    flat = idx.reshape(-1)
+    return torch.cat([emb(flat[lo:lo + step]) for lo in range(0, n, step)]).view(*idx.shape, emb.embedding_dim)
+
+
 def _warn_float64_once():
     """float64 callers get float64 tensors back, computed with fp32-class arithmetic (split-fp16 products, ~22 significant
     bits, fp32 accumulation): say so once per process instead of silently (VERDICT r2 weak #7)."""
@@ -815,7 +827,7 @@ class EGNN_Network(nn.Module):
             if lazy:
                 tok, tok_emb, edges = edges, self.edge_emb.weight, None
             else:
-                edges = self.edge_emb(edges)
+                edges = _embed_pairs(self.edge_emb, edges)
 
         if self.num_adj_degrees is not None:
             assert adj_mat is not None, "adjacency matrix must be passed in (keyword argument adj_mat)"
@@ -828,7 +840,7 @@ class EGNN_Network(nn.Module):
                     edges = EdgeLookup(edges=edges, tok=tok, tok_emb=tok_emb, deg=adj_indices, deg_emb=self.adj_emb.weight)
                     tok = None
                 else:
-                    adj_emb = self.adj_emb(adj_indices.long())
+                    adj_emb = _embed_pairs(self.adj_emb, adj_indices.long())
                     edges = torch.cat((edges, adj_emb), dim=-1) if edges is not None else adj_emb
         if tok is not None:                                         # edge tokens without adjacency degrees
             edges = EdgeLookup(tok=tok, tok_emb=tok_emb)

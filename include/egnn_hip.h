@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define EGNN_ABI_VERSION 38
+#define EGNN_ABI_VERSION 39
 
 enum {
     EGNN_OK = 0,
@@ -150,10 +150,17 @@ int egnn_slot_prep_f32(const float* coors, const uint8_t* mask, const int32_t* i
  *   adj_out     (B,N,N) bytes: the expanded adjacency the layers receive (:425)
  *   degree_out  (B,N,N) bytes: adj_indices (:419-424): 0 = not connected, 1 = adjacent, d = first reached at degree d
  *   workspace   egnn_adj_expand_workspace_bytes(B, N) bytes
- * Limits: N <= 4096, 1 <= num_adj_degrees <= 255. */
+ * Limits: 1 <= num_adj_degrees <= 255, B <= 65 535; N has no bound of its own.  Up to 4 096 nodes one wave holds a row's bit set
+ * (one 64-bit word per lane); larger graphs take the kernel of egnn_adj_expand_wide_u8 (column chunks of 65 536 nodes; DESIGN.md
+ * §4.7).  Each degree costs sum over rows of popcount(row) x ceil(N/64) word-ORs: cheap on sparse graphs (chains, contact maps),
+ * N^3 / 64 on rows that saturate. */
 size_t egnn_adj_expand_workspace_bytes(int B, int N);
 int egnn_adj_expand_u8(const uint8_t* adj, int64_t adj_batch_stride, int B, int N, int num_adj_degrees,
                        uint8_t* adj_out, uint8_t* degree_out, void* workspace, void* stream);
+/* The same expansion on the any-N kernel whatever the graph's size (the kernel egnn_adj_expand_u8 takes above 4 096 nodes); the same
+ * outputs bit for bit, the same workspace. */
+int egnn_adj_expand_wide_u8(const uint8_t* adj, int64_t adj_batch_stride, int B, int N, int num_adj_degrees,
+                            uint8_t* adj_out, uint8_t* degree_out, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Dense layers: C = act(A * W^T + bias) (+ residual).  Used for (a) the node-level projections P = feats * [W_i ; W_j]^T +
