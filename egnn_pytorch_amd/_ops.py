@@ -76,19 +76,14 @@ def empty(*shape, dtype, device):
     return t
 
 
-_RAW_STREAM = os.environ.get("EGNN_RAW_STREAM", "1") != "0"
-
-
 def _stream():
     """The raw hipStream_t of torch's current stream on the current device.  Through the C binding when it exists: the public
     torch.cuda.current_stream() builds a Stream object through three layers of device-index helpers (8 us a call, thirteen calls per
     forward: a third of the host time of a forward, tools/host_overhead_probe.py)."""
-    if _RAW_STREAM:
-        try:
-            return torch._C._cuda_getCurrentRawStream(torch._C._cuda_getDevice())
-        except AttributeError:
-            pass
-    return torch.cuda.current_stream().cuda_stream
+    try:
+        return torch._C._cuda_getCurrentRawStream(torch._C._cuda_getDevice())
+    except AttributeError:
+        return torch.cuda.current_stream().cuda_stream
 
 
 _side = {}
@@ -722,9 +717,6 @@ def token_attn(q, kv_tok, b, n, heads, dim_head, scale):
     return out
 
 
-_HOST_READ_EVENTS = os.environ.get("EGNN_HOST_READ_EVENTS", "1") != "0"     # 0: every small read-back drains the stream (`.tolist()`)
-
-
 class HostRead:
     """A few words of device memory on their way to the host WITHOUT draining the stream: created right behind the kernel that writes
     them -- a copy to pinned memory and an event behind that copy -- and waited for (`tensor()` / `floats()` / `ints()`) only where the
@@ -735,7 +727,7 @@ class HostRead:
 
     def __init__(self, t):
         self.dtype = t.dtype
-        if t.is_cuda and _HOST_READ_EVENTS:
+        if t.is_cuda:
             self.buf = torch.empty(t.numel(), dtype=t.dtype, pin_memory=True)
             with torch.cuda.device(t.device):                # (the copy and the event on the tensor's device's current stream)
                 self.buf.copy_(t.reshape(-1), non_blocking=True)

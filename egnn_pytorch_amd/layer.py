@@ -26,11 +26,6 @@ from .attention import GlobalLinearAttention
 
 _SPATIAL_ORDER = os.environ.get("EGNN_SPATIAL_ORDER", "1") != "0"     # scheduling knob only; results do not depend on it
 _SLOT_PREP = os.environ.get("EGNN_SLOT_PREP", "1") != "0"             # per-slot records for the edge pass's setup (same results)
-_SIDE_STREAM = os.environ.get("EGNN_SIDE_STREAM", "1") != "0"         # neighbour selection beside the projection GEMM
-# EGNN_Network: the next layer's neighbour selection started right behind this layer's edge pass (it needs the new coordinates only).  Off:
-# measured at c3 / c5 full size it is worth -1.8 % / +0.5 % -- the selection already runs beside the next layer's projection, and two
-# kernels that share the CUs share their throughput (profiles/r04_experiments/network_selection_look_ahead.txt)
-_PREFETCH = os.environ.get("EGNN_PREFETCH", "0") != "0"
 # egnn_edge_args.algo: 0 = the library chooses (persistent wave-per-node kernel where it applies), 1 = the general edge kernel always
 # (A/B measurements; tests/test_gpu_kernels.py checks the two against each other)
 _EDGE_ALGO = int(os.environ.get("EGNN_EDGE_ALGO", "0"))
@@ -40,21 +35,15 @@ _EDGE_ALGO = int(os.environ.get("EGNN_EDGE_ALGO", "0"))
 # otherwise it raises EGNNRangeError.  "exact": always the plain-fp32 kernels (inference only).
 _PRECISION = os.environ.get("EGNN_PRECISION", "fast")
 _DENSE_PW = os.environ.get("EGNN_DENSE_PW", "1") != "0"            # dense layers with N % 32 == 0 on the wave-per-node edge kernel
-_SHARED_FEATS_IMAGE = os.environ.get("EGNN_SHARED_FEATS_IMAGE", "1") != "0"   # 0: a second packed image of feats for the projection
-_NODE_MLP_FUSED = os.environ.get("EGNN_NODE_MLP_FUSED", "1") != "0"   # node_mlp of narrow layers in one launch (csrc/node_mlp_fused.hip)
-_ENTRY_FORK = os.environ.get("EGNN_ENTRY_FORK", "1") != "0"        # ... which then waits for an event recorded at the layer's entry, not for them
-_LATE_SELECT = os.environ.get("EGNN_LATE_SELECT", "1") != "0"      # node-level launches before the neighbour selection (see _forward_hip)
 # Inference forwards as ONE call of the C whole-layer entry (egnn_layer_forward_opts_f32: the same kernels in the same order, enqueued from
 # C) instead of a dozen Python-side launches: ~200 us of host time per forward become a few tens.  Only with every scheduling switch
 # above at its default -- the C entry implements the default policy -- and never while per-kernel timing is on.
 _C_FORWARD = os.environ.get("EGNN_C_FORWARD", "1") != "0"
-_PROJ_ROW_MASK = os.environ.get("EGNN_PROJ_ROW_MASK", "1") != "0"     # projection GEMM skips M-tiles of padded nodes (inference)
 
 
 def _default_policy():
     """every scheduling switch at its default (read at call time: tests flip them on the module)"""
-    return (_SPATIAL_ORDER and _SLOT_PREP and _EDGE_ALGO == 0 and _SHARED_FEATS_IMAGE and _NODE_MLP_FUSED and _ENTRY_FORK and _LATE_SELECT
-            and not _PREFETCH and _PROJ_ROW_MASK)
+    return _SPATIAL_ORDER and _SLOT_PREP and _EDGE_ALGO == 0
 _exact_now = contextvars.ContextVar("egnn_exact_now", default=False)       # per thread / context: concurrent forwards do not see each other's
 _warned_rerun = False
 
@@ -218,6 +207,10 @@ class EGNN(nn.Module):
             raise ValueError(f"edges shape {tuple(edges.shape)} != {(b, n, n, self.edge_dim)}")
         if mask is not None and tuple(mask.shape) != (b, n):
             raise ValueError(f"mask shape {tuple(mask.shape)} != {(b, n)}")
+        if adj_mat is not None and self._use_nearest():               # (a dense layer does not read the adjacency)
+            want = (b, n, n) if adj_mat.dim() == 3 else (n, n)
+            if tuple(adj_mat.shape) != want:
+                raise ValueError(f"adj_mat shape {tuple(adj_mat.shape)} != {want}")
         # the kernels take raw device pointers: a tensor on another device (or on the host) would be read as garbage, not rejected
         for name, t in (("coors", coors), ("mask", mask), ("adj_mat", adj_mat), ("edges", None if isinstance(edges, EdgeLookup) else edges)):
             if t is not None and t.device != feats.device:
@@ -237,10 +230,9 @@ class EGNN(nn.Module):
                 out = self._call(feats, coors, edges, mask, adj_mat, None)[:2]
         return out
 
-    def _call(self, feats, coors, edges, mask, adj_mat, order_hint, presel=None, prefetch=None):
+    def _call(self, feats, coors, edges, mask, adj_mat, order_hint):
         """(node_out, coors_out, order): inference under no_grad, or -- when a graph has to be recorded -- through
-        autograd.EGNNFunction (HIP forward, recompute-in-backward).  presel / prefetch: EGNN_Network's look-ahead of the neighbour
-        selection (`_select_neighbors`), inference only."""
+        autograd.EGNNFunction (HIP forward, recompute-in-backward)."""
         if _ops.RANGE_CHECK == "deferred" and feats.is_cuda:
             _ops.check_range(feats.device, wait=False)              # an earlier call's status, if it has arrived
         if _autograd.wants_grad(self, feats, coors, edges):
@@ -249,8 +241,7 @@ class EGNN(nn.Module):
             order = None                                            # (scheduling hint only; recomputed by the next layer)
         else:
             with torch.no_grad():
-                node_out, coors_out, order = self._forward_with_hint(feats, coors, edges, mask, adj_mat, order_hint, presel=presel,
-                                                                     prefetch=prefetch)[:3]
+                node_out, coors_out, order = self._forward_with_hint(feats, coors, edges, mask, adj_mat, order_hint)[:3]
         return node_out, coors_out, order
 
     def _forward_hip_checked(self, feats, coors, edges, mask, adj_mat, order_hint, want_u=False, drop_seed=None):
@@ -263,41 +254,46 @@ class EGNN(nn.Module):
         """training mode with dropout > 0: every forward draws a fresh mask seed (egnn_pytorch_amd/_dropout.py)"""
         return self.training and self.dropout_p > 0
 
-    def _forward_with_hint(self, feats, coors, edges, mask, adj_mat, order_hint, want_u=False, drop_seed=None, presel=None, prefetch=None,
-                           selection=False):
+    def _forward_with_hint(self, feats, coors, edges, mask, adj_mat, order_hint, want_u=False, drop_seed=None, selection=False):
         """forward + the scheduling permutation it used (EGNN_Network hands layer 0's on to the next layers).  selection: the caller
         reads the neighbour list (idx, rank) from the returned tuple -- the one-call C forward keeps it in its workspace."""
         self._check_inputs(feats, coors, edges, mask, adj_mat)
         _abi.load()
         f_dtype, c_dtype = feats.dtype, coors.dtype
-        if self.float64_kernels():
+        f64 = self.float64_kernels()
+        if f64 and isinstance(edges, EdgeLookup):
+            raise NotImplementedError("float64 modules take the materialised (B,N,N,edge_dim) edge features")
+        if not f64 and torch.float64 in (f_dtype, c_dtype):
+            _warn_float64_once()
+        b, n = feats.shape[:2]
+        if b == 0 or (n == 0 and not self._use_nearest()):
+            # empty batch / empty dense graphs: the reference returns empty outputs (N = 0 on the k-NN path: topk's error)
+            return torch.empty_like(feats), torch.empty_like(coors), None, None, None, self.valid_radius, None, None
+        if f64:
             # a float64 module computes in float64, as the reference does (its own tests run in float64, tests/test_equivariance.py:6):
             # the plain kernels instantiated for double (include/egnn_hip.h, "The float64 path")
-            if isinstance(edges, EdgeLookup):
-                raise NotImplementedError("float64 modules take the materialised (B,N,N,edge_dim) edge features")
             with torch.cuda.device(feats.device):
                 if self.dropout_active() and drop_seed is None:
                     drop_seed = _dropout.draw_seed()
                 out = self._forward_exact(feats.double(), coors.double(), None if edges is None else edges.double(), mask, adj_mat,
+                                          self._neighbour_count(n, adj_mat),
                                           dtype=torch.float64, want_u=want_u,
                                           drop=(self.dropout_p, drop_seed) if self.dropout_active() else None)
             if f_dtype != torch.float64 or c_dtype != torch.float64:
                 out = (out[0].to(f_dtype), out[1].to(c_dtype)) + tuple(out[2:])
             return out
-        if f_dtype == torch.float64 or c_dtype == torch.float64:
-            _warn_float64_once()
-        if (_C_FORWARD and _default_policy() and not want_u and not selection and drop_seed is None and presel is None and prefetch is None and f_dtype == torch.float32
+        if (_C_FORWARD and _default_policy() and not want_u and not selection and drop_seed is None and f_dtype == torch.float32
                 and c_dtype == torch.float32 and _ops._timer is None and not self.dropout_active() and not exact_active()):
             out = self._forward_c(feats, coors, edges, mask, adj_mat, order_hint)
             if out is not None:
                 return out
+        kr = self._neighbour_count(n, adj_mat)                    # (the C entry declined before reading it)
         with torch.cuda.device(feats.device):
             if self.dropout_active() and drop_seed is None:
                 drop_seed = _dropout.draw_seed()
             out = self._forward_hip(feats.float(), coors.float(),
                                     edges if (edges is None or isinstance(edges, EdgeLookup)) else edges.float(), mask, adj_mat, order_hint,
-                                    want_u=want_u, drop=(self.dropout_p, drop_seed) if self.dropout_active() else None,
-                                    presel=presel, prefetch=prefetch)
+                                    want_u=want_u, drop=(self.dropout_p, drop_seed) if self.dropout_active() else None, kr=kr)
         if f_dtype != torch.float32 or c_dtype != torch.float32:
             out = (out[0].to(f_dtype), out[1].to(c_dtype)) + tuple(out[2:])
         return out
@@ -312,83 +308,92 @@ class EGNN(nn.Module):
         """A float64 module runs on the float64 kernels (training-mode dropout included: the plain kernels evaluate the same hash masks)."""
         return self.compute_dtype() == torch.float64
 
-    def _select_outputs(self, coors, adj_mat, order_hint, k):
-        """The four outputs of the k-NN selection (idx, rank, order or None, slots or None), allocated on the LAUNCH stream."""
-        b, n = coors.shape[:2]
-        dev = coors.device
-        want_order = adj_mat is None and 64 <= n <= 4096 and _SPATIAL_ORDER and coors.shape[-1] == 3
-        have_hint = order_hint is not None and tuple(order_hint.shape) == (b, n)
-        return (_ops.empty(b, n, k, dtype=torch.int32, device=dev), _ops.empty(b, n, k, dtype=torch.float32, device=dev),
-                _ops.empty(b, n, dtype=torch.int32, device=dev) if (want_order and not have_hint) else None,
-                _ops.empty(b * n * k, 4, dtype=torch.int32, device=dev) if (_SLOT_PREP and coors.shape[-1] == 3) else None)
+    # ------------------------------------------------------------------ dispatch rules (each stated once, for both launch paths)
+    def _use_nearest(self):
+        """the k-NN path (a neighbour list of K per node) rather than the dense all-pairs one"""
+        return self.num_nearest_neighbors > 0 or self.only_sparse_neighbors
 
-    def _select_neighbors(self, coors, mask, adj_mat, order_hint, fork=None):
-        """(idx, rank, order, slots, K, valid_radius) of egnn_pytorch.py:230-260 for fp32 coordinates on the device: the K nearest
-        neighbours (None, None, None, None, N on the dense path), the Morton order the edge pass schedules by, the per-slot records.
-        Launched on the side stream (EGNN_SIDE_STREAM=0: the current one); whoever consumes the result joins that stream first.
-        fork = (outputs of _select_outputs, event): the side stream waits for that EVENT of the launch stream -- recorded at the layer's
-        entry, before its node-level launches -- instead of for the stream's tail, so the selection runs beside node_prep and the
-        projection although it is enqueued behind them (the outputs were allocated at the same point: a block the allocator recycles
-        from a tensor freed AFTER the event could still be in use by a launch the side stream does not wait for)."""
-        b, n = coors.shape[:2]
-        num_nearest = self.num_nearest_neighbors
-        valid_radius = self.valid_radius
-        use_nearest = num_nearest > 0 or self.only_sparse_neighbors
-        idx = rank = order = slots = None
-        if not use_nearest:
-            # dense all-pairs.  With N % 32 == 0 and the standard layer's shape the wave-per-node edge kernel applies (csrc/edge_pw.hip):
-            # it reads per-slot records, here with j = k.  Only when the batch fills the chip with one wave per node (measured, round 5:
-            # B N = 16 384 ... 32 768 nodes -2 ... -6.5 %; BASELINE.json's c2 -- 2048 nodes, each wave walking 8 rounds -- +25 %, so c2
-            # stays on the general kernel, which splits a node's slots over workgroups).  The records are 16 B N^2 bytes: bounded.
-            if (_SLOT_PREP and _DENSE_PW and b * n >= 8192 and n % 32 == 0 and 32 <= n <= 4096 and coors.shape[-1] == 3 and self.m_dim <= 16
-                    and self.edge_dim == 0 and self.fourier_features == 0 and not self.dropout_active() and b * n * n * 16 <= (1 << 28)):
-                slots = _ops.slot_prep(coors, _ops._u8(mask), None, None, None, valid_radius)
-            return None, None, None, slots, n, valid_radius
+    def _neighbour_count(self, n, adj_mat):
+        """(K, valid_radius) of a call on N-node graphs (egnn_pytorch.py:240-252): N on the dense path; on the k-NN path the module's
+        K -- or, for only_sparse_neighbors with an adjacency, its maximum degree and radius 0."""
+        if not self._use_nearest():
+            return n, self.valid_radius
+        k, valid_radius = self.num_nearest_neighbors, self.valid_radius
         if adj_mat is not None and self.only_sparse_neighbors:
-            num_nearest = _ops.adj_max_degree(adj_mat)                # host sync, as upstream (:249)
-            valid_radius = 0.0
-        k = num_nearest
+            with torch.cuda.device(adj_mat.device):
+                k, valid_radius = _ops.adj_max_degree(adj_mat), 0.0   # host sync, as upstream (:249)
         if k > n:
             raise RuntimeError("selected index k out of range")      # torch.topk's error upstream
-        if k > 0:
-            # Neighbour selection (VALU / scalar bound, no MFMA) and the Morton order (one workgroup per graph) depend on
-            # the coordinates only; the projection GEMM that follows (MFMA bound) depends on the features only.  Forked onto
-            # a side stream they share the CUs instead of queueing (EGNN_SIDE_STREAM=0: one stream); joined before the
-            # edge pass.
-            # k-NN path: neighbours are spatial -> workgroups that own Morton-adjacent nodes share gathered rows in L1.
-            # Scheduling only (results do not depend on it), so a stack of layers reuses the first layer's order:
-            # coordinates move by small steps per layer and the locality survives.
-            mask8 = _ops._u8(mask)
-            want_order = adj_mat is None and 64 <= n <= 4096 and _SPATIAL_ORDER and coors.shape[-1] == 3
-            have_hint = order_hint is not None and tuple(order_hint.shape) == (b, n)
+        return k, valid_radius
 
-            # The four outputs are allocated HERE, on the launch stream, and written by the side stream: the launch stream waits for the
-            # side stream before it reads them, so when they are freed every use is ordered before the launch stream's later work and the
-            # allocator may reuse the blocks at once.  (Allocated inside the fork they belonged to the side stream's pool and needed
-            # record_stream(): four calls per forward and frees deferred to events.)
-            idx_o, rank_o, order_o, slots_o = fork[0] if fork is not None else self._select_outputs(coors, adj_mat, order_hint, k)
+    def _order(self, coors, adj_mat, order_hint):
+        """The Morton order the k-NN edge pass schedules by: `order_hint` when it fits, else a new (B,N) buffer for it (allocated on the
+        launch stream); None when no order is used.  Neighbours are spatial, so workgroups that own Morton-adjacent nodes share gathered
+        rows in L1.  Scheduling only (results do not depend on it), so a stack of layers reuses the first layer's order: coordinates
+        move by small steps per layer and the locality survives."""
+        b, n, cdim = coors.shape
+        if not (_SPATIAL_ORDER and self._use_nearest() and adj_mat is None and cdim == 3 and 64 <= n <= 4096):
+            return None
+        if order_hint is not None and tuple(order_hint.shape) == (b, n) and order_hint.dtype == torch.int32 and order_hint.is_contiguous():
+            return order_hint
+        return _ops.empty(b, n, dtype=torch.int32, device=coors.device)
 
-            def select():
-                # (the Morton order launched AHEAD of the selection was measured in round 6: +- 0.3 %, not kept)
-                idx_, rank_ = _ops.knn_select(coors, mask, adj_mat, k, out=(idx_o, rank_o))
-                order_ = (order_hint if have_hint else _ops.spatial_order(coors, out=order_o, mask8=mask8)) if want_order else None
-                # the edge pass's setup as one coalesced record per slot instead of a chain of dependent loads
-                slots_ = _ops.slot_prep(coors, mask8, idx_, rank_, order_, valid_radius, out=slots_o) if slots_o is not None else None
-                return idx_, rank_, order_, slots_
+    def _dense_pw(self, b, n, cdim):
+        """A dense layer on the wave-per-node edge kernel (csrc/edge_pw.hip), which reads per-slot records, here with j = k: with
+        N % 32 == 0 and the standard layer's shape, and only when the batch fills the chip with one wave per node (measured, round 5:
+        B N = 16 384 ... 32 768 nodes -2 ... -6.5 %; BASELINE.json's c2 -- 2048 nodes, each wave walking 8 rounds -- +25 %, so c2 stays
+        on the general kernel, which splits a node's slots over workgroups).  The records are 16 B N^2 bytes: bounded."""
+        return (_SLOT_PREP and _DENSE_PW and b * n >= 8192 and n % 32 == 0 and 32 <= n <= 4096 and cdim == 3 and self.m_dim <= 16
+                and self.edge_dim == 0 and self.fourier_features == 0 and not self.dropout_active() and b * n * n * 16 <= (1 << 28))
 
-            # (not while per-kernel timing is on: events on two streams would charge one kernel's wait to another)
-            use_side = _SIDE_STREAM and _ops._timer is None
-            side = _ops.side_stream(coors.device) if use_side else None
-            if side is not None:
-                if fork is not None and fork[1] is not None:
-                    side.wait_event(fork[1])
-                else:
-                    side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    idx, rank, order, slots = select()
-            else:
-                idx, rank, order, slots = select()
-        return idx, rank, order, slots, k, valid_radius
+    def _proj_row_mask(self, mask8, b, n, k, cdim, w, want_u, drop):
+        """The projection GEMM's row mask (M-tiles of padded nodes are not computed), or None.  Only where the rows of padded nodes are
+        read by masked-out edges alone: a k-NN layer whose edge pass is the wave-per-node kernel.  Not under autograd or dropout: the
+        backward differentiates through every edge."""
+        if (mask8 is None or want_u or drop is not None or not self._use_nearest() or k < 6 or not _SLOT_PREP or _EDGE_ALGO != 0
+                or _abi.load().egnn_edge_pw_covers(b, n, k, w["S"], self.fourier_features, self.edge_dim, self.m_dim, cdim, 2 * w["Hp"]) != 1):
+            return None
+        return mask8.view(-1)
+
+    def _select_outputs(self, coors, adj_mat, order_hint, k):
+        """The four outputs of the k-NN selection (idx, rank, order or None, slots or None), allocated on the LAUNCH stream: the launch
+        stream waits for the side stream before it reads them, so when they are freed every use is ordered before the launch stream's
+        later work and the allocator may reuse the blocks at once.  (Allocated inside the fork they belonged to the side stream's pool
+        and needed record_stream(): four calls per forward and frees deferred to events.)  order is the taken hint, if any."""
+        b, n = coors.shape[:2]
+        dev = coors.device
+        return (_ops.empty(b, n, k, dtype=torch.int32, device=dev), _ops.empty(b, n, k, dtype=torch.float32, device=dev),
+                self._order(coors, adj_mat, order_hint),
+                _ops.empty(b * n * k, 4, dtype=torch.int32, device=dev) if (_SLOT_PREP and coors.shape[-1] == 3) else None)
+
+    def _select_neighbors(self, coors, mask, adj_mat, order_hint, k, valid_radius, outs, fork=None):
+        """(idx, rank, order, slots) of egnn_pytorch.py:230-260 for fp32 coordinates on the device, K > 0: the K nearest neighbours, the
+        Morton order the edge pass schedules by, the per-slot records, written into `outs` (`_select_outputs`).  Neighbour selection
+        (VALU / scalar bound, no MFMA) and the Morton order (one workgroup per graph) depend on the coordinates only; the projection GEMM
+        (MFMA bound) on the features only: launched on the side stream they share the CUs instead of queueing, and whoever consumes the
+        result joins that stream first.  fork: an event of the launch stream -- recorded at the layer's entry, before its node-level
+        launches -- the side stream waits for instead of the stream's tail, so the selection runs beside node_prep and the projection
+        although it is enqueued behind them.  It reads only what existed at that event: coors, mask, adj_mat and `outs`."""
+        idx_o, rank_o, order_o, slots_o = outs
+        mask8 = _ops._u8(mask)                                      # (a view: the caller made the mask contiguous before the fork)
+
+        def select():
+            # (the Morton order launched AHEAD of the selection was measured in round 6: +- 0.3 %, not kept)
+            idx_, rank_ = _ops.knn_select(coors, mask, adj_mat, k, out=(idx_o, rank_o))
+            order_ = order_o if order_o is None or order_o is order_hint else _ops.spatial_order(coors, out=order_o, mask8=mask8)
+            # the edge pass's setup as one coalesced record per slot instead of a chain of dependent loads
+            slots_ = _ops.slot_prep(coors, mask8, idx_, rank_, order_, valid_radius, out=slots_o) if slots_o is not None else None
+            return idx_, rank_, order_, slots_
+
+        if _ops._timer is not None:
+            return select()             # (one stream while per-kernel timing is on: events on two would charge one kernel's wait to another)
+        side = _ops.side_stream(coors.device)
+        if fork is not None:
+            side.wait_event(fork)
+        else:
+            side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            return select()
 
     def _c_state(self, device):
         """(desc, info, blob on `device`, fused node_mlp image or None) of the C whole-layer entry for the current parameters; None when the
@@ -410,35 +415,24 @@ class EGNN(nn.Module):
     def _forward_c(self, feats, coors, edges, mask, adj_mat, order_hint):
         """The fp32 inference forward as one call of egnn_layer_forward_opts_f32 (include/egnn_hip.h; csrc/layer_api.hip mirrors
         `_forward_hip_impl` launch for launch, so the outputs are the same bits).  Returns `_forward_hip`'s tuple, or None when the call is
-        outside what the C entry covers (edge look-up tables, wide shapes, the wave-per-node kernel on dense batches, empty inputs, another
-        current device): the Python launch sequence below then runs it."""
+        outside what the C entry covers (edge look-up tables, wide shapes, the wave-per-node kernel on dense batches, another current
+        device): the Python launch sequence then runs it.  K is read after those checks, and a call with K = 0 goes to the Python launch
+        sequence from here, with that K: the adjacency's maximum degree is read once per call."""
         b, n, dim = feats.shape
         cdim = coors.shape[-1]
-        use_nearest = self.num_nearest_neighbors > 0 or self.only_sparse_neighbors
+        use_nearest = self._use_nearest()
         dev = feats.device
-        if (isinstance(edges, EdgeLookup) or b == 0 or n == 0 or cdim > 8 or self.m_dim > 64
-                or 2 * self.fourier_features + 1 + self.edge_dim > 16 or dev.index != torch.cuda.current_device()
-                or (adj_mat is not None and (not adj_mat.is_cuda or adj_mat.dtype != torch.bool))):
+        if (isinstance(edges, EdgeLookup) or cdim > 8 or self.m_dim > 64 or 2 * self.fourier_features + 1 + self.edge_dim > 16
+                or dev.index != torch.cuda.current_device() or (adj_mat is not None and adj_mat.dtype != torch.bool)
+                or (not use_nearest and self._dense_pw(b, n, cdim))):
             return None
-        if not use_nearest and (b * n >= 8192 and n % 32 == 0 and 32 <= n <= 4096 and cdim == 3 and self.m_dim <= 16 and self.edge_dim == 0
-                                and self.fourier_features == 0 and _DENSE_PW and b * n * n * 16 <= (1 << 28)):
-            return None                                             # (dense batches that fill the chip: the wave-per-node kernel)
         st = self._c_state(dev)
         if st is None:
             return None
         desc, info, blob_dev, img = st
-        valid_radius = self.valid_radius
-        if use_nearest:
-            k = self.num_nearest_neighbors
-            if adj_mat is not None and self.only_sparse_neighbors:
-                k = _ops.adj_max_degree(adj_mat)                    # host sync, as upstream (:249)
-                valid_radius = 0.0
-            if k > n:
-                raise RuntimeError("selected index k out of range")  # torch.topk's error upstream
-            if k == 0:
-                return None
-        else:
-            k = n
+        kr = k, valid_radius = self._neighbour_count(n, adj_mat)
+        if k == 0:                                                  # (no messages: not covered by the C entry)
+            return self._forward_hip(feats, coors, edges, mask, adj_mat, order_hint, kr=kr)
         feats, coors = feats.contiguous(), coors.contiguous()
         if edges is not None:
             edges = edges.contiguous().float()
@@ -447,19 +441,15 @@ class EGNN(nn.Module):
         lib = _abi.load()
         nbytes = lib.egnn_workspace_bytes(desc, b, n, k)
         # every buffer is allocated HERE, on the launch stream (the side stream writes the selection's part of the workspace between the
-        # two events of this call: `_select_neighbors` has the argument)
+        # two events of this call: `_select_outputs` has the argument)
         ws = _ops.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
         node_out = _ops.empty(b, n, dim, dtype=torch.float32, device=dev) if self.node_mlp is not None else feats
         coors_out = _ops.empty(b, n, cdim, dtype=torch.float32, device=dev) if self.coors_mlp is not None else coors
         opts = _abi.ForwardOpts()
-        order = None
-        if use_nearest and adj_mat is None and 64 <= n <= 4096 and cdim == 3:
-            if order_hint is not None and tuple(order_hint.shape) == (b, n) and order_hint.dtype == torch.int32 and order_hint.is_contiguous():
-                order, opts.order_is_hint = order_hint, 1
-            else:
-                order = _ops.empty(b, n, dtype=torch.int32, device=dev)
-            opts.order = order.data_ptr()
-        if use_nearest and _SIDE_STREAM:
+        order = self._order(coors, adj_mat, order_hint)
+        if order is not None:
+            opts.order, opts.order_is_hint = order.data_ptr(), int(order is order_hint)
+        if use_nearest:
             opts.side_stream, opts.ev_fork, opts.ev_join = _ops.side_handles(dev)
         if img is not None:
             opts.nmf_img = img.data_ptr()
@@ -472,60 +462,63 @@ class EGNN(nn.Module):
         _abi.check(rc, "egnn_layer_forward_opts_f32")
         return node_out, coors_out, order, None, None, valid_radius, None, None
 
-    def _forward_hip(self, feats, coors, edges, mask, adj_mat, order_hint=None, want_u=False, drop=None, presel=None, prefetch=None):
+    def _forward_hip(self, feats, coors, edges, mask, adj_mat, order_hint=None, want_u=False, drop=None, kr=None):
+        """The Python launch sequence; kr = (K, valid_radius) of `_neighbour_count` when the caller has read it already."""
+        if kr is None:
+            kr = self._neighbour_count(feats.shape[1], adj_mat)
         try:
-            return self._forward_hip_impl(feats, coors, edges, mask, adj_mat, order_hint, want_u, drop, presel, prefetch)
+            return self._forward_hip_impl(feats, coors, edges, mask, adj_mat, kr, order_hint, want_u, drop)
         except BaseException:
             # the neighbour selection may still be writing its outputs on the side stream: join it before they are freed (they belong
-            # to the launch stream's pool: `_select_neighbors`)
-            if _SIDE_STREAM and feats.is_cuda:
+            # to the launch stream's pool: `_select_outputs`)
+            if feats.is_cuda:
                 torch.cuda.current_stream().wait_stream(_ops.side_stream(feats.device))
             raise
 
-    def _forward_hip_impl(self, feats, coors, edges, mask, adj_mat, order_hint, want_u, drop, presel, prefetch):
+    def _forward_hip_impl(self, feats, coors, edges, mask, adj_mat, kr, order_hint, want_u, drop):
         # more per-edge scalars than the split-fp16 edge kernels carry (2 fourier + 1 + edge_dim > 16, up to 160): the plain-fp32 kernels
         # ... and more than 8 coordinates (the fused kernels keep x_i - x_j in registers up to 8)
         # ... and heads wider than 64 message channels (the fused kernels hold up to four 16-channel accumulator tiles per edge tile)
         wide_shape = 2 * self.fourier_features + 1 + self.edge_dim > 16 or coors.shape[-1] > 8 or self.m_dim > 64
         if exact_active() or wide_shape:
-            return self._forward_exact(feats, coors, edges, mask, adj_mat, want_u=want_u, drop=drop)
+            return self._forward_exact(feats, coors, edges, mask, adj_mat, kr, want_u=want_u, drop=drop)
         b, n, dim = feats.shape
+        k, valid_radius = kr
         w = self.packed_weights()
         feats = feats.contiguous()
         coors = coors.contiguous()
+        # What the neighbour selection reads on the side stream -- coors, mask, adj_mat -- is made contiguous HERE, before the fork event
+        # below, and every `_u8` of it is a view from then on: a copy enqueued behind that event (a sliced or expanded mask) would be a
+        # kernel the side stream does not wait for, and the selection could read its output before it is written.
+        mask = None if mask is None else mask.contiguous()
+        adj_mat = None if adj_mat is None else adj_mat.contiguous()
+        mask8 = _ops._u8(mask)
         feats2d = feats.view(b * n, dim)
         lookup = edges if isinstance(edges, EdgeLookup) else None
         if lookup is not None:
             edges = lookup.edges
         elif edges is not None:
             edges = edges.contiguous().float()
-        mask8 = _ops._u8(mask)
 
         # ---- neighbour selection (egnn_pytorch.py:230-260)
-        use_nearest = self.num_nearest_neighbors > 0 or self.only_sparse_neighbors
-        if b == 0 or (n == 0 and not use_nearest):
-            # empty batch / empty dense graphs: the reference returns empty outputs (N = 0 on the k-NN path: topk's error)
-            return torch.empty_like(feats), torch.empty_like(coors), None, None, None, self.valid_radius, None, None
-        # (EGNN_Network hands over what the previous layer started on the side stream right behind its edge pass)
-        # When K is known without looking at the data (the k-NN path; not only_sparse_neighbors, whose K is the adjacency's maximum degree),
-        # the node-level launches go FIRST and the selection -- on the side stream, needed by the edge pass only -- is enqueued behind
-        # them: the first kernel of the forward starts ~30 us earlier, which is what a synchronous range check exposes per call.
-        sel = presel
-        late_select = (_LATE_SELECT and sel is None and use_nearest and 0 < self.num_nearest_neighbors <= n
-                       and not (adj_mat is not None and self.only_sparse_neighbors))
-        if sel is None and not late_select:
-            sel = self._select_neighbors(coors, mask, adj_mat, order_hint)
-        fork = None
-        if late_select and _SIDE_STREAM and _ENTRY_FORK and _ops._timer is None:
-            # the selection is enqueued behind the node-level launches but depends on nothing they write: fork point = here
-            fork = (self._select_outputs(coors, adj_mat, order_hint, self.num_nearest_neighbors), _ops.fork_event(feats.device))
-        idx = rank = order = slots = None
-        k, valid_radius = self.num_nearest_neighbors, self.valid_radius
-        if sel is not None:
-            idx, rank, order, slots, k, valid_radius = sel
+        use_nearest = self._use_nearest()
+        sel = outs = fork = None
+        if not use_nearest:
+            sel = None, None, None, (_ops.slot_prep(coors, mask8, None, None, None, valid_radius) if self._dense_pw(b, n, coors.shape[-1])
+                                     else None)
+        elif k > 0:
+            outs = self._select_outputs(coors, adj_mat, order_hint, k)
+            if adj_mat is not None and self.only_sparse_neighbors:
+                sel = self._select_neighbors(coors, mask, adj_mat, order_hint, k, valid_radius, outs)
+            else:
+                # When K is known without looking at the data (not only_sparse_neighbors with an adjacency, whose K is its maximum
+                # degree), the node-level launches go FIRST and the selection -- on the side stream, needed by the edge pass only -- is
+                # enqueued behind them, although it depends on nothing they write: fork point = here.  The first kernel of the forward
+                # starts ~30 us earlier, which is what a synchronous range check exposes per call.
+                fork = _ops.fork_event(feats.device)
 
         node_out, coors_out = feats, coors
-        node_in = u_pre = proj_kept = None
+        node_in = u_pre = proj_kept = idx = rank = order = None
         if k > 0:
             # ---- node-level projections P = feats [W_i ; W_j]^T + [b1 ; 0]
             # (K >= 6: the edge pass feeds P_i to its first-layer MFMA as (fp16 hi, fp16 lo) words)
@@ -536,29 +529,20 @@ class EGNN(nn.Module):
                 # (egnn_pytorch.py:335-336); the edge pass drops m_i into the zero columns
                 # (node_norm = Identity, the reference's default: the two are the same values -- the projection reads the first
                 # `dim` columns of the [feats | 0] image, egnn_linear_hl_lda_f32; 134 MB less to write at the north-star shape)
-                shared = _SHARED_FEATS_IMAGE and w.get("gamma") is None
-                if shared:
+                if w.get("gamma") is None:
                     node_in = feats_hl = _ops.node_prep_hl(feats2d, None, None, None, 1e-5, self.m_dim)
                 else:
                     node_in, feats_hl = _ops.node_prep_hl(feats2d, None, w.get("gamma"), w.get("beta"), w.get("ln_eps", 1e-5),
                                                           self.m_dim, with_raw=True)
             else:
                 feats_hl = _ops.split_f16(feats2d)
-            # (a padded batch: the rows of padded nodes are read by masked-out edges only -- whole tiles of them are not computed.
-            # Not under autograd: the backward differentiates through every edge)
-            proj = _ops.linear_hl(feats_hl, w["Wcat_split"], 2 * hp, w["bcat"], name="node_proj",
-                                  split_cols=hp if pi_split else 0,
-                                  row_mask=mask8.view(-1) if (mask8 is not None and not want_u and drop is None and _PROJ_ROW_MASK
-                                                              and use_nearest and pi_split and _SLOT_PREP and _EDGE_ALGO == 0
-                                                              and _abi.load().egnn_edge_pw_covers(b, n, k, w["S"], self.fourier_features,
-                                                                                                  self.edge_dim, self.m_dim, coors.shape[-1],
-                                                                                                  2 * hp) == 1) else None)
+            proj = _ops.linear_hl(feats_hl, w["Wcat_split"], 2 * hp, w["bcat"], name="node_proj", split_cols=hp if pi_split else 0,
+                                  row_mask=self._proj_row_mask(mask8, b, n, k, coors.shape[-1], w, want_u, drop))
             del feats_hl
             if sel is None:
-                sel = self._select_neighbors(coors, mask, adj_mat, order_hint, fork=fork)
-            idx, rank, order, slots, k_sel, valid_radius = sel
-            assert k_sel == k
-            side_join = use_nearest and k > 0 and _SIDE_STREAM and _ops._timer is None
+                sel = self._select_neighbors(coors, mask, adj_mat, order_hint, k, valid_radius, outs, fork)
+            idx, rank, order, slots = sel
+            side_join = use_nearest and _ops._timer is None
             a = _abi.EdgeArgs()
             a.B, a.N, a.K, a.dim, a.m_dim = b, n, k, dim, self.m_dim
             a.H, a.Hp = w["H"], hp
@@ -604,10 +588,6 @@ class EGNN(nn.Module):
                 a.U_out = u_pre.data_ptr()
             a.algo = _EDGE_ALGO
             _ops.edge_fused(a, feats.device)
-            if prefetch is not None:
-                # the next layer's neighbour selection needs this layer's coordinates and nothing else: started here, on the side
-                # stream, it runs beside this layer's node_mlp and the next layer's projection instead of in front of them
-                prefetch(coors_out, order)
             if u_pre is not None:
                 proj_kept = (proj, pi_split)
             del proj
@@ -616,7 +596,7 @@ class EGNN(nn.Module):
 
         # ---- node update (egnn_pytorch.py:335-337)
         if self.node_mlp is not None:
-            if _NODE_MLP_FUSED and drop is None and "nmf_img" in w:
+            if drop is None and "nmf_img" in w:
                 # narrow layers (dim <= 256): both Linears in one launch, the hidden activation stays in registers
                 node_out = _ops.node_mlp_fused(node_in, w["nmf_img"], w["W5_split"][2], w["b5"], w["W6_split"][2], w["b6"], feats2d,
                                                dim, self.m_dim).view(b, n, dim)
@@ -627,9 +607,10 @@ class EGNN(nn.Module):
         return node_out, coors_out, order, idx, rank, valid_radius, u_pre, proj_kept
 
 
-    def _forward_exact(self, feats, coors, edges, mask, adj_mat, dtype=torch.float32, want_u=False, drop=None):
+    def _forward_exact(self, feats, coors, edges, mask, adj_mat, kr, dtype=torch.float32, want_u=False, drop=None):
         """The layer on the plain-fp32 kernels (include/egnn_hip.h, "The wide-range path"): exact-fp32 GEMMs, fp32 node_norm, the edge
-        pass as fp32 VALU arithmetic on the module's own weight tensors.  Same neighbour selection, same return tuple as _forward_hip.
+        pass as fp32 VALU arithmetic on the module's own weight tensors.  Same arguments (kr = (K, valid_radius) of `_neighbour_count`),
+        same neighbour selection, same return tuple as _forward_hip.
         dtype = torch.float64: the same kernels instantiated for double ("The float64 path"; feats / coors / edges are float64).
         drop = (p, seed): training-mode dropout -- the fused kernels' hash masks at the three sites (egnn_edge_exact_args.drop_*,
         egnn_drop_silu_*)."""
@@ -644,22 +625,10 @@ class EGNN(nn.Module):
         elif edges is not None:
             edges = edges.contiguous().to(dtype)
         mask8 = _ops._u8(mask)
-        num_nearest, valid_radius = self.num_nearest_neighbors, self.valid_radius
-        use_nearest = num_nearest > 0 or self.only_sparse_neighbors
+        k, valid_radius = kr
         idx = rank = None
-        if b == 0 or (n == 0 and not use_nearest):
-            return torch.empty_like(feats), torch.empty_like(coors), None, None, None, valid_radius, None, None
-        if use_nearest:
-            if adj_mat is not None and self.only_sparse_neighbors:
-                num_nearest = _ops.adj_max_degree(adj_mat)
-                valid_radius = 0.0
-            k = num_nearest
-            if k > n:
-                raise RuntimeError("selected index k out of range")
-            if k > 0:
-                idx, rank = _ops.knn_select(coors, mask, adj_mat, k)
-        else:
-            k = n
+        if self._use_nearest() and k > 0:
+            idx, rank = _ops.knn_select(coors, mask, adj_mat, k)
         f32 = lambda t: t.detach().to(dtype).contiguous()                # noqa: E731  (the module's tensors in the compute dtype)
         node_out, coors_out, m_i = feats, coors, None
         u_pre = proj_keep = None                                         # want_u (forward under autograd): u (E, m_dim) and the projection table
@@ -850,24 +819,10 @@ class EGNN_Network(nn.Module):
             global_tokens = self.global_tokens[None].expand(b, -1, -1)
         coor_changes = [coors]
         order = None
-        # Inference look-ahead (EGNN_PREFETCH=1; off by default, see _PREFETCH): layer l + 1's neighbour selection depends on layer l's
-        # coordinates only, which its edge pass writes -- before node_mlp.  Started right behind that edge pass on the side stream, it
-        # runs beside node_mlp (and the next layer's attention block / projection) as well.
-        look_ahead = (_PREFETCH and not torch.is_grad_enabled() and coors.is_cuda and coors.dtype == torch.float32
-                      and _SIDE_STREAM and _ops._timer is None and not exact_active())
-        pending = [None]
-        layers = list(self.layers)
-        for li, (global_attn, egnn) in enumerate(layers):
+        for global_attn, egnn in self.layers:
             if global_attn is not None:
                 feats, global_tokens = global_attn(feats, global_tokens, mask=mask)           # :445-446
-            presel, pending[0] = pending[0], None
-            prefetch = None
-            if look_ahead and li + 1 < len(layers):
-                nxt = layers[li + 1][1]
-                if (nxt.num_nearest_neighbors > 0 or nxt.only_sparse_neighbors) and not nxt.float64_kernels():
-                    def prefetch(coors_out, order_used, nxt=nxt):
-                        pending[0] = nxt._select_neighbors(coors_out, mask, adj_mat, order_used)
-            feats, coors, order = egnn._call(feats, coors, edges, mask, adj_mat, order, presel=presel, prefetch=prefetch)
+            feats, coors, order = egnn._call(feats, coors, edges, mask, adj_mat, order)
             coor_changes.append(coors)
         if return_coor_changes:
             return feats, coors, coor_changes

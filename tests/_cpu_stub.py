@@ -30,7 +30,7 @@ def _select(layer, coors, mask, adj_mat):
 def install():
     from egnn_pytorch_amd import _ops, autograd as A, layer as L
 
-    def forward_stub(self, feats, coors, edges, mask, adj_mat, order_hint, want_u=False, drop_seed=None, presel=None, prefetch=None):
+    def forward_stub(self, feats, coors, edges, mask, adj_mat, order_hint, want_u=False, drop_seed=None):
         idx, rank, radius = _select(self, coors, mask, adj_mat)
         with torch.no_grad():
             node, co = A.layer_given_neighbors(self, feats, coors, edges, mask, idx, rank, radius)

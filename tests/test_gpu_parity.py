@@ -877,3 +877,102 @@ def test_inputs_on_another_device_are_rejected_not_read():
     with pytest.raises(RuntimeError, match="same device"):
         layer(feats, coors.cpu())
     layer(feats, coors, mask=mask.cuda())
+
+
+@pytest.mark.parametrize("path", ["python", "autograd", "network_edge_lookup"])
+@pytest.mark.parametrize("kind", ["sliced", "expanded"])
+def test_non_contiguous_masks_give_the_bits_of_contiguous_ones(kind, path, monkeypatch):
+    """The neighbour selection runs on a side stream that waits for an event recorded at the layer's entry: a mask made contiguous
+    behind that event (a slice of a wider mask, one row expanded over the batch) would be a copy it does not wait for.  Same bits as
+    the contiguous mask on the paths that launch from Python: the per-kernel sequence (EGNN_C_FORWARD=0), a forward under autograd,
+    EGNN_Network inference with edge look-up tables.  (A timing-dependent race: this guards, it need not reproduce it.)"""
+    from egnn_pytorch_amd import EGNN, EGNN_Network, layer as L
+    torch.manual_seed(7)
+    g = torch.Generator().manual_seed(4)
+    b, n = 3, 200
+    if kind == "sliced":
+        mask = (torch.rand(b, n + 17, generator=g) < 0.7).cuda()[:, :n]
+    else:
+        mask = (torch.arange(n) < n - 23).cuda()[None].expand(b, n)
+    assert not mask.is_contiguous()
+    coors = torch.randn(b, n, 3, generator=g).cuda()
+    if path == "network_edge_lookup":
+        net = EGNN_Network(depth=2, dim=32, num_tokens=10, num_edge_tokens=5, edge_dim=4, num_nearest_neighbors=16).cuda().eval()
+        for p in net.parameters():
+            if p.dim() > 1 and p.shape[0] > 1 and p.shape[1] > 1:
+                p.mul_(20.0)
+        seq = torch.randint(0, 10, (b, n), generator=g).cuda()
+        etok = torch.randint(0, 5, (b, n, n), generator=g).cuda()
+
+        def run(m):
+            return net(seq, coors, edges=etok, mask=m)
+    else:
+        layer = EGNN(dim=32, num_nearest_neighbors=16, norm_coors=True).cuda().eval()
+        for p in layer.parameters():
+            p.mul_(30.0)
+        feats = torch.randn(b, n, 32, generator=g).cuda()
+        if path == "python":
+            monkeypatch.setattr(L, "_C_FORWARD", False)
+
+        def run(m):
+            if path == "python":
+                return layer(feats, coors, mask=m)
+            with torch.enable_grad():
+                out = layer(feats.requires_grad_(), coors, mask=m)
+            assert out[0].requires_grad
+            return [t.detach() for t in out]
+    got, want = run(mask), run(mask.contiguous())
+    torch.cuda.synchronize()
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+
+
+@pytest.mark.parametrize("c_forward", [True, False], ids=["one_call", "python"])
+def test_adjacency_of_another_shape_is_rejected_not_read(c_forward, monkeypatch):
+    """A k-NN layer reads adj_mat as (N,N) or (B,N,N) bytes: any other shape -- (1,N,N) with B > 1 included, it is not broadcast --
+    raises ValueError before anything is launched, on the one-call C path and on the per-kernel sequence alike.  A dense layer does
+    not read the adjacency (as upstream) and keeps ignoring it."""
+    from egnn_pytorch_amd import EGNN, layer as L
+    monkeypatch.setattr(L, "_C_FORWARD", c_forward)
+    b, n = 2, 16
+    feats, coors = torch.randn(b, n, 16).cuda(), torch.randn(b, n, 3).cuda()
+    bad = [torch.ones(n + 1, n + 1, dtype=torch.bool).cuda(), torch.ones(b, n, n + 1, dtype=torch.bool).cuda(),
+           torch.ones(1, n, n, dtype=torch.bool).cuda()]
+    chain = (torch.arange(n)[:, None] - torch.arange(n)[None, :]).abs() <= 1
+    for kw in (dict(num_nearest_neighbors=4), dict(only_sparse_neighbors=True)):
+        layer = EGNN(dim=16, **kw).cuda().eval()
+        for adj in bad:
+            with pytest.raises(ValueError, match="adj_mat shape"):
+                layer(feats, coors, adj_mat=adj)
+        for adj in (chain.cuda(), chain[None].expand(b, n, n).cuda()):
+            layer(feats, coors, adj_mat=adj)
+    dense = EGNN(dim=16).cuda().eval()
+    want = dense(feats, coors)
+    for adj in bad:
+        got = dense(feats, coors, adj_mat=adj)
+        assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("degree", [0, 3], ids=["no_edges", "chain"])
+def test_adjacency_degree_is_read_once_per_forward(degree, monkeypatch):
+    """only_sparse_neighbors with an adjacency: K is its maximum degree, one device->host read per forward -- also when the one-call
+    C entry hands the call to the per-kernel sequence (K = 0, no messages).  Same bits as the per-kernel sequence on its own."""
+    from egnn_pytorch_amd import EGNN, _ops, layer as L
+    torch.manual_seed(2)
+    b, n = 2, 48
+    layer = EGNN(dim=16, only_sparse_neighbors=True, norm_feats=True).cuda().eval()
+    for p in layer.parameters():
+        p.mul_(30.0)
+    feats, coors = torch.randn(b, n, 16).cuda(), torch.randn(b, n, 3).cuda()
+    i = torch.arange(n)
+    adj = (((i[:, None] - i[None, :]).abs() <= 1) & (degree > 0)).cuda()
+    reads = []
+    orig = _ops.adj_max_degree
+    monkeypatch.setattr(_ops, "adj_max_degree", lambda a: reads.append(1) or orig(a))
+    got = layer(feats, coors, adj_mat=adj)
+    assert len(reads) == 1
+    monkeypatch.setattr(L, "_C_FORWARD", False)
+    want = layer(feats, coors, adj_mat=adj)
+    assert len(reads) == 2
+    torch.cuda.synchronize()
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
