@@ -10,7 +10,7 @@ import contextvars
 import threading
 import time
 import os
-from ctypes import byref
+from ctypes import byref, c_int64
 
 import torch
 
@@ -693,6 +693,43 @@ def edge_features_gather(lookup, idx, b, n, k):
                                                        _ptr(out), _stream())
     _abi.check(rc, "egnn_edge_features_gather_f32")
     return out
+
+
+def edge_features_grad(lookup, idx, b, n, k, g, want_tok=True, want_deg=True, g_edges=None):
+    """The transpose of `edge_features_gather` -- egnn_edge_features_grad_f32: g (B N K, >= edge_dim) fp32 rows whose first
+    lookup.width columns are d loss / d the gathered features (row stride g.stride(0)) -> (g_tok_emb (V1, d1) or None,
+    g_deg_emb (V2, d2) or None), sums in a fixed order.  g_edges: a zeroed (B,N,N,d1) fp32 tensor for dense float edges, which
+    receives its rows in place.  lookup's label tensors are read for graphs [0, b): pass a lookup sliced to the graphs of g."""
+    dev = g.device
+    if g.dim() != 2 or g.stride(1) != 1 or g.shape[0] != b * n * k or g.shape[1] < lookup.width:
+        raise ValueError(f"edge_features_grad: g {tuple(g.shape)} / strides {g.stride()} for {b * n * k} edges of width {lookup.width}")
+    if g.dtype != torch.float32:
+        raise TypeError("edge_features_grad: g must be float32")
+    on1 = want_tok and lookup.tok is not None
+    on2 = want_deg and lookup.deg is not None
+    v1 = lookup.tok_emb.shape[0] if on1 else 0
+    v2 = lookup.deg_emb.shape[0] if on2 else 0
+    g_tok = empty(v1, lookup.d1, dtype=torch.float32, device=dev) if on1 else None
+    g_deg = empty(v2, lookup.d2, dtype=torch.float32, device=dev) if on2 else None
+    if g_edges is not None and (g_edges.dtype != torch.float32 or not g_edges.is_contiguous()
+                                or tuple(g_edges.shape) != (b, n, n, lookup.d1)):
+        raise ValueError("edge_features_grad: g_edges must be a contiguous (B,N,N,d1) float32 tensor")
+    if idx is not None and (idx.dtype != torch.int32 or not idx.is_contiguous() or tuple(idx.shape) != (b, n, k)):
+        raise ValueError(f"edge_features_grad: idx must be a contiguous ({b}, {n}, {k}) int32 tensor")
+    for lab in ((lookup.tok,) if on1 else ()) + ((lookup.deg,) if on2 else ()):
+        if not lab.is_contiguous() or tuple(lab.shape) != (b, n, n):
+            raise ValueError(f"edge_features_grad: labels {tuple(lab.shape)} != {(b, n, n)}")
+    lib = _abi.load()
+    args = (_ptr(g), g.stride(0), _ptr(lookup.tok) if on1 else None, v1, lookup.d1, _ptr(lookup.deg) if on2 else None, v2,
+            lookup.d2, _ptr(idx), b, n, k, _ptr(g_tok), _ptr(g_deg), _ptr(g_edges))
+    nw = c_int64(0)
+    _abi.check(lib.egnn_edge_features_grad_f32(*args, None, byref(nw), _stream()), "egnn_edge_features_grad_f32")
+    work = empty(max(1, nw.value), dtype=torch.float32, device=dev)
+    nw = c_int64(work.numel())
+    with _timed("edge_features_grad"):
+        rc = lib.egnn_edge_features_grad_f32(*args, _ptr(work), byref(nw), _stream())
+    _abi.check(rc, "egnn_edge_features_grad_f32")
+    return g_tok, g_deg
 
 
 def induced_attn(q, kv, mask, b, n, heads, dim_head, scale):

@@ -117,8 +117,9 @@ def _per_edge(module, x):
     return x
 
 
-def edge_scalars(layer, coors, edges, idx):
-    """rel = x_i - x_j and the per-edge scalars [fourier(d), d, e_ij] in the column order of edge_mlp.0.weight (:282-285)."""
+def edge_scalars(layer, coors, edges, idx, edges_by_k=False):
+    """rel = x_i - x_j and the per-edge scalars [fourier(d), d, e_ij] in the column order of edge_mlp.0.weight (:282-285).
+    edges_by_k: `edges` are the (B,N,K,edge_dim) features of the selected pairs already (egnn_edge_features_gather_f32)."""
     b, n, _ = coors.shape
     if idx is None:
         rel = coors[:, :, None, :] - coors[:, None, :, :]                          # (B,N,N,C)
@@ -127,7 +128,10 @@ def edge_scalars(layer, coors, edges, idx):
         k = idx.shape[-1]
         bi = torch.arange(b, device=coors.device)[:, None, None]
         rel = coors[:, :, None, :] - coors[bi, idx]                               # (B,N,K,C)
-        e_ij = None if edges is None else torch.gather(edges, 2, idx[..., None].expand(b, n, k, edges.shape[-1]))
+        if edges is None or edges_by_k:
+            e_ij = edges
+        else:
+            e_ij = torch.gather(edges, 2, idx[..., None].expand(b, n, k, edges.shape[-1]))
     dist = (rel ** 2).sum(dim=-1, keepdim=True)
     scal = _fourier(dist, layer.fourier_features) if layer.fourier_features > 0 else dist
     if e_ij is not None:
@@ -279,16 +283,18 @@ def tail_edge_backward(layer, u, coors, idx, pair_mask, g_coors_out, g_msum):
                 m=mm.reshape(e, m), m0=m0.reshape(e, m), g_gate=g_gate)
 
 
-def layer_given_neighbors(layer, feats, coors, edges, mask, idx, rank, valid_radius, factorised=True, drop=None, graph_offset=0):
+def layer_given_neighbors(layer, feats, coors, edges, mask, idx, rank, valid_radius, factorised=True, drop=None, graph_offset=0,
+                          edges_by_k=False):
     """EGNN.forward (egnn_pytorch.py:262-341) for given neighbours.
     idx (B,N,K) int64 / rank (B,N,K): the selection of :258 (None, None = dense all-pairs, K = N).
+    edges_by_k: `edges` are (B,N,K,edge_dim), the features of the selected pairs (see `edge_scalars`).
     Differentiable in feats, coors, edges and the parameters of `layer`.
     factorised: evaluate the first Linear of edge_mlp as (W_i h_i + b) + W_j h_j + W_s s_ij with the dim-wide products done
     once per node -- the same factorisation the HIP forward uses, 16x fewer flops than Linear(cat(...)) at
     the north-star shape, identical mathematics; False = the reference's literal cat + Linear."""
     b, n, dim = feats.shape
     dense = idx is None
-    rel, scal = edge_scalars(layer, coors, edges, idx)
+    rel, scal = edge_scalars(layer, coors, edges, idx, edges_by_k)
     lin = layer.edge_mlp[0]
     if factorised:
         w_i, w_j, w_s = lin.weight[:, :dim], lin.weight[:, dim:2 * dim], lin.weight[:, 2 * dim:]
@@ -336,11 +342,72 @@ def _dropout_native_ok(layer):
             and os.environ.get("EGNN_TAIL_SCALAR", "0") != "1" and os.environ.get("EGNN_BWD_DROP_NATIVE", "1") != "0")
 
 
+def _ops_mod():
+    from . import _ops
+    return _ops
+
+
+# EGNNFunction's inputs ahead of the layer's parameters: (layer, order_hint, mask, adj, feats, coors, edges, lookup, tok_emb, deg_emb).
+# The three backward paths see (and return) the layout without inputs 7 .. 9 -- (..., edges, *params) -- and EGNNFunction.backward
+# adds the tables' gradients (ctx.table_grads) back in.
+_NPRE = 10
+
+
+def _need(ctx):
+    """needs_input_grad in the layout of the backward paths: (layer, order_hint, mask, adj, feats, coors, edges, *params)"""
+    need = ctx.needs_input_grad
+    return need if not getattr(ctx, "table_inputs", False) else need[:7] + need[_NPRE:]
+
+
+class _LookupGrads:
+    """The gradients of an EdgeLookup's tables (EGNNFunction inputs 6, 8, 9) in the backward: per chunk of graphs `add` hands the
+    edge columns of d loss / d per-edge scalars to egnn_edge_features_grad_f32; the embedding gradients of the chunks are summed in
+    chunk order, the dense float edges' rows are stored into a zeroed (B,N,N,d1) tensor.  Nothing else of size B N^2 is allocated."""
+
+    def __init__(self, ctx, b, n, device):
+        self.ctx = ctx
+        self.lookup = ctx.lookup
+        self.dtypes = ctx.table_dtypes
+        need = ctx.needs_input_grad                         # (EGNNFunction's own layout: the tables are inputs 6, 8, 9)
+        self.want = (bool(need[6]) and self.lookup.edges is not None, bool(need[8]), bool(need[9]))
+        self.g_edges = torch.zeros(b, n, n, self.lookup.d1, dtype=torch.float32, device=device) if self.want[0] else None
+        self.tok = self.deg = None
+
+    @property
+    def active(self):
+        return any(self.want)
+
+    def add(self, lo, hi, i32, n, k, g_rows):
+        """graphs [lo, hi): i32 their neighbour list (None: dense), g_rows ((hi - lo) n k, >= width) rows whose first `width` columns are
+        d loss / d the gathered features."""
+        if not self.active or k == 0:
+            return
+        ge = None if self.g_edges is None else self.g_edges[lo:hi]
+        t, d = _ops_mod().edge_features_grad(self.lookup.graphs(lo, hi), i32, hi - lo, n, k, g_rows, want_tok=self.want[1],
+                                             want_deg=self.want[2], g_edges=ge)
+        if t is not None:
+            self.tok = t if self.tok is None else self.tok + t
+        if d is not None:
+            self.deg = d if self.deg is None else self.deg + d
+
+    def outputs(self):
+        """the gradient of the dense float edges (input 6, or None); those of tok_emb / deg_emb (inputs 8, 9) go to ctx.table_grads,
+        where EGNNFunction.backward picks them up (the backward paths return the layout (..., edges, *params))"""
+        live = self.lookup.live
+        tables = []
+        for on, g, w, dt in ((self.want[1], self.tok, live[1], self.dtypes[1]), (self.want[2], self.deg, live[2], self.dtypes[2])):
+            tables.append((torch.zeros(w.shape, dtype=torch.float32, device=w.device) if g is None else g).to(dt) if on else None)
+        self.ctx.table_grads = tuple(tables)
+        return self.g_edges.to(self.dtypes[0]) if self.want[0] else None
+
+
 class EGNNFunction(torch.autograd.Function):
     """forward: HIP kernels; backward: `_backward_native` / `_backward_exact` / `_backward_recompute` (module docstring)."""
 
     @staticmethod
-    def forward(ctx, layer, order_hint, mask, adj_mat, feats, coors, edges, *params):
+    def forward(ctx, layer, order_hint, mask, adj_mat, feats, coors, edges, lookup, tok_emb, deg_emb, *params):
+        # edges: a dense (B,N,N,edge_dim) tensor -- or, with `lookup` (layer.EdgeLookup), its dense float edges if it has any; tok_emb /
+        # deg_emb: the embedding weights behind `lookup` (lookup.live), inputs here so that they receive gradients
         # the native backward computes in fp32 like the forward: float64 / bfloat16 / float16 modules and inputs pass through
         # the same boundary conversion (gradients are returned in the callers' dtypes)
         # training-mode dropout: the forward kernels draw their masks from a hash of (seed, site, row, unit); the backward re-evaluates
@@ -363,7 +430,8 @@ class EGNNFunction(torch.autograd.Function):
         exact_native = bool(_NATIVE_EXACT and exact_path and s_in <= (40 if f64 else 80) and feats.is_cuda)
         with torch.no_grad():
             node_out, coors_out, order, idx, rank, valid_radius, u_pre, proj = layer._forward_hip_checked(
-                feats, coors, edges, mask, adj_mat, order_hint, want_u=native or exact_native, drop_seed=None if drop is None else drop[1])
+                feats, coors, edges if lookup is None else lookup, mask, adj_mat, order_hint, want_u=native or exact_native,
+                drop_seed=None if drop is None else drop[1])
         ctx.drop = drop
         ctx.set_materialize_grads(False)
         ctx.exact_native = exact_native and u_pre is not None
@@ -375,10 +443,21 @@ class EGNNFunction(torch.autograd.Function):
             b, n = feats.shape[:2]
             idx = torch.empty(b, n, 0, dtype=torch.int32, device=feats.device)
             rank = torch.empty(b, n, 0, dtype=torch.float32, device=feats.device)
+        ctx.lookup = lookup
+        if lookup is not None:
+            # the backward differentiates from the (B,N,K,edge_dim) features of the selected pairs, as the edge pass read them -- E x D,
+            # not B N^2 D -- and hands d loss / d them to egnn_edge_features_grad_f32 (`_LookupGrads`)
+            b, n = feats.shape[:2]
+            k = n if idx is None else idx.shape[-1]
+            with torch.no_grad():
+                edges = (_ops_mod().edge_features_gather(lookup, idx, b, n, k) if k > 0 else
+                         torch.empty(b, n, 0, lookup.width, dtype=torch.float32, device=feats.device))
+            ctx.table_dtypes = tuple(None if t is None else t.dtype for t in lookup.live)
         ctx.layer = layer
         ctx.has_u = u_pre is not None                    # (E, 16 ceil(m_dim / 16)) fp32: E x m, not E x H
         ctx.valid_radius = valid_radius
         ctx.has_edges = edges is not None
+        ctx.edges_by_k = lookup is not None                  # (the saved `edges` are the gathered (B,N,K,D) features)
         none = feats.new_empty(0)
         ctx.save_for_backward(feats, coors, edges if edges is not None else none, mask if mask is not None else none,
                               idx if idx is not None else none, rank if rank is not None else none,
@@ -404,19 +483,23 @@ class EGNNFunction(torch.autograd.Function):
         # (set_materialize_grads(False): an output the loss does not depend on arrives as None, not as zeros)
         ctx.dead_outputs = (g_node is None, g_coors is None)
         if g_node is None and g_coors is None:
-            return (None,) * (7 + len(ctx.param_versions))
+            return (None,) * (_NPRE + len(ctx.param_versions))
         for p, v in zip(ctx.layer.parameters(), ctx.param_versions):
             if p._version != v:
                 raise RuntimeError("one of the variables needed for gradient computation has been modified by an inplace "
                                    "operation: a parameter of egnn_pytorch_amd.EGNN changed between forward and backward "
                                    f"(version {p._version}, expected {v})")
+        ctx.table_inputs, ctx.table_grads = True, (None, None)
         if ctx.has_u:
             from . import _ops
             if getattr(ctx, "exact_native", False):
-                return _backward_exact(ctx, g_node, g_coors)
-            with _ops.backward_status():            # range bits of these kernels go to the backward's status word
-                return _backward_native(ctx, g_node, g_coors)
-        return _backward_recompute(ctx, g_node, g_coors)
+                out = _backward_exact(ctx, g_node, g_coors)
+            else:
+                with _ops.backward_status():        # range bits of these kernels go to the backward's status word
+                    out = _backward_native(ctx, g_node, g_coors)
+        else:
+            out = _backward_recompute(ctx, g_node, g_coors)
+        return tuple(out[:7]) + (None,) + ctx.table_grads + tuple(out[7:])
 
 
 def _pooled_messages(layer, u, m0, i64, r0, valid_radius):
@@ -550,7 +633,7 @@ def _backward_exact(ctx, g_node, g_coors):
     edges = None if edges is None else edges.to(dtype)
     rank = None if rank is None else rank.to(dtype)
     params = list(layer.parameters())
-    need = ctx.needs_input_grad
+    need = _need(ctx)
     b, n, dim = feats.shape
     dev = feats.device
     k = idx32.shape[-1] if idx32 is not None else n
@@ -562,7 +645,9 @@ def _backward_exact(ctx, g_node, g_coors):
     tail_params = [p for p in params if id(p) not in head]
     grads = {id(p): torch.zeros_like(p, dtype=dtype) for p in params}
     g_feats, g_coors_in = torch.zeros_like(feats), torch.zeros_like(coors)
-    want_ge = edges is not None and need[6]
+    by_k = getattr(ctx, "edges_by_k", False)
+    lk = _LookupGrads(ctx, b, n, dev) if by_k else None                  # (edge look-up tables: their gradients per chunk)
+    want_ge = edges is not None and need[6] and not by_k
     g_edges = torch.zeros_like(edges) if want_ge else None
     g_node = torch.zeros_like(feats) if g_node is None else g_node.to(dtype)
     g_coors = torch.zeros_like(coors) if g_coors is None else g_coors.to(dtype)
@@ -588,7 +673,7 @@ def _backward_exact(ctx, g_node, g_coors):
         with torch.enable_grad():
             c = c0.detach().requires_grad_(True)
             e = None if e0 is None else e0.detach().requires_grad_(want_ge)
-            rel, scal = edge_scalars(layer, c, e, i64)                            # (the scalars' own graph: step 4)
+            rel, scal = edge_scalars(layer, c, e, i64, by_k)                      # (the scalars' own graph: step 4)
         if m <= 64 and _TAIL_GENERIC:
             # ---- 1. behind u, in closed form: the pooled messages (E x m element-wise), node_norm / node_mlp on the exact GEMMs, the
             # per-edge chain on egnn_edge_tail_exact_bwd_* with its parameter gradients contracted on the exact GEMMs
@@ -638,7 +723,7 @@ def _backward_exact(ctx, g_node, g_coors):
             g_scal = _ops.empty(ec, s_in, dtype=dtype, device=dev)
             a = _abi.EdgeExactBwdArgs()
             a.B, a.N, a.K, a.m_dim, a.H = bc, n, k, m, h
-            a.fourier, a.edge_dim, a.coor_dim, a.edges_by_k = layer.fourier_features, layer.edge_dim, cdim, 0
+            a.fourier, a.edge_dim, a.coor_dim, a.edges_by_k = layer.fourier_features, layer.edge_dim, cdim, int(by_k)
             pc = proj[lo * n:hi_ * n]
             a.Pi, a.Pj, a.ldp = pc.data_ptr(), pc.data_ptr() + esz * hq, 2 * hq
             a.Ws, a.ldws = w1.data_ptr() + esz * 2 * dim, w1.shape[1]
@@ -663,6 +748,8 @@ def _backward_exact(ctx, g_node, g_coors):
             gw1[:, dim:2 * dim] += _ops.linear_f32(gpj_t, f_t, dim, bn, name="bwd_exact_dw1")
             grads[id(lin0.bias)] += gpi.sum(dim=0)
             del gpi, gpi_t, gpj, gpj_t, f_t
+            if lk is not None:                                            # the edge columns of d/d scalars -> the tables
+                lk.add(lo, hi_, i32, n, k, g_scal[:, s_in - layer.edge_dim:])
         # ---- 4. d loss / d scalars -> coordinates (squared distance, fourier terms) and edge features
         sg = torch.autograd.grad([scal], [c] + ([e] if want_ge else []), [g_scal.view_as(scal)], allow_unused=True)
         if sg[0] is not None:
@@ -673,7 +760,7 @@ def _backward_exact(ctx, g_node, g_coors):
     out_params = [grads[id(p)].to(op.dtype) if (need[7 + i] and id(p) not in unused) else None
                   for i, (p, op) in enumerate(zip(params, orig_params))]
     return (None, None, None, None, g_feats.to(in_dtypes[0]) if need[4] else None, g_coors_in.to(in_dtypes[1]) if need[5] else None,
-            g_edges.to(in_dtypes[2]) if (want_ge and need[6]) else None) + tuple(out_params)
+            lk.outputs() if lk is not None else (g_edges.to(in_dtypes[2]) if (want_ge and need[6]) else None)) + tuple(out_params)
 
 
 def _unused_params(layer, ctx=None):
@@ -884,7 +971,7 @@ def _backward_native(ctx, g_node, g_coors):
     g_node = None if g_node is None else g_node.float()
     g_coors = None if g_coors is None else g_coors.float()
     params = list(layer.parameters())
-    need = ctx.needs_input_grad                          # (layer, order_hint, mask, adj, feats, coors, edges, *params)
+    need = _need(ctx)                                    # (layer, order_hint, mask, adj, feats, coors, edges, *params)
     b, n, dim = feats.shape
     k = idx32.shape[-1] if idx32 is not None else n
     m = layer.m_dim
@@ -900,7 +987,9 @@ def _backward_native(ctx, g_node, g_coors):
         off += p.numel()
     g_feats = torch.zeros_like(feats)
     g_coors_in = torch.zeros_like(coors)
-    want_ge = edges is not None and need[6]                 # (the (B,N,N,edge_dim) input: its gradient only if somebody asked for it)
+    by_k = getattr(ctx, "edges_by_k", False)
+    lk = _LookupGrads(ctx, b, n, feats.device) if by_k else None        # (edge look-up tables: their gradients per chunk)
+    want_ge = edges is not None and need[6] and not by_k    # (the (B,N,N,edge_dim) input: its gradient only if somebody asked for it)
     g_edges = torch.zeros_like(edges) if want_ge else None
     if g_node is None:
         g_node = torch.zeros_like(feats)
@@ -1018,7 +1107,7 @@ def _backward_native(ctx, g_node, g_coors):
                         with torch.no_grad():
                             rel, scal = edge_scalars(layer, c0, None, i64)
                 else:
-                    rel, scal = edge_scalars(layer, c, e, i64)                               # (only the scalars' graph is used below)
+                    rel, scal = edge_scalars(layer, c, e, i64, by_k)                         # (only the scalars' graph is used below)
             if f0.is_cuda and _GRAD_GEMM:
                 g_f, g_mi = _node_mlp_backward(layer, w, f, m_i[..., :m], g_node[lo:hi_], grads_by_id, drop, lo * n, overlap=early)
                 g_feats[lo:hi_] += g_f
@@ -1098,7 +1187,7 @@ def _backward_native(ctx, g_node, g_coors):
             with torch.enable_grad():
                 c = c0.detach().requires_grad_(True)
                 e = None if e0 is None else e0.detach().requires_grad_(want_ge)
-                rel, scal = edge_scalars(layer, c, e, i64)                        # (only the scalars' graph is used below)
+                rel, scal = edge_scalars(layer, c, e, i64, by_k)                  # (only the scalars' graph is used below)
             with torch.no_grad():
                 u4 = u_all[lo:hi_, :, :, :m]
                 m_i, pm, cnt = _pooled_messages(layer, u4, m0, i64, r0, ctx.valid_radius)
@@ -1127,7 +1216,7 @@ def _backward_native(ctx, g_node, g_coors):
                 c = c0.detach().requires_grad_(True)
                 e = None if e0 is None else e0.detach().requires_grad_(want_ge)
                 u = u_all[lo:hi_, :, :, :m].detach().requires_grad_(True)
-                rel, scal = edge_scalars(layer, c, e, i64)
+                rel, scal = edge_scalars(layer, c, e, i64, by_k)
                 out_n, out_c = layer_tail(layer, f, c, u, rel, m0, i64, r0, ctx.valid_radius)
                 outs, gouts = [], []
                 for o, g in ((out_n, g_node[lo:hi_]), (out_c, g_coors[lo:hi_])):
@@ -1214,6 +1303,8 @@ def _backward_native(ctx, g_node, g_coors):
             grads_by_id[id(lin3.weight)] += g_w2[:m, :h]
             grads_by_id[id(lin3.bias)] += bias2 if bias2 is not None else gu16[:, :m].sum(dim=0)
             del gz_i, gz_j
+            if lk is not None:                                      # the edge columns of d/d scalars -> the tables
+                lk.add(lo, hi_, i32, n, k, g_scal.view(ec, s_in)[:, s_in - layer.edge_dim:])
         # d loss / d scalars -> coordinates (through d = |x_i - x_j|^2 and the fourier terms) and edge features
         if closed_dist:
             with torch.no_grad():                                   # d = |rel|^2:  d loss / d rel += 2 g_d rel
@@ -1240,7 +1331,7 @@ def _backward_native(ctx, g_node, g_coors):
     out_params = [grads_by_id[id(p)].to(op.dtype) if (need[7 + i] and id(p) not in unused) else None
                   for i, (p, op) in enumerate(zip(params, orig_params))]
     return (None, None, None, None, g_feats.to(in_dtypes[0]) if need[4] else None, g_coors_in.to(in_dtypes[1]) if need[5] else None,
-            g_edges.to(in_dtypes[2]) if want_ge else None, *out_params)
+            lk.outputs() if lk is not None else (g_edges.to(in_dtypes[2]) if want_ge else None), *out_params)
 
 
 def _backward_recompute(ctx, g_node, g_coors):
@@ -1263,10 +1354,13 @@ def _backward_recompute(ctx, g_node, g_coors):
     b, n, _ = feats.shape
     k = idx.shape[-1] if idx is not None else n
     step = _chunk_graphs(layer, n, k, b)
-    need = ctx.needs_input_grad                      # (layer, order_hint, mask, adj, feats, coors, edges, *params)
+    need = _need(ctx)                                # (layer, order_hint, mask, adj, feats, coors, edges, *params)
     g_feats = torch.zeros_like(feats) if need[4] else None
     g_coors_in = torch.zeros_like(coors) if need[5] else None
-    g_edges = torch.zeros_like(edges) if (edges is not None and need[6]) else None
+    by_k = getattr(ctx, "edges_by_k", False)
+    lk = _LookupGrads(ctx, b, n, feats.device) if by_k else None        # (edge look-up tables: d/d the gathered features -> the tables)
+    want_e = edges is not None and (lk.active if by_k else bool(need[6]))
+    g_edges = torch.zeros_like(edges) if (want_e and not by_k) else None
     g_params = [torch.zeros_like(p) if need[7 + i] else None for i, p in enumerate(params)]
     if g_node is None:
         g_node = torch.zeros_like(feats)
@@ -1277,10 +1371,10 @@ def _backward_recompute(ctx, g_node, g_coors):
         with torch.enable_grad():
             f = feats[lo:hi].detach().requires_grad_(need[4])
             c = coors[lo:hi].detach().requires_grad_(need[5])
-            e = None if edges is None else edges[lo:hi].detach().requires_grad_(bool(need[6]))
+            e = None if edges is None else edges[lo:hi].detach().requires_grad_(want_e)
             out_n, out_c = layer_given_neighbors(layer, f, c, e, None if mask is None else mask[lo:hi],
                                                  None if idx is None else idx[lo:hi], None if rank is None else rank[lo:hi],
-                                                 ctx.valid_radius, drop=getattr(ctx, "drop", None), graph_offset=lo)
+                                                 ctx.valid_radius, drop=getattr(ctx, "drop", None), graph_offset=lo, edges_by_k=by_k)
             wrt = [t for t in (f, c, e) if t is not None and t.requires_grad] + [p for p, g in zip(params, g_params) if g is not None]
             outs, gouts = [], []
             for o, g in ((out_n, g_node[lo:hi]), (out_c, g_coors[lo:hi])):
@@ -1299,7 +1393,9 @@ def _backward_recompute(ctx, g_node, g_coors):
                 g_coors_in[lo:hi] = g
         if e is not None and e.requires_grad:
             g = next(it)
-            if g is not None:
+            if g is not None and by_k:
+                lk.add(lo, hi, None if idx is None else idx[lo:hi].int().contiguous(), n, k, g.float().reshape(-1, g.shape[-1]))
+            elif g is not None:
                 g_edges[lo:hi] = g
         for i, gp in enumerate(g_params):
             if gp is not None:
@@ -1309,7 +1405,8 @@ def _backward_recompute(ctx, g_node, g_coors):
     cast = lambda g, dt: None if g is None else g.to(dt)                                        # noqa: E731
     unused = _unused_params(layer, ctx)
     g_params = [None if id(p) in unused else g for p, g in zip(params, g_params)]
-    return (None, None, None, None, cast(g_feats, in_dtypes[0]), cast(g_coors_in, in_dtypes[1]), cast(g_edges, in_dtypes[2]), *g_params)
+    return (None, None, None, None, cast(g_feats, in_dtypes[0]), cast(g_coors_in, in_dtypes[1]),
+            lk.outputs() if lk is not None else cast(g_edges, in_dtypes[2]), *g_params)
 
 
 def wants_grad(layer, *tensors):

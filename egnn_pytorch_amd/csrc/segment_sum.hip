@@ -99,3 +99,197 @@ extern "C" int egnn_edge_features_gather_f32(const float* edges, const int64_t* 
                        edge_tok, edge_tok_emb, d1, adj_deg, adj_deg_emb, d2, idx, N, K, total, out);
     return egnn_launch_status();
 }
+
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Its transpose, the backward of EGNN_Network's per-pair edge features under autograd -- see
+// include/egnn_hip.h::egnn_edge_features_grad_f32.  The gradient of an embedding table is a sum over the edges that carry each
+// label; like every sum over edges here it has a fixed order and no float atomics:
+//   launch 1: G workgroups (G a function of E and the table sizes only), each reduces a contiguous range of edges into a (V, D)
+//             partial.  Its four waves take consecutive quarters of the range; a wave splits into P = 64 / D lane groups (one lane
+//             per column), group p walks edges p, p + P, ... of the quarter in order into an LDS table of its own; the 4 P tables
+//             are then summed in (wave, group) order.  Vocabularies whose tables do not fit LDS_WAVE_FLOATS per wave run in label
+//             blocks, one blockIdx.y per block: every label's sum still visits the same edges in the same order, so the bits do not
+//             depend on the block size.
+//   launch 2: one thread per output element sums the G partials in index order.
+// Dense float edges (no token table) have no reduction: the pairs of one row are distinct, so their gradient rows are stored.
+namespace {
+
+constexpr int FGRAD_LDS_WAVE_FLOATS = 2048;                    // 8 KB per wave, 32 KB per workgroup
+constexpr int FGRAD_EDGES_PER_GROUP = 2048;                    // edges per workgroup of launch 1 at most, before the G cap
+
+struct FeatGradTable {
+    int V, D, Vb, nb, col0;                                    // vocabulary, width, labels per block, blocks, first column in g
+    int64_t off;                                               // offset of this table in a partial
+};
+
+__device__ __forceinline__ int fgrad_groups(int D) { return D <= 64 ? 64 / D : 1; }
+
+__global__ __launch_bounds__(256) void edge_features_grad_part_kernel(const float* __restrict__ g, int64_t ld,
+                                                                      const int64_t* __restrict__ tok, const uint8_t* __restrict__ deg,
+                                                                      const int32_t* __restrict__ idx, int N, int K, int64_t E,
+                                                                      int64_t per, FeatGradTable t1, FeatGradTable t2,
+                                                                      float* __restrict__ part, int64_t stride)
+{
+    __shared__ float tab[4 * FGRAD_LDS_WAVE_FLOATS];
+    const bool second = (int)blockIdx.y >= t1.nb;
+    const FeatGradTable t = second ? t2 : t1;
+    const int blk = second ? (int)blockIdx.y - t1.nb : (int)blockIdx.y;
+    const int D = t.D, P = fgrad_groups(D), Vb = t.Vb;
+    const int vb0 = blk * Vb;
+    const int vn = min(Vb, t.V - vb0);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int o = threadIdx.x; o < 4 * FGRAD_LDS_WAVE_FLOATS; o += 256) tab[o] = 0.f;
+    __syncthreads();
+
+    const int64_t e0 = (int64_t)blockIdx.x * per;
+    const int64_t e1 = min(E, e0 + per);
+    const int64_t q = e1 > e0 ? (e1 - e0 + 3) / 4 : 0;
+    const int64_t ws = e0 + wave * q;
+    const int64_t we = min(e1, ws + q);
+    const int p = D <= 64 ? lane / D : 0;
+    const int c0 = D <= 64 ? lane - p * D : lane;
+    float* mine = tab + wave * FGRAD_LDS_WAVE_FLOATS + p * Vb * D;
+    const float* gcol = g + t.col0;
+    auto label = [&](int64_t e) -> int {                       // this block's row of edge e's label, or -1
+        const int64_t node = e / K;                            // b * N + i
+        const int k = (int)(e - node * K);
+        const int j = idx ? idx[e] : k;
+        if ((unsigned)j >= (unsigned)N) return -1;
+        const int64_t pair = node * N + j;
+        const int64_t v = (second ? (int64_t)deg[pair] : tok[pair]) - vb0;
+        return (v >= 0 && v < vn) ? (int)v : -1;
+    };
+    if (p < P) {
+        int64_t e = ws + p;
+        for (; e + 3 * (int64_t)P < we; e += 4 * (int64_t)P) { // four edges in flight, added in order
+            int r[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) r[u] = label(e + u * (int64_t)P);
+            for (int c = c0; c < D; c += 64) {
+                float x[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) x[u] = gcol[(e + u * (int64_t)P) * ld + c];
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+                    if (r[u] >= 0) mine[r[u] * D + c] += x[u];
+            }
+        }
+        for (; e < we; e += P) {
+            const int r = label(e);
+            if (r < 0) continue;
+            for (int c = c0; c < D; c += 64) mine[r * D + c] += gcol[e * ld + c];
+        }
+    }
+    __syncthreads();
+    const int tables = 4 * P;
+    float* out = part + (int64_t)blockIdx.x * stride + t.off + (int64_t)vb0 * D;
+    for (int o = threadIdx.x; o < vn * D; o += 256) {
+        float s = 0.f;
+        for (int w = 0; w < tables; ++w) s += tab[(w / P) * FGRAD_LDS_WAVE_FLOATS + (w % P) * Vb * D + o];
+        out[o] = s;
+    }
+}
+
+__global__ __launch_bounds__(256) void edge_features_grad_sum_kernel(const float* __restrict__ part, int64_t stride, int G,
+                                                                     int64_t n1, float* __restrict__ out1, float* __restrict__ out2)
+{
+    const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (o >= stride) return;
+    float s = 0.f;
+    int gi = 0;
+    for (; gi + 4 <= G; gi += 4) {                             // four loads in flight, added in index order
+        const float a = part[(int64_t)gi * stride + o], b = part[(int64_t)(gi + 1) * stride + o];
+        const float c = part[(int64_t)(gi + 2) * stride + o], d = part[(int64_t)(gi + 3) * stride + o];
+        s += a;
+        s += b;
+        s += c;
+        s += d;
+    }
+    for (; gi < G; ++gi) s += part[(int64_t)gi * stride + o];
+    if (o < n1) out1[o] = s;
+    else out2[o - n1] = s;
+}
+
+__global__ __launch_bounds__(256) void edge_features_grad_dense_kernel(const float* __restrict__ g, int64_t ld,
+                                                                       const int32_t* __restrict__ idx, int N, int K, int d1,
+                                                                       int64_t total, float* __restrict__ g_edges)
+{
+    for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (int64_t)gridDim.x * 256) {
+        const int64_t e = o / d1;
+        const int c = (int)(o - e * d1);
+        const int64_t node = e / K;
+        const int k = (int)(e - node * K);
+        const int j = idx ? idx[e] : k;
+        if ((unsigned)j >= (unsigned)N) continue;
+        g_edges[(node * N + j) * d1 + c] = g[e * ld + c];
+    }
+}
+
+FeatGradTable fgrad_table(bool on, int V, int D, int col0, int64_t off)
+{
+    FeatGradTable t{};
+    if (!on) return t;
+    const int P = D <= 64 ? 64 / D : 1;
+    t.V = V;
+    t.D = D;
+    t.Vb = FGRAD_LDS_WAVE_FLOATS / (P * D) > 1 ? FGRAD_LDS_WAVE_FLOATS / (P * D) : 1;
+    t.nb = (V + t.Vb - 1) / t.Vb;
+    t.col0 = col0;
+    t.off = off;
+    return t;
+}
+
+}  // namespace
+
+extern "C" int egnn_edge_features_grad_f32(const float* g, int64_t ld, const int64_t* edge_tok, int V1, int d1,
+                                           const uint8_t* adj_deg, int V2, int d2, const int32_t* idx, int B, int N, int K,
+                                           float* g_tok_emb, float* g_deg_emb, float* g_edges, float* work, int64_t* work_floats,
+                                           void* stream)
+{
+    if (!work_floats) return EGNN_E_NULLPTR;
+    if (B <= 0 || N <= 0 || K <= 0 || d1 < 0 || d2 < 0 || d1 + d2 <= 0 || ld < d1 + d2) return EGNN_E_SHAPE;
+    if (!idx && K != N) return EGNN_E_SHAPE;
+    const bool on1 = g_tok_emb != nullptr, on2 = g_deg_emb != nullptr;
+    if ((on1 && (!edge_tok || V1 <= 0 || d1 <= 0)) || (on2 && (!adj_deg || V2 <= 0 || d2 <= 0))) return EGNN_E_SHAPE;
+    if (g_edges && (edge_tok || d1 <= 0)) return EGNN_E_SHAPE;
+    if ((on1 && d1 > FGRAD_LDS_WAVE_FLOATS) || (on2 && d2 > FGRAD_LDS_WAVE_FLOATS)) return EGNN_E_UNSUPPORTED;
+    const FeatGradTable t1 = fgrad_table(on1, V1, d1, 0, 0), t2 = fgrad_table(on2, V2, d2, d1, on1 ? (int64_t)V1 * d1 : 0);
+    if ((int64_t)t1.nb + t2.nb > 65535) return EGNN_E_UNSUPPORTED;
+    const int64_t E = (int64_t)B * N * K;
+    const int64_t n1 = on1 ? (int64_t)V1 * d1 : 0, n2 = on2 ? (int64_t)V2 * d2 : 0;
+    const int64_t stride = n1 + n2;
+    int64_t G = 0;
+    if (stride > 0) {
+        // a function of E and the table sizes only: the partition, and with it every bit of the result, is the same on any device
+        int64_t cap = (int64_t(1) << 24) / stride;
+        cap = cap < 1 ? 1 : (cap > 1024 ? 1024 : cap);
+        G = (E + FGRAD_EDGES_PER_GROUP - 1) / FGRAD_EDGES_PER_GROUP;
+        G = G < cap ? G : cap;
+    }
+    if (!work) {                                                 // size query: nothing is launched
+        *work_floats = G * stride;
+        return EGNN_OK;
+    }
+    if (*work_floats < G * stride) return EGNN_E_SHAPE;
+    if (!g) return EGNN_E_NULLPTR;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (g_edges) {
+        const int64_t total = E * d1;
+        int64_t blocks = (total + 255) / 256;
+        if (blocks > 65536) blocks = 65536;
+        hipLaunchKernelGGL(edge_features_grad_dense_kernel, dim3((unsigned)blocks), dim3(256), 0, st, g, ld, idx, N, K, d1, total,
+                           g_edges);
+        const int rc = egnn_launch_status();
+        if (rc) return rc;
+    }
+    if (stride == 0) return EGNN_OK;
+    const int64_t per = (E + G - 1) / G;
+    hipLaunchKernelGGL(edge_features_grad_part_kernel, dim3((unsigned)G, (unsigned)(t1.nb + t2.nb)), dim3(256), 0, st, g, ld,
+                       edge_tok, adj_deg, idx, N, K, E, per, t1, t2, work, stride);
+    int rc = egnn_launch_status();
+    if (rc) return rc;
+    hipLaunchKernelGGL(edge_features_grad_sum_kernel, dim3((unsigned)((stride + 255) / 256)), dim3(256), 0, st, work, stride, (int)G,
+                       n1, g_tok_emb, g_deg_emb);
+    return egnn_launch_status();
+}

@@ -14,6 +14,7 @@ kernels (the E x H work of every shape the fused forward covers) or recomputes t
 from __future__ import annotations
 
 import contextlib
+import copy
 import contextvars
 import os
 import warnings
@@ -90,11 +91,14 @@ _FLOAT_DTYPES = (torch.float32, torch.float64, torch.float16, torch.bfloat16)
 class EdgeLookup:
     """Per-pair edge features given as look-up tables instead of a materialised (B,N,N,edge_dim) tensor: what EGNN_Network's
     front-end produces (egnn_pytorch.py:410-432) -- [edge_emb(edge tokens) or float edges | adj_emb(adjacency-degree labels)].
-    The edge kernel reads the tables for the K selected pairs of each node (include/egnn_hip.h: egnn_edge_args.edge_tok ...);
-    inference only (under autograd the network materialises the tensor so that the embeddings receive gradients)."""
+    The edge kernel reads the tables for the K selected pairs of each node (egnn_edge_features_gather_f32).  `edges`, `tok_emb` and
+    `deg_emb` (`live`) are the caller's tensors -- the dense float edges and the embedding weights -- and the kernels read detached fp32
+    copies of them.  Under autograd the layer hands the live ones to autograd.EGNNFunction as differentiable inputs: their gradients
+    come from egnn_edge_features_grad_f32, a reduction over the selected pairs only."""
 
     def __init__(self, edges=None, tok=None, tok_emb=None, deg=None, deg_emb=None):
-        self.edges = None if edges is None else edges.contiguous().float()
+        self.live = (edges, tok_emb if tok is not None else None, deg_emb if deg is not None else None)
+        self.edges = None if edges is None else edges.detach().contiguous().float()
         self.tok = None if tok is None else tok.contiguous().long()
         self.tok_emb = None if tok_emb is None else tok_emb.detach().contiguous().float()
         self.deg = None if deg is None else deg.contiguous()
@@ -105,6 +109,14 @@ class EdgeLookup:
     @property
     def width(self):
         return self.d1 + self.d2
+
+    def graphs(self, lo, hi):
+        """The same tables for graphs [lo, hi) of the batch (the labels and dense edges sliced, the embedding tables shared)."""
+        out = copy.copy(self)
+        out.edges = None if self.edges is None else self.edges[lo:hi]
+        out.tok = None if self.tok is None else self.tok[lo:hi]
+        out.deg = None if self.deg is None else self.deg[lo:hi]
+        return out
 
 
 def _mlp(d_in, d_hidden, d_out, dropout, final_act):
@@ -235,8 +247,11 @@ class EGNN(nn.Module):
         autograd.EGNNFunction (HIP forward, recompute-in-backward)."""
         if _ops.RANGE_CHECK == "deferred" and feats.is_cuda:
             _ops.check_range(feats.device, wait=False)              # an earlier call's status, if it has arrived
-        if _autograd.wants_grad(self, feats, coors, edges):
-            node_out, coors_out = _autograd.EGNNFunction.apply(self, order_hint, mask, adj_mat, feats, coors, edges,
+        lookup = edges if isinstance(edges, EdgeLookup) else None
+        # (edge look-up tables: the dense float edges and the two embedding weights they were built from are differentiable inputs)
+        dense, tok_w, deg_w = lookup.live if lookup is not None else (edges, None, None)
+        if _autograd.wants_grad(self, feats, coors, dense, tok_w, deg_w):
+            node_out, coors_out = _autograd.EGNNFunction.apply(self, order_hint, mask, adj_mat, feats, coors, dense, lookup, tok_w, deg_w,
                                                                *self.parameters())
             order = None                                            # (scheduling hint only; recomputed by the next layer)
         else:
@@ -787,10 +802,11 @@ class EGNN_Network(nn.Module):
             assert n <= self.num_positions, \
                 f"given sequence length {n} must be less than the number of positions {self.num_positions} set at init"
             feats = feats + self.pos_emb(torch.arange(n, device=feats.device))[None]
-        # Edge features for the layers.  Inference: look-up tables (EdgeLookup) -- the (B,N,N,edge_dim+adj_dim) tensor of :410-432
-        # is never materialised, the edge kernel reads the embedding rows of the K selected pairs of each node.  Under autograd:
-        # the tensor, so that the embeddings receive gradients.
-        lazy = not torch.is_grad_enabled() and not any(l.float64_kernels() for _, l in self.layers)       # (depth = 0: an empty loop, as upstream)
+        # Edge features for the layers: look-up tables (EdgeLookup) -- the (B,N,N,edge_dim+adj_dim) tensor of :410-432 is never
+        # materialised, the edge kernel reads the embedding rows of the K selected pairs of each node.  Under autograd the embedding
+        # weights (and dense float edges) are inputs of each layer's autograd.EGNNFunction, whose backward reduces their gradients over
+        # the same pairs (egnn_edge_features_grad_f32).  Float64 modules take the materialised tensor, in inference and training.
+        lazy = not any(l.float64_kernels() for _, l in self.layers)       # (depth = 0: an empty loop, as upstream)
         tok = tok_emb = None
         if edges is not None and self.edge_emb is not None:
             if lazy:

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define EGNN_ABI_VERSION 39
+#define EGNN_ABI_VERSION 40
 
 enum {
     EGNN_OK = 0,
@@ -390,6 +390,23 @@ int egnn_edge_fused_f32(const egnn_edge_args* args, void* stream);
 int egnn_edge_features_gather_f32(const float* edges, const int64_t* edge_tok, const float* edge_tok_emb, int d1,
                                   const uint8_t* adj_deg, const float* adj_deg_emb, int d2, const int32_t* idx,
                                   int B, int N, int K, float* out, void* stream);
+
+/* Its transpose: the gradients of the look-up tables under autograd, from the per-edge gradient rows g (E x ld fp32, E = B*N*K;
+ * columns [0, d1) belong to the first table, [d1, d1+d2) to adj_deg_emb -- the edge columns of d loss / d per-edge scalars):
+ *   g_tok_emb[v, :] = sum of g[e, :d1]    over the edges e = (b,i,k) with edge_tok[b,i,j] == v,  j = idx[b,i,k]   (V1 x d1)
+ *   g_deg_emb[v, :] = sum of g[e, d1:]    over the edges with adj_deg[b,i,j] == v                                  (V2 x d2)
+ *   g_edges[b,i,j, :] = g[e, :d1]         dense float edges (edge_tok NULL): a plain store, the K pairs of a row are distinct;
+ *                                         the caller zeroes g_edges (B,N,N,d1) -- pairs no edge selected keep their 0
+ * (idx NULL: dense, j = k, K = N).  Each output is optional (NULL: skipped); labels outside [0, V) are ignored.  The sums have a
+ * fixed order -- G workgroups (G a function of E, V1 d1 and V2 d2 only) reduce contiguous edge ranges into partials in LDS, a
+ * second launch adds the G partials in index order -- so results are bit-identical from run to run and on any device, and for
+ * any vocabulary size (tables larger than the LDS budget run in label blocks that visit the edges in the same order).
+ * work: G * (V1 d1 + V2 d2) floats; work NULL = size query: *work_floats receives the size, nothing is launched.  Otherwise
+ * *work_floats is the size of `work`.  d1, d2 <= 2048. */
+int egnn_edge_features_grad_f32(const float* g, int64_t ld, const int64_t* edge_tok, int V1, int d1,
+                                const uint8_t* adj_deg, int V2, int d2, const int32_t* idx, int B, int N, int K,
+                                float* g_tok_emb, float* g_deg_emb, float* g_edges, float* work, int64_t* work_floats,
+                                void* stream);
 
 /* Backward of the edge pass without anything of size E x H in memory (autograd of egnn_pytorch.py:279-287;
  * csrc/edge_bwd.hip).  One call = one pass over a list of L entries (edges) grouped by a key node: by the source node i

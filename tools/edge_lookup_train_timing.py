@@ -1,0 +1,75 @@
+"""One EGNN_Network training step (forward + backward) on edge look-up tables against the materialised recipe (MI355X; run from the
+repository root): B = 1, a chain adjacency with 3 degrees, 6 edge tokens, edge_dim = adj_dim = 8, depth 2, K = 16, dim 16, at
+N = 4 096, 8 192 and 16 384.  "lookup" is the network itself (the layers read the K selected pairs' embedding rows; the embedding
+gradients come from egnn_edge_features_grad_f32); "materialised" builds cat(edge_emb(tokens), adj_emb(labels)) as a dense
+(1,N,N,16) tensor in torch (`_embed_pairs`: torch's embedding in chunks above 2^24 indices) and calls each EGNN layer with it.
+Device events, 2 warm-up + median of 5 steps, and the peak device memory of one step above its inputs; one JSON line
+(DESIGN.md §4.7).  `quick` runs toy sizes."""
+import json
+import sys
+
+import torch
+
+sys.path.insert(0, ".")
+from egnn_pytorch_amd import EGNN_Network, _ops  # noqa: E402
+from egnn_pytorch_amd.layer import _embed_pairs  # noqa: E402
+
+QUICK = "quick" in sys.argv[1:]
+SIZES = (512, 1024) if QUICK else (4096, 8192, 16384)
+
+
+def materialised(net, tokens, coors, adj, edge_tok):
+    feats = net.token_emb(tokens)
+    adj_mat, deg = _ops.adj_expand(adj, 1, net.num_adj_degrees)
+    edges = torch.cat((_embed_pairs(net.edge_emb, edge_tok), _embed_pairs(net.adj_emb, deg.long())), dim=-1)
+    for _, egnn in net.layers:
+        feats, coors = egnn(feats, coors, edges=edges, adj_mat=adj_mat)
+    return feats, coors
+
+
+def step(fn, coors):
+    x = coors.clone().requires_grad_(True)
+    h, co = fn(x)
+    (h.sum() + co.sum()).backward()
+
+
+def timed(fn, coors):
+    for _ in range(2):
+        step(fn, coors)
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(5):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        step(fn, coors)
+        b.record()
+        torch.cuda.synchronize()
+        ts.append(a.elapsed_time(b))
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    step(fn, coors)
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated() - base
+    return round(sorted(ts)[2], 3), round(peak / 2**30, 3)
+
+
+torch.manual_seed(0)
+net = EGNN_Network(num_tokens=20, num_edge_tokens=6, edge_dim=8, dim=16, depth=2, num_nearest_neighbors=16, num_adj_degrees=3,
+                   adj_dim=8).cuda()
+res = {}
+for n in SIZES:
+    i = torch.arange(n, device="cuda")
+    adj = (i[:, None] - i[None, :]).abs() <= 1
+    tokens = torch.randint(0, 20, (1, n), device="cuda")
+    coors = torch.randn(1, n, 3, device="cuda") * 4
+    edge_tok = torch.randint(0, 6, (1, n, n), device="cuda")
+    for name, fn in (("lookup", lambda x: net(tokens, x, adj_mat=adj, edges=edge_tok)),
+                     ("materialised", lambda x: materialised(net, tokens, x, adj, edge_tok))):
+        ms, gib = timed(fn, coors)
+        res[f"{n}_{name}_ms"] = ms
+        res[f"{n}_{name}_peak_gib"] = gib
+        net.zero_grad(set_to_none=True)
+    del adj, edge_tok
+    torch.cuda.empty_cache()
+print(json.dumps(res))
