@@ -3,6 +3,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1 without a launcher: spawns the N ranks itself)
     python bench.py ... --dump-outputs DIR                        (also writes the last timed step's outputs, rank 0's, to DIR/*.npy)
+    python bench.py ... --full                                    (also every secondary figure of the line, see below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,13 +13,20 @@ EGNN(dim=512, num_nearest_neighbors=32), B=64 graphs x N=1024 nodes per GPU, fp3
 sharded over ranks (weak scaling: 64 graphs per GPU), no collective in the data path; the timed
 region is bracketed by barrier + synchronize and the max over ranks is taken.
 
-Rank 0 prints ONE JSON line: the driver contract plus
+Rank 0 prints ONE JSON line.  A plain run sets up, primes, warms up, times the K steps, writes
+--dump-outputs and prints the driver contract (value, ms_per_step, ...) with the run's configuration;
+nothing else.  With --full the line also carries the figures that take work or runs of their own:
+  "value_range_check_*" -- the same K steps again in the other mode of the range check;
   "roofline"     -- the dominant kernel against its roofline, duration measured live with events on
-                    the launch stream (the kernels are launched on torch's current stream);
+                    the launch stream (the kernels are launched on torch's current stream), its HBM
+                    traffic and clocks from child runs under rocprofv3 --pmc;
   "kernels"      -- the same for every kernel of the step;
+  "value_unprimed", "value_ragged_masks" -- `value` of child runs without priming / with ragged masks;
   "cpu_baseline" -- the reference module itself (oracle/_ref, torch CPU, all host cores) on a bounded
                     sample of the same workload on this box's host cores; the numpy port if the
-                    artefact is absent (`kind` says which).
+                    artefact is absent (`kind` says which);
+  "train_step"   -- forward + backward of the north-star workload after the timed region.
+--train-step, --reference-eager and --hipgraph add their figures in either mode.
 """
 import argparse
 import json
@@ -168,9 +176,10 @@ def _pmc_child(workload, counter, timeout_s):
     env.update(TMPDIR="/tmp", EGNN_BENCH_TRAFFIC_CHILD="1")
     rows = []
     with tempfile.TemporaryDirectory(dir="/tmp") as tmp:
+        # (--full without its child runs: the counter pass sees the per-kernel probe's launches too)
         cmd = [rp, "--kernel-trace", "--pmc", counter, "-d", tmp, "-o", "pmc", "--output-format", "csv", "--", sys.executable,
-               os.path.abspath(__file__), "--workload", workload, "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-train-step",
-               "--no-live-traffic"]
+               os.path.abspath(__file__), "--workload", workload, "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
+               "--no-train-step", "--no-live-traffic"]
         try:
             subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=timeout_s, check=True)
         except Exception as ex:                      # (never fatal: the line falls back to the committed profile)
@@ -226,15 +235,15 @@ def live_clocks(workload, timeout_s=150):
 
 
 def child_value(args, extra_flags, env_extra=None, timeout_s=120):
-    """`value` of a child run of this command (same workload / steps / warm-up, no CPU baseline, training step or PMC passes) with
-    `extra_flags`: (graphs/s, None) or (None, why not).  For secondary figures of the line; never fatal."""
+    """`value` of a plain child run of this command (same workload / steps / warm-up, none of --full's figures) with `extra_flags`:
+    (graphs/s, None) or (None, why not).  For secondary figures of the line; never fatal."""
     import subprocess
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "GROUP_RANK", "ROLE_RANK", "MASTER_ADDR", "MASTER_PORT")
            and not k.startswith("TORCHELASTIC")}
     env.update(EGNN_BENCH_TRAFFIC_CHILD="1", **(env_extra or {}))
-    cmd = [sys.executable, os.path.abspath(__file__), "--workload", args.workload, "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--no-cpu-baseline", "--no-train-step", "--no-live-traffic"] + list(extra_flags)
+    cmd = [sys.executable, os.path.abspath(__file__), "--workload", args.workload, "--steps", str(args.steps), "--warmup", str(args.warmup)] \
+        + list(extra_flags)
     try:
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout_s, check=True)
         return float(json.loads(r.stdout.strip().splitlines()[-1])["value"]), None
@@ -244,15 +253,15 @@ def child_value(args, extra_flags, env_extra=None, timeout_s=120):
 
 def unprimed_value(args, timeout_s=120):
     """`value` of a FRESH process that skips the priming steps (EGNN_BENCH_PRIME=0: only the contract's W warm-up steps in front of the
-    timed region), as BENCH_r01 ... r04 were taken: a child run of this command without the CPU baseline, the training step and the PMC
-    passes.  Returns (graphs/s, None) or (None, why not).  Secondary figure: what the priming changes is visible in the line."""
+    timed region), as BENCH_r01 ... r04 were taken: a plain child run of this command (none of --full's figures).  Returns (graphs/s,
+    None) or (None, why not).  Secondary figure: what the priming changes is visible in the line."""
     import subprocess
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "GROUP_RANK", "ROLE_RANK", "MASTER_ADDR", "MASTER_PORT")
            and not k.startswith("TORCHELASTIC")}
     env.update(EGNN_BENCH_PRIME="0", EGNN_BENCH_TRAFFIC_CHILD="1")
-    cmd = [sys.executable, os.path.abspath(__file__), "--workload", args.workload, "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--no-cpu-baseline", "--no-train-step", "--no-live-traffic"] + (["--ragged-mask"] if args.ragged_mask else [])
+    cmd = [sys.executable, os.path.abspath(__file__), "--workload", args.workload, "--steps", str(args.steps), "--warmup", str(args.warmup)] \
+        + (["--ragged-mask"] if args.ragged_mask else [])
     try:
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout_s, check=True)
         return float(json.loads(r.stdout.strip().splitlines()[-1])["value"]), None
@@ -477,6 +486,10 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="north_star", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure every secondary figure of the line (the other range-check mode, per-kernel rooflines with live "
+                         "HBM traffic and clocks, unprimed and ragged-mask child runs, the CPU baseline, the north-star training step); "
+                         "the --no-* options below take single ones out again")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--standin-backend", default=None, choices=["gloo"],
                     help="TEST AID (tests/test_sharding_gloo.py): run the rank logic -- env parsing, process group, broadcast-free "
@@ -484,7 +497,7 @@ def main():
                          "no numbers of any meaning")
     ap.add_argument("--ragged-mask", action="store_true", help="ragged masks (len ~ U{N/2..N}) instead of all-True")
     ap.add_argument("--train-step", action="store_true", help="also time forward + backward of the same workload (not part of `value`); "
-                                                               "on by default for the single-layer workloads at N = 1")
+                                                               "on by default with --full for the north-star workload at N = 1")
     ap.add_argument("--no-train-step", action="store_true", help="skip the forward + backward timing")
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="do not run the two rocprofv3 --pmc passes that measure the dominant kernel's HBM traffic (roofline.traffic then "
@@ -655,9 +668,9 @@ def main():
     if args.dump_outputs and rank == 0:                  # the last timed step's outputs, before any later run can touch them
         dumped = dump_outputs(dict(zip(("feats", "coors"), last_out[0])), args.dump_outputs)
 
-    # the same K steps in the other mode of the range check, so that the line shows what the per-forward synchronisation costs
+    # --full: the same K steps in the other mode of the range check, so that the line shows what the per-forward synchronisation costs
     value_other, other_mode = None, ("deferred" if _ops.RANGE_CHECK == "sync" else "sync")
-    if world == 1 and _ops.RANGE_CHECK in ("sync", "deferred"):
+    if args.full and world == 1 and _ops.RANGE_CHECK in ("sync", "deferred"):
         mode = _ops.RANGE_CHECK
         _ops.RANGE_CHECK = other_mode
         try:
@@ -667,60 +680,19 @@ def main():
         finally:
             _ops.RANGE_CHECK = mode
 
-    # ---- per-kernel durations (events on the launch stream), outside the timed region
-    PROBE_STEPS = 5
-    with phase_timer() as pt:
-        for _ in range(PROBE_STEPS):
-            step()
-    summary = pt.summary()
-    per_kernel = {k: sum(v) / len(v) for k, v in summary.items()}              # average duration of one launch
-    launches = {k: len(v) / PROBE_STEPS for k, v in summary.items()}           # launches per step (network: one per layer)
+    # ---- --full: per-kernel durations (events on the launch stream), outside the timed region
+    if args.full:
+        PROBE_STEPS = 5
+        with phase_timer() as pt:
+            for _ in range(PROBE_STEPS):
+                step()
+        summary = pt.summary()
+        per_kernel = {k: sum(v) / len(v) for k, v in summary.items()}              # average duration of one launch
+        launches = {k: len(v) / PROBE_STEPS for k, v in summary.items()}           # launches per step (network: one per layer)
 
     if rank == 0:
         counts, shp = model_counts(kwargs, b, n)
         depth = kwargs.get("depth", 1)
-        # kernels ordered by their share of the step; the roofline object is the dominant one
-        order = sorted(per_kernel.items(), key=lambda kv: -kv[1] * launches[kv[0]])
-        kernels = [roofline_entry(k, counts, ms, launches[k]) for k, ms in order if k in counts]
-        other = {k: round(ms * launches[k], 4) for k, ms in order if k not in counts}
-        dominant = dict(next(kr for kr in kernels if kr["bound"] in ("hbm", "mfma")))
-        traffic = thead = None
-        tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(tpath):
-            try:
-                tj = json.load(open(tpath))
-                per_wl = tj.get(args.workload, tj if args.workload == "north_star" and "north_star" not in tj else {})
-                traffic = per_wl.get(dominant["kernel"])
-                thead = per_wl.get("_head", tj.get("_head"))
-            except Exception:
-                traffic = None
-        dominant["traffic_profile"] = traffic                # (the committed profile's figure, with the commit it was taken at)
-        dominant["traffic_head"] = thead
-        src = "profiles/pmc_traffic.json: (2 FETCH_SIZE + WRITE_SIZE) * 1024 per launch, separate rocprofv3 --pmc passes " \
-              "of this command (tools/profile.sh)" if traffic is not None else None
-        under_profiler = "rocprofiler" in os.environ.get("LD_PRELOAD", "") or any(k.startswith("ROCPROF") for k in os.environ)
-        if world == 1 and not args.no_live_traffic and os.environ.get("EGNN_BENCH_TRAFFIC_CHILD") != "1" and not under_profiler:
-            live, note = live_traffic(args.workload, dominant["kernel"])
-            if live is not None:
-                traffic, src = live, note
-                dominant["traffic_head"] = git_head()
-            else:
-                src = (src or "none") + f" [live measurement unavailable: {note}]"
-        dominant["traffic"] = traffic
-        dominant["traffic_source"] = src
-        # the clock each kernel actually ran at (the chip clocks to its power budget: the MFMA peak of 2.5 PFLOP/s assumes 2.4 GHz)
-        if world == 1 and not args.no_live_traffic and os.environ.get("EGNN_BENCH_TRAFFIC_CHILD") != "1" and not under_profiler:
-            clocks, cnote = live_clocks(args.workload)
-            if clocks:
-                for kr in kernels + [dominant]:
-                    ghz = clocks.get(kr["kernel"])
-                    if ghz:
-                        kr["effective_clock_ghz"] = ghz
-                        if kr["bound"] == "mfma":
-                            kr["frac_at_clock"] = round(kr["frac"] * 2.4 / ghz, 4)
-                dominant["clock_source"] = cnote
-            else:
-                dominant["clock_source"] = f"unavailable: {cnote}"
         graphs = world * b * args.steps
         value = graphs / elapsed
         out = {
@@ -729,39 +701,80 @@ def main():
             "ms_per_step": round(elapsed / args.steps * 1e3, 4), "ms_per_step_by_rank": rank_ms, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "edges_per_s": round(value * n * shp["K"] * depth, 1), "range_check": _ops.RANGE_CHECK, "priming_steps": PRIME_STEPS + PRIME_SYNC,
-            f"value_range_check_{other_mode}": None if value_other is None else round(value_other, 2),
             "config": {"workload": workload_label(kwargs, b, n, shp["K"]), "name": args.workload,
                        "graphs_per_gpu": b, "nodes": n, "neighbors": shp["K"], "layers": depth, "global_batch": world * b,
                        "mask": "ragged" if args.ragged_mask else "all-true",
                        "parallelism": f"batch-shard x{world} (no data-path collective)"},
             "head": git_head(),
-            "roofline": dominant,
-            "kernels": kernels,
-            "other_kernels_ms_per_step": other,
-            "sum_kernel_ms": round(sum(per_kernel[k] * launches[k] for k in per_kernel), 4),
         }
         if dumped is not None:
             out["dump_outputs"] = dumped
-        if world == 1 and PRIME_STEPS > 0 and not args.no_live_traffic and os.environ.get("EGNN_BENCH_TRAFFIC_CHILD") != "1" and not under_profiler:
-            uv, why = unprimed_value(args)
-            out["value_unprimed"] = round(uv, 2) if uv is not None else None
-            if uv is None:
-                out["value_unprimed_note"] = f"child run failed: {why}"
-        if (world == 1 and not args.ragged_mask and not args.no_live_traffic and os.environ.get("EGNN_BENCH_TRAFFIC_CHILD") != "1"
-                and not under_profiler and not kwargs.get("only_sparse_neighbors")):
-            # a padded batch (the parity protocol's ragged masks, SURVEY.md section 8d: len ~ U{N/2..N}): the edge pass and the projection
-            # skip the padded nodes.  Secondary figure; `value` is the all-true batch the metric is defined on.
-            rv, why = child_value(args, ["--ragged-mask"])
-            out["value_ragged_masks"] = round(rv, 2) if rv is not None else None
-            if rv is None:
-                out["value_ragged_masks_note"] = f"child run failed: {why}"
         if dist is not None:
             out["process_group"] = {"backend": dist.get_backend(), "world_size": world}
-        if not args.no_cpu_baseline and world == 1:          # the CPU leg is timed at N = 1 only
-            out["cpu_baseline"] = cpu_baseline(args.workload, kwargs, n)
+        if args.full:
+            out[f"value_range_check_{other_mode}"] = None if value_other is None else round(value_other, 2)
+            # kernels ordered by their share of the step; the roofline object is the dominant one
+            order = sorted(per_kernel.items(), key=lambda kv: -kv[1] * launches[kv[0]])
+            kernels = [roofline_entry(k, counts, ms, launches[k]) for k, ms in order if k in counts]
+            other = {k: round(ms * launches[k], 4) for k, ms in order if k not in counts}
+            dominant = dict(next(kr for kr in kernels if kr["bound"] in ("hbm", "mfma")))
+            traffic = thead = None
+            tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(tpath):
+                try:
+                    tj = json.load(open(tpath))
+                    per_wl = tj.get(args.workload, tj if args.workload == "north_star" and "north_star" not in tj else {})
+                    traffic = per_wl.get(dominant["kernel"])
+                    thead = per_wl.get("_head", tj.get("_head"))
+                except Exception:
+                    traffic = None
+            dominant["traffic_profile"] = traffic                # (the committed profile's figure, with the commit it was taken at)
+            dominant["traffic_head"] = thead
+            src = "profiles/pmc_traffic.json: (2 FETCH_SIZE + WRITE_SIZE) * 1024 per launch, separate rocprofv3 --pmc passes " \
+                  "of this command (tools/profile.sh)" if traffic is not None else None
+            under_profiler = "rocprofiler" in os.environ.get("LD_PRELOAD", "") or any(k.startswith("ROCPROF") for k in os.environ)
+            live_ok = world == 1 and not args.no_live_traffic and os.environ.get("EGNN_BENCH_TRAFFIC_CHILD") != "1" and not under_profiler
+            if live_ok:
+                live, note = live_traffic(args.workload, dominant["kernel"])
+                if live is not None:
+                    traffic, src = live, note
+                    dominant["traffic_head"] = git_head()
+                else:
+                    src = (src or "none") + f" [live measurement unavailable: {note}]"
+            dominant["traffic"] = traffic
+            dominant["traffic_source"] = src
+            # the clock each kernel actually ran at (the chip clocks to its power budget: the MFMA peak of 2.5 PFLOP/s assumes 2.4 GHz)
+            if live_ok:
+                clocks, cnote = live_clocks(args.workload)
+                if clocks:
+                    for kr in kernels + [dominant]:
+                        ghz = clocks.get(kr["kernel"])
+                        if ghz:
+                            kr["effective_clock_ghz"] = ghz
+                            if kr["bound"] == "mfma":
+                                kr["frac_at_clock"] = round(kr["frac"] * 2.4 / ghz, 4)
+                    dominant["clock_source"] = cnote
+                else:
+                    dominant["clock_source"] = f"unavailable: {cnote}"
+            out.update(roofline=dominant, kernels=kernels, other_kernels_ms_per_step=other,
+                       sum_kernel_ms=round(sum(per_kernel[k] * launches[k] for k in per_kernel), 4))
+            if live_ok and PRIME_STEPS > 0:
+                uv, why = unprimed_value(args)
+                out["value_unprimed"] = round(uv, 2) if uv is not None else None
+                if uv is None:
+                    out["value_unprimed_note"] = f"child run failed: {why}"
+            if live_ok and not args.ragged_mask and not kwargs.get("only_sparse_neighbors"):
+                # a padded batch (the parity protocol's ragged masks, SURVEY.md section 8d: len ~ U{N/2..N}): the edge pass and the projection
+                # skip the padded nodes.  Secondary figure; `value` is the all-true batch the metric is defined on.
+                rv, why = child_value(args, ["--ragged-mask"])
+                out["value_ragged_masks"] = round(rv, 2) if rv is not None else None
+                if rv is None:
+                    out["value_ragged_masks_note"] = f"child run failed: {why}"
+            if not args.no_cpu_baseline and world == 1:          # the CPU leg is timed at N = 1 only
+                out["cpu_baseline"] = cpu_baseline(args.workload, kwargs, n)
         if args.reference_eager and world == 1:
             out["reference_gpu_eager"] = reference_gpu_eager(kwargs, b, n, device)
-        default_train = args.workload == "north_star" and not args.no_train_step
+        default_train = args.full and args.workload == "north_star" and not args.no_train_step
         if (args.train_step or default_train) and world == 1 and not is_net:
             # after the timed inference region (never part of `value`): must not cost the line if it fails
             try:

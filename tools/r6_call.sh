@@ -7,7 +7,7 @@
 TAG="${1:-r6}"; SUITE="${2:-1}"; TRACE="${3:-1}"; shift 3
 REPO="$(pwd)"; OUT="$REPO/gpurun_out/$TAG"; mkdir -p "$OUT"; export TMPDIR=/tmp
 if [ "$SUITE" = 1 ]; then bash tools/gpu_suite.sh "$TAG"; fi
-python bench.py --no-cpu-baseline --no-train-step --no-live-traffic "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"
+python bench.py --full --no-cpu-baseline --no-train-step --no-live-traffic "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"
 python - <<PY
 import json
 d = json.load(open("$OUT/bench.json"))
@@ -16,7 +16,7 @@ print({k["kernel"]: k["avg_ms"] for k in d.get("kernels", [])})
 PY
 if [ "$TRACE" = 1 ]; then
   cd /tmp
-  rocprofv3 --kernel-trace -d "$OUT/trace" -o trace --output-format csv -- python "$REPO/bench.py" --steps 8 --warmup 3 --no-cpu-baseline --no-train-step --no-live-traffic "$@" > "$OUT/trace.log" 2>&1
+  rocprofv3 --kernel-trace -d "$OUT/trace" -o trace --output-format csv -- python "$REPO/bench.py" --full --steps 8 --warmup 3 --no-cpu-baseline --no-train-step --no-live-traffic "$@" > "$OUT/trace.log" 2>&1
   cd "$REPO"
   CSV="$(find "$OUT/trace" -name '*kernel_trace.csv' | head -1)"
   python tools/timeline.py "$CSV" 3 > "$OUT/timeline.txt" 2>&1; tail -45 "$OUT/timeline.txt"

@@ -1,7 +1,7 @@
 """Gaps between the kernels of one forward step, from a rocprofv3 --kernel-trace CSV:   python tools/timeline.py <kernel_trace.csv> [steps] [from=<index>]
 Prints, for the last `steps` steps (a step starts at node_prep_hl_kernel) -- or for `steps` steps from step number `from=` on, counted from
-the start of the trace: bench.py's timed region lies behind its priming + warm-up steps, its per-kernel timing (events between the
-launches) at the end -- every kernel's start relative to the step, its duration and the idle gap before it on the union of all streams."""
+the start of the trace: bench.py's timed region lies behind its priming + warm-up steps, the per-kernel timing of `--full` (events
+between the launches) at the end -- every kernel's start relative to the step, its duration and the idle gap before it on the union of all streams."""
 import csv
 import sys
 

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Kernel trace of the training step at the north-star shape (GPU box, from the repo root):   bash tools/train_trace.sh <tag>
-# rocprofv3 --kernel-trace --stats over `bench.py --train-step` (4 forward + backward pairs after the timed inference region);
+# rocprofv3 --kernel-trace --stats over `bench.py --full --train-step` (4 forward + backward pairs after the timed inference region);
 # prints every kernel's calls / total / average so that the backward's ATen kernels and gaps can be read off next to ours.
 TAG="${1:-train}"
 REPO="$(pwd)"
@@ -8,7 +8,7 @@ OUT="$REPO/gpurun_out/train_$TAG"
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o trace --output-format csv -- python $REPO/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-live-traffic --train-step > "$OUT/trace.log" 2>&1
+rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o trace --output-format csv -- python $REPO/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-live-traffic --train-step > "$OUT/trace.log" 2>&1
 echo "trace rc=$?"
 grep "^{\"metric\"" "$OUT/trace.log" | tail -1 > "$OUT/bench_line.json"
 cd "$REPO"
