@@ -16,7 +16,7 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int
 
 import torch  # noqa: F401  (must precede CDLL, see module docstring)
 
-ABI_VERSION = 40
+ABI_VERSION = 41
 _LIB_NAME = "libegnn_hip.so"
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 
@@ -36,6 +36,8 @@ SYMBOLS = (
     "egnn_edge_exact_bwd_f32", "egnn_edge_exact_bwd_f64", "egnn_edge_exact_node_sums_f32", "egnn_edge_exact_node_sums_f64",
     "egnn_edge_tail_exact_bwd_f32", "egnn_edge_tail_exact_bwd_f64", "egnn_status_publish",
     "egnn_node_mlp_fused_halves", "egnn_node_mlp_fused_pack_f16", "egnn_node_mlp_fused_f32",
+    "egnn_edge_hidden_fwd_f32", "egnn_edge_hidden_fwd_f64", "egnn_edge_hidden_bwd_f32", "egnn_edge_hidden_bwd_f64",
+    "egnn_edge_hidden_bwd2_f32", "egnn_edge_hidden_bwd2_f64",
 )
 
 
@@ -100,6 +102,17 @@ class EdgeTailExactArgs(Structure):
         ("W3", c_void_p), ("b3", c_void_p), ("W4", c_void_p), ("b4", c_void_p), ("scale", c_void_p), ("gate_w", c_void_p), ("gate_b", c_void_p),
         ("gU", c_void_p), ("g_rel", c_void_p), ("ghid_t", c_void_p), ("a3_t", c_void_p), ("mm_t", c_void_p), ("m0_t", c_void_p),
         ("g_w", c_void_p), ("g_scale", c_void_p), ("g_gate", c_void_p),
+        ("drop_thr", c_uint32), ("drop_seed", c_uint32), ("drop_inv_keep", c_float), ("drop_eid0", c_int64),
+    ]
+
+
+class EdgeHiddenArgs(Structure):
+    """Mirror of `struct egnn_edge_hidden_args` (include/egnn_hip.h): the E x H block as a twice-differentiable op."""
+    _fields_ = [
+        ("B", c_int32), ("N", c_int32), ("K", c_int32), ("m_dim", c_int32), ("H", c_int32), ("S", c_int32),
+        ("idx", c_void_p), ("Pi", c_void_p), ("Pj", c_void_p), ("s", c_void_p), ("Ws", c_void_p), ("W2", c_void_p), ("b2", c_void_p),
+        ("gU", c_void_p), ("cPi", c_void_p), ("cPj", c_void_p), ("cs", c_void_p), ("cWs", c_void_p), ("cW2", c_void_p), ("cb2", c_void_p),
+        ("u", c_void_p), ("A_T", c_void_p), ("DZ_T", c_void_p), ("g_s", c_void_p), ("g_gU", c_void_p), ("DAV_T", c_void_p), ("R_T", c_void_p),
         ("drop_thr", c_uint32), ("drop_seed", c_uint32), ("drop_inv_keep", c_float), ("drop_eid0", c_int64),
     ]
 
@@ -387,6 +400,10 @@ def load():
     for fn in (lib.egnn_edge_tail_exact_bwd_f32, lib.egnn_edge_tail_exact_bwd_f64):
         fn.restype = c_int
         fn.argtypes = [POINTER(EdgeTailExactArgs), c_void_p]
+    for name in ("egnn_edge_hidden_fwd_f32", "egnn_edge_hidden_fwd_f64", "egnn_edge_hidden_bwd_f32", "egnn_edge_hidden_bwd_f64",
+                 "egnn_edge_hidden_bwd2_f32", "egnn_edge_hidden_bwd2_f64"):
+        getattr(lib, name).restype = c_int
+        getattr(lib, name).argtypes = [POINTER(EdgeHiddenArgs), c_void_p]
     for fn in (lib.egnn_edge_exact_node_sums_f32, lib.egnn_edge_exact_node_sums_f64):
         fn.restype = c_int
         fn.argtypes = [c_void_p, c_int64, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
@@ -399,7 +416,7 @@ def load():
     lib.egnn_struct_bytes.restype = c_int64
     lib.egnn_struct_bytes.argtypes = [c_int]
     for which, mirror in enumerate((EdgeArgs, EdgeBwdArgs, EdgeTailArgs, LayerDesc, PackedInfo, EdgeExactArgs, EdgeExactBwdArgs, EdgeTailExactArgs,
-                                    ForwardOpts)):
+                                    ForwardOpts, EdgeHiddenArgs)):
         if lib.egnn_struct_bytes(which) != ctypes.sizeof(mirror):
             raise EGNNHipError(f"{path}: sizeof({mirror.__name__}) = {ctypes.sizeof(mirror)} here, {lib.egnn_struct_bytes(which)} in the "
                                f"library: the ctypes mirror in _abi.py and include/egnn_hip.h disagree")

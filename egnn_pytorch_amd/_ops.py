@@ -590,6 +590,15 @@ def edge_exact_bwd(args: "_abi.EdgeExactBwdArgs", dtype):
     _abi.check(rc, "egnn_edge_exact_bwd_f64" if f64 else "egnn_edge_exact_bwd_f32")
 
 
+def edge_hidden(which, args: "_abi.EdgeHiddenArgs", dtype):
+    """egnn_edge_hidden_{fwd, bwd, bwd2}_f32 / _f64 (include/egnn_hip.h): the E x H block of the layer -- forward, first-order and
+    second-order backward -- for one chunk of graphs; dtype = what the data pointers of args hold."""
+    name = f"egnn_edge_hidden_{which}_{'f64' if dtype == torch.float64 else 'f32'}"
+    with _timed("edge_hidden_" + which):
+        rc = getattr(_abi.load(), name)(byref(args), _stream())
+    _abi.check(rc, name)
+
+
 def edge_exact_node_sums(dz_t, nodes, k, order, seg):
     """egnn_edge_exact_node_sums_*: (d/d P_i, its transpose, d/d P_j, its transpose) -- (nodes, H), (H, nodes) twice -- from dz^T (H, E):
     the K edges leaving a node and the edges arriving at it (CSR lists of egnn_dest_lists_i32), summed in a fixed order."""

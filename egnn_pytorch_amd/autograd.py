@@ -156,10 +156,19 @@ def _edge_rows(b, n, k, device, graph_offset):
     return (torch.arange(b * n * k, device=device) + graph_offset * n * k).view(b, n, k)
 
 
-def layer_tail(layer, feats, coors, u, rel, mask, idx, rank, valid_radius, drop=None, graph_offset=0):
+def _norm_twice(rel):
+    """|rel| over the last dimension with finite derivatives of every order at rel = 0 (torch's norm has a NaN second derivative there:
+    the self pair of every k-NN row).  Below sqrt(tiny) it is 0 -- inside CoorsNorm's clamp to eps, where the gradient is 0 either way."""
+    sq = (rel * rel).sum(dim=-1, keepdim=True)
+    tiny = torch.finfo(rel.dtype).tiny
+    return torch.where(sq > tiny, sq.clamp(min=tiny).sqrt(), torch.zeros_like(sq))
+
+
+def layer_tail(layer, feats, coors, u, rel, mask, idx, rank, valid_radius, drop=None, graph_offset=0, twice=False):
     """Everything of EGNN.forward behind the second Linear of edge_mlp (:183-341): u (B,N,K,m_dim) = edge_mlp[3](...) ->
     second SiLU, gate, masks, coors_mlp / CoorsNorm / clamp / coordinate update, pooling, node_norm + node_mlp + residual.
-    drop = (p, seed): training-mode dropout with the kernels' hash masks (egnn_pytorch_amd/_dropout.py)."""
+    drop = (p, seed): training-mode dropout with the kernels' hash masks (egnn_pytorch_amd/_dropout.py).
+    twice: CoorsNorm's norm through `_norm_twice` (second-order autograd)."""
     from . import _dropout
     b = feats.shape[0]
     m_ij = layer.edge_mlp[4](u)
@@ -182,7 +191,7 @@ def layer_tail(layer, feats, coors, u, rel, mask, idx, rank, valid_radius, drop=
         else:
             w = _per_edge(layer.coors_mlp, m_ij).squeeze(-1)                      # (:303-304)
         if layer.norm_coors:                                                      # CoorsNorm (:67-77)
-            norm = rel.norm(dim=-1, keepdim=True)
+            norm = _norm_twice(rel) if twice else rel.norm(dim=-1, keepdim=True)
             rel = rel / norm.clamp(min=layer.coors_norm.eps) * layer.coors_norm.scale
         if pair_mask is not None:
             w = w.masked_fill(~pair_mask, 0.0)
@@ -284,17 +293,27 @@ def tail_edge_backward(layer, u, coors, idx, pair_mask, g_coors_out, g_msum):
 
 
 def layer_given_neighbors(layer, feats, coors, edges, mask, idx, rank, valid_radius, factorised=True, drop=None, graph_offset=0,
-                          edges_by_k=False):
+                          edges_by_k=False, edge_hidden=False):
     """EGNN.forward (egnn_pytorch.py:262-341) for given neighbours.
     idx (B,N,K) int64 / rank (B,N,K): the selection of :258 (None, None = dense all-pairs, K = N).
     edges_by_k: `edges` are (B,N,K,edge_dim), the features of the selected pairs (see `edge_scalars`).
     Differentiable in feats, coors, edges and the parameters of `layer`.
     factorised: evaluate the first Linear of edge_mlp as (W_i h_i + b) + W_j h_j + W_s s_ij with the dim-wide products done
     once per node -- the same factorisation the HIP forward uses, 16x fewer flops than Linear(cat(...)) at
-    the north-star shape, identical mathematics; False = the reference's literal cat + Linear."""
+    the north-star shape, identical mathematics; False = the reference's literal cat + Linear.
+    edge_hidden: the E x H block (first Linear, dropout, SiLU, second Linear) as `EdgeHidden`, twice differentiable without an E x H
+    tensor in ATen -- what second-order autograd runs (`_backward_twice`)."""
     b, n, dim = feats.shape
     dense = idx is None
     rel, scal = edge_scalars(layer, coors, edges, idx, edges_by_k)
+    if edge_hidden:
+        # (x_i - x_i of a self pair is identically 0: written as a constant 0, so that CoorsNorm's 1 / eps Jacobian does not turn the
+        # exact cancellation of its two terms into rounding noise -- what csrc/edge_tail.hip does at first order)
+        own = (torch.eye(n, dtype=torch.bool, device=coors.device)[None] if dense else
+               idx == torch.arange(n, device=coors.device)[None, :, None])
+        rel = rel.masked_fill(own[..., None], 0.0)
+        u = _edge_hidden_block(layer, feats, scal, idx, drop, graph_offset)
+        return layer_tail(layer, feats, coors, u, rel, mask, idx, rank, valid_radius, drop, graph_offset, twice=True)
     lin = layer.edge_mlp[0]
     if factorised:
         w_i, w_j, w_s = lin.weight[:, :dim], lin.weight[:, dim:2 * dim], lin.weight[:, 2 * dim:]
@@ -317,6 +336,320 @@ def layer_given_neighbors(layer, feats, coors, edges, mask, idx, rank, valid_rad
         for mod in list(layer.edge_mlp)[1:4]:                                     # dropout | Identity, SiLU, Linear
             u = mod(u)
     return layer_tail(layer, feats, coors, u, rel, mask, idx, rank, valid_radius, drop, graph_offset)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Second order (create_graph=True): the E x H block of `layer_given_neighbors` as a twice-differentiable op.  `EdgeHidden` computes
+#     z = P_i[i] + P_j[j] + W_s s  ->  dropout  ->  SiLU  ->  Linear  ->  u (E, m)
+# and its backward is `EdgeHiddenGrad`, whose forward is the block's first-order backward and whose backward (once_differentiable) is
+# the second-order one.  On the device both run on csrc/edge_hidden.hip; on host tensors (the tests) they evaluate the closed forms
+# below, which are the kernels' specification.  Per edge e = (b, i, k) with neighbour j; d = the dropout factor (hash mask / keep, or 1):
+#     x = d (P_i[i] + P_j[j] + W_s s_e);  sig = sigmoid(x);  a = x sig
+#     a1 = sig (1 + x (1 - sig))                      (SiLU')
+#     a2 = sig (1 - sig) (2 + x (1 - 2 sig))          (SiLU'')
+#     u_e = W2 a + b2
+# First order, given gU_e:
+#     g_a = W2^T gU_e;  dz_e = d a1 g_a
+#     dP_i[n] = sum of dz_e over the edges leaving n;  dP_j[n] = over the edges arriving at n
+#     dW_s = sum dz_e s_e^T;  ds_e = W_s^T dz_e;  dW2 = sum gU_e a_e^T;  db2 = sum gU_e
+# Second order, given the cotangents Pbar_i, Pbar_j, Wbar_s, sbar, Wbar2, bbar2 of those six outputs:
+#     v_e = Pbar_i[i] + Pbar_j[j] + Wbar_s s_e + W_s sbar_e
+#     r_e = d (d a2 g_a v_e + a1 Wbar2^T gU_e)                           (d/d z_e)
+#     d/d gU_e = W2 (d a1 v_e) + Wbar2 a_e + bbar2
+#     d/d P_i[n] = sum of r_e leaving n;  d/d P_j[n] = sum of r_e arriving at n
+#     d/d W_s = sum (r_e s_e^T + dz_e sbar_e^T);  d/d s_e = W_s^T r_e + Wbar_s^T dz_e
+#     d/d W2 = sum gU_e (d a1 v_e)^T;  b2 gets nothing
+# What the second-order graph keeps per layer: node tables, E x S and E x m tensors -- never E x H; the (H, E) tables of the kernels are
+# transient, per chunk of graphs within _TWICE_BYTES.
+_TWICE_BYTES = _EXACT_BWD_BYTES
+_TWICE_MAX_GRAPHS = 0                 # tests: force the chunking over graphs (0 = by size only)
+# the sums over all edges (d/d W_s, d/d W2) are taken per block of whole graphs of about this many edges and the blocks' partials summed
+# at the end: the same bits whatever the chunking (the chunks are whole numbers of blocks)
+_TWICE_BLOCK_EDGES = 1 << 16
+_EDGE_HIDDEN_SPEC = False             # True: `_backward_twice` runs the block as its torch expression (tools/force_train_timing.py "aten")
+
+
+def _edge_ends(idx, b, n, k, device):
+    """(source row, neighbour row) (E,) int64 of every edge in the (B N, H) node tables; idx (B,N,K) or None (dense, K = N)"""
+    src = torch.arange(b * n, device=device).repeat_interleave(k)
+    base = (torch.arange(b, device=device) * n)[:, None, None]
+    j = torch.arange(n, device=device)[None, None, :].expand(b, n, n) if idx is None else idx.long()
+    return src, (base + j).reshape(-1)
+
+
+def _edge_drop_factor(drop, e, h, dtype, device):
+    """d (E, H): the forward's hash mask of edge_mlp's dropout (drop = (p, seed, first edge id)) times 1 / keep as the kernels hold it
+    (an fp32 number); None without dropout"""
+    if drop is None:
+        return None
+    from . import _dropout
+    p, seed, eid0 = drop
+    keep = _dropout.keep_mask(seed, _dropout.SITE_EDGE, torch.arange(e, device=device) + eid0, torch.arange(h, device=device), p)
+    inv = float(torch.tensor(_dropout.inv_keep(p), dtype=torch.float32))
+    return keep.to(dtype) * inv
+
+
+def edge_hidden_torch(p_i, p_j, s, w_s, w2, b2, idx, drop, dims):
+    """The block as a literal torch expression (differentiable by autograd to any order): u (E, m) from P_i, P_j (B N, H), s (E, S),
+    W_s (H, S), W2 (m, H), b2 (m); idx (B,N,K) or None; drop = (p, seed, first edge id) or None; dims = (B, N, K)."""
+    src, dst = _edge_ends(idx, *dims, p_i.device)
+    z = p_i[src] + p_j[dst] + s @ w_s.t()
+    d = _edge_drop_factor(drop, z.shape[0], z.shape[1], z.dtype, z.device)
+    x = z if d is None else z * d
+    return torch.nn.functional.silu(x) @ w2.t() + b2
+
+
+def _silu_terms(p_i, p_j, s, w_s, idx, drop, dims):
+    src, dst = _edge_ends(idx, *dims, p_i.device)
+    z = p_i[src] + p_j[dst] + s @ w_s.t()
+    d = _edge_drop_factor(drop, z.shape[0], z.shape[1], z.dtype, z.device)
+    x = z if d is None else z * d
+    sg = torch.sigmoid(x)
+    om = 1 - sg
+    return src, dst, (1.0 if d is None else d), x * sg, sg * (1 + x * om), sg * om * (2 + x * (1 - 2 * sg))
+
+
+def edge_hidden_backward_spec(g_u, p_i, p_j, s, w_s, w2, idx, drop, dims):
+    """First-order backward of the block in closed form -> (dP_i, dP_j, ds, dW_s, dW2, db2)."""
+    src, dst, d, a, a1, _ = _silu_terms(p_i, p_j, s, w_s, idx, drop, dims)
+    dz = d * a1 * (g_u @ w2)
+    zeros = torch.zeros_like(p_i)
+    return (zeros.index_add(0, src, dz), zeros.index_add(0, dst, dz), dz @ w_s, dz.t() @ s, g_u.t() @ a, g_u.sum(dim=0))
+
+
+def edge_hidden_double_backward_spec(g_u, p_i, p_j, s, w_s, w2, idx, drop, dims, cot):
+    """Second-order backward of the block in closed form: cot = the cotangents of (dP_i, dP_j, ds, dW_s, dW2, db2) ->
+    (d/d gU, d/d P_i, d/d P_j, d/d s, d/d W_s, d/d W2)."""
+    cpi, cpj, cs, cws, cw2, cb2 = cot
+    src, dst, d, a, a1, a2 = _silu_terms(p_i, p_j, s, w_s, idx, drop, dims)
+    g_a = g_u @ w2
+    v = cpi[src] + cpj[dst] + s @ cws.t() + cs @ w_s.t()
+    dz = d * a1 * g_a
+    dav = d * a1 * v
+    r = d * (d * a2 * g_a * v + a1 * (g_u @ cw2))
+    zeros = torch.zeros_like(p_i)
+    return (dav @ w2.t() + a @ cw2.t() + cb2, zeros.index_add(0, src, r), zeros.index_add(0, dst, r), r @ w_s + dz @ cws,
+            r.t() @ s + dz.t() @ cs, g_u.t() @ dav)
+
+
+def _eh_args(dims, lo, hi, p_i, p_j, s, w_s, w2, idx, drop):
+    """egnn_edge_hidden_args for graphs [lo, hi): the node rows, edges and neighbour list of those graphs"""
+    from . import _abi, _ops
+    b, n, k = dims
+    a = _abi.EdgeHiddenArgs()
+    a.B, a.N, a.K, a.m_dim, a.H, a.S = hi - lo, n, k, w2.shape[0], w_s.shape[0], w_s.shape[1]
+    a.idx = None if idx is None else idx[lo:hi].data_ptr()
+    a.Pi, a.Pj = p_i[lo * n:hi * n].data_ptr(), p_j[lo * n:hi * n].data_ptr()
+    a.s, a.Ws, a.W2 = s[lo * n * k:hi * n * k].data_ptr(), w_s.data_ptr(), w2.data_ptr()
+    if drop is not None:
+        _ops.set_drop(a, drop[:2], drop[2] + lo * n * k)
+    return a
+
+
+def _eh_plan(dims, h, tables, esz):
+    """(graphs per chunk, graphs per contraction block): the chunks keep `tables` (H, E) tables within _TWICE_BYTES (a single graph whose
+    tables alone exceed it is one chunk) and are whole numbers of blocks; the blocks depend on the shape and the budget only"""
+    b, n, k = dims
+    fit = max(1, min(b, int(_TWICE_BYTES // max(1, tables * n * k * h * esz))))     # graphs whose tables fit the budget (at least one)
+    blk = max(1, min(fit, _TWICE_BLOCK_EDGES // max(1, n * k)))
+    step = fit if _TWICE_MAX_GRAPHS <= 0 else min(fit, _TWICE_MAX_GRAPHS)
+    return max(blk, step // blk * blk), blk
+
+
+def _contig(*ts):
+    return tuple(None if t is None else t.contiguous() for t in ts)
+
+
+def _edge_hidden_fwd_gpu(p_i, p_j, s, w_s, w2, b2, idx, drop, dims):
+    from . import _ops
+    p_i, p_j, s, w_s, w2, b2, idx = _contig(p_i, p_j, s, w_s, w2, b2, idx)
+    b, n, k = dims
+    u = _ops.empty(b * n * k, w2.shape[0], dtype=p_i.dtype, device=p_i.device)
+    if u.numel():
+        a = _eh_args(dims, 0, b, p_i, p_j, s, w_s, w2, idx, drop)
+        a.b2, a.u = b2.data_ptr(), u.data_ptr()
+        _ops.edge_hidden("fwd", a, p_i.dtype)
+    return u
+
+
+def _edge_hidden_bwd_gpu(g_u, p_i, p_j, s, w_s, w2, idx, drop, dims, cot=None):
+    """First order (cot None) -> (dP_i, dP_j, ds, dW_s, dW2, db2) or second order -> (d/d gU, d/d P_i, d/d P_j, d/d s, d/d W_s, d/d W2)
+    on egnn_edge_hidden_bwd_* / _bwd2_*, per chunk of graphs: the per-node sums on egnn_edge_exact_node_sums_*, the sums over all edges
+    on the exact GEMMs per block of graphs (partials summed at the end)."""
+    from . import _ops
+    g_u, p_i, p_j, s, w_s, w2, idx = _contig(g_u, p_i, p_j, s, w_s, w2, idx)
+    second = cot is not None
+    if second:
+        cpi, cpj, cs, cws, cw2, cb2 = _contig(*(c.to(p_i.dtype) for c in cot))
+    dt, dev = p_i.dtype, p_i.device
+    b, n, k = dims
+    h, sd = w_s.shape
+    m = w2.shape[0]
+    e = b * n * k
+    g_pi, g_pj = torch.zeros_like(p_i), torch.zeros_like(p_i)
+    g_s = torch.zeros(e, sd, dtype=dt, device=dev)
+    g_gu = torch.zeros(e, m, dtype=dt, device=dev) if second else None
+    step, blk = _eh_plan(dims, h, 3 if second else 2, 8 if dt == torch.float64 else 4)
+    nb = (b + blk - 1) // blk
+    p_ws = torch.zeros(nb, h, sd, dtype=dt, device=dev)
+    p_w2 = torch.zeros(nb, m, h, dtype=dt, device=dev)
+    if e:
+        gu_t, s_t = g_u.t().contiguous(), s.t().contiguous()
+        cs_t = cs.t().contiguous() if second else None
+        for lo in range(0, b, step):
+            hi = min(b, lo + step)
+            ec, e0 = (hi - lo) * n * k, lo * n * k
+            a = _eh_args(dims, lo, hi, p_i, p_j, s, w_s, w2, idx, drop)
+            a.gU, a.g_s = g_u[e0:e0 + ec].data_ptr(), g_s[e0:e0 + ec].data_ptr()
+            dz_t = _ops.empty(h, ec, dtype=dt, device=dev)
+            a.DZ_T = dz_t.data_ptr()
+            if second:
+                dav_t, r_t = (_ops.empty(h, ec, dtype=dt, device=dev) for _ in range(2))
+                a.cPi, a.cPj = cpi[lo * n:hi * n].data_ptr(), cpj[lo * n:hi * n].data_ptr()
+                a.cs, a.cWs, a.cW2, a.cb2 = cs[e0:e0 + ec].data_ptr(), cws.data_ptr(), cw2.data_ptr(), cb2.data_ptr()
+                a.g_gU, a.DAV_T, a.R_T = g_gu[e0:e0 + ec].data_ptr(), dav_t.data_ptr(), r_t.data_ptr()
+                _ops.edge_hidden("bwd2", a, dt)
+                node_t = r_t
+            else:
+                a_t = _ops.empty(h, ec, dtype=dt, device=dev)
+                a.A_T = a_t.data_ptr()
+                _ops.edge_hidden("bwd", a, dt)
+                node_t = dz_t
+            dl = _ops.dest_lists(None if idx is None else idx[lo:hi], hi - lo, n, k, dev)
+            gpi, _, gpj, _ = _ops.edge_exact_node_sums(node_t, (hi - lo) * n, k, dl.order, dl.seg)
+            g_pi[lo * n:hi * n], g_pj[lo * n:hi * n] = gpi, gpj
+            for g0 in range(lo, hi, blk):
+                c0, c1 = (g0 - lo) * n * k, (min(hi, g0 + blk) - lo) * n * k
+                cols = slice(e0 + c0, e0 + c1)
+                if second:                                           # d/d W_s = r^T s + dz^T sbar;  d/d W2 = gU^T (d a1 v)
+                    t = _ops.linear_f32(r_t[:, c0:c1], s_t[:, cols], sd, c1 - c0, name="twice_dws")
+                    _ops.linear_f32(dz_t[:, c0:c1], cs_t[:, cols], sd, c1 - c0, residual=t, out=p_ws[g0 // blk], name="twice_dws")
+                    _ops.linear_f32(gu_t[:, cols], dav_t[:, c0:c1], h, c1 - c0, out=p_w2[g0 // blk], name="twice_dw2")
+                else:                                                # d/d W_s = dz^T s;  d/d W2 = gU^T a
+                    _ops.linear_f32(dz_t[:, c0:c1], s_t[:, cols], sd, c1 - c0, out=p_ws[g0 // blk], name="twice_dws")
+                    _ops.linear_f32(gu_t[:, cols], a_t[:, c0:c1], h, c1 - c0, out=p_w2[g0 // blk], name="twice_dw2")
+            del dz_t, node_t
+    if second:
+        return g_gu, g_pi, g_pj, g_s, p_ws.sum(dim=0), p_w2.sum(dim=0)
+    return g_pi, g_pj, g_s, p_ws.sum(dim=0), p_w2.sum(dim=0), g_u.sum(dim=0)
+
+
+class EdgeHidden(torch.autograd.Function):
+    """u (E, m) = W2 SiLU(d (P_i[i] + P_j[j] + W_s s)) + b2, twice differentiable (the closed forms above).  Inputs: P_i, P_j (B N, H),
+    s (E, S), W_s (H, S), W2 (m, H), b2 (m), idx int32 (B,N,K) or None (dense, K = N), drop = (p, seed, first edge id) or None,
+    dims = (B, N, K)."""
+
+    @staticmethod
+    def forward(ctx, p_i, p_j, s, w_s, w2, b2, idx, drop, dims):
+        ctx.save_for_backward(p_i, p_j, s, w_s, w2)
+        ctx.meta = (idx, drop, dims)
+        if not p_i.is_cuda:
+            return edge_hidden_torch(p_i, p_j, s, w_s, w2, b2, idx, drop, dims)
+        return _edge_hidden_fwd_gpu(p_i, p_j, s, w_s, w2, b2, idx, drop, dims)
+
+    @staticmethod
+    def backward(ctx, g_u):
+        p_i, p_j, s, w_s, w2 = ctx.saved_tensors
+        return EdgeHiddenGrad.apply(g_u, p_i, p_j, s, w_s, w2, *ctx.meta) + (None, None, None)
+
+
+class EdgeHiddenGrad(torch.autograd.Function):
+    """forward: the first-order backward of `EdgeHidden` -> (dP_i, dP_j, ds, dW_s, dW2, db2); backward: the second-order one
+    (`EdgeHiddenGradGrad`: a third order raises)."""
+
+    @staticmethod
+    def forward(ctx, g_u, p_i, p_j, s, w_s, w2, idx, drop, dims):
+        ctx.save_for_backward(g_u, p_i, p_j, s, w_s, w2)
+        ctx.meta = (idx, drop, dims)
+        if not g_u.is_cuda:
+            return edge_hidden_backward_spec(g_u, p_i, p_j, s, w_s, w2, idx, drop, dims)
+        return _edge_hidden_bwd_gpu(g_u, p_i, p_j, s, w_s, w2, idx, drop, dims)
+
+    @staticmethod
+    def backward(ctx, cpi, cpj, cs, cws, cw2, cb2):
+        saved = ctx.saved_tensors
+        if torch.is_grad_enabled():                  # (a graph of the second order: the primal operands behind the third-order guard)
+            saved = _ThirdOrderGuard.apply(*saved)
+        return EdgeHiddenGradGrad.apply(*saved, cpi, cpj, cs, cws, cw2, cb2, *ctx.meta) + (None, None, None)
+
+
+class EdgeHiddenGradGrad(torch.autograd.Function):
+    """The second-order backward of `EdgeHidden`: (gU, P_i, P_j, s, W_s, W2; the cotangents Pbar_i, Pbar_j, sbar, Wbar_s, Wbar2, bbar2) ->
+    (d/d gU, P_i, P_j, s, W_s, W2).  It is linear in the cotangents; its derivative with respect to them (what
+    torch.autograd.functional.hvp's double-backward trick asks for -- still second order) is the JVP of the first-order map F = EdgeHiddenGrad
+    in the direction of the incoming gradients (gU', P_i', P_j', s', W_s', W2'):
+        z' = P_i'[i] + P_j'[j] + W_s' s + W_s s';  dz' = d (d a2 g_a z' + a1 W2'^T gU) + d a1 W2^T gU'
+        F' = (node sums of dz', dz' W_s + dz W_s', sum (dz' s^T + dz s'^T), sum (gU' a^T + gU (d a1 z')^T), sum gU')
+    = this op with the cotangents (P_i', P_j', s', W_s', W2', 0) plus EdgeHiddenGrad with gU' -- both ops themselves, so the rule holds at
+    every order it is asked at.  Its derivative with respect to the primal operands is a third derivative: those operands come through
+    `_ThirdOrderGuard`, which raises when a gradient actually has to pass it."""
+
+    @staticmethod
+    def forward(ctx, g_u, p_i, p_j, s, w_s, w2, cpi, cpj, cs, cws, cw2, cb2, idx, drop, dims):
+        saved, cot = (g_u, p_i, p_j, s, w_s, w2), (cpi, cpj, cs, cws, cw2, cb2)
+        ctx.save_for_backward(*saved)
+        ctx.meta = (idx, drop, dims)
+        ctx.cb2_shape = cb2.shape
+        if not g_u.is_cuda:
+            return edge_hidden_double_backward_spec(*saved, idx, drop, dims, cot)
+        return _edge_hidden_bwd_gpu(*saved, idx, drop, dims, cot=cot)
+
+    @staticmethod
+    def backward(ctx, d_gu, d_pi, d_pj, d_s, d_ws, d_w2):
+        saved = ctx.saved_tensors
+        g_u, p_i, p_j, s, w_s, w2 = saved
+        zero = lambda t, like: torch.zeros_like(like) if t is None else t           # noqa: E731
+        d_gu, d_pi, d_pj, d_s, d_ws, d_w2 = (zero(t, like) for t, like in zip((d_gu, d_pi, d_pj, d_s, d_ws, d_w2), saved))
+        need = ctx.needs_input_grad
+        cot_grads = (None,) * 6
+        if any(need[6:12]):
+            cb2_zero = torch.zeros(ctx.cb2_shape, dtype=w2.dtype, device=w2.device)
+            jv = EdgeHiddenGradGrad.apply(*saved, d_pi, d_pj, d_s, d_ws, d_w2, cb2_zero, *ctx.meta)      # (_, dP_i', dP_j', ds', dW_s', dW2')
+            fv = EdgeHiddenGrad.apply(d_gu, p_i, p_j, s, w_s, w2, *ctx.meta)                                  # terms linear in gU'
+            cot_grads = (jv[1] + fv[0], jv[2] + fv[1], jv[3] + fv[2], jv[4] + fv[3], jv[5] + fv[4], fv[5])
+        # the primal operands: a third derivative -- zeros here, handed to `_ThirdOrderGuard` (inputs of this op under a second-order graph),
+        # which raises only if autograd needs a gradient through it
+        primal = tuple(torch.zeros_like(t) if need[i] else None for i, t in enumerate(saved))
+        return primal + cot_grads + (None, None, None)
+
+
+class _ThirdOrderGuard(torch.autograd.Function):
+    """Identity on the primal operands of `EdgeHiddenGradGrad`; its backward raises: a gradient through it is a third derivative.  (torch's
+    once_differentiable hangs its error node on detached copies of the outputs, which torch.autograd.grad(..., inputs=...) prunes -- a
+    third order would come out silently incomplete; this node stays connected to its inputs, so a third order reaches it and raises,
+    while second-order products that differentiate only with respect to cotangents -- hvp's double-backward trick -- never visit it.)"""
+
+    @staticmethod
+    def forward(ctx, *ts):
+        return tuple(t.clone() for t in ts)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        raise RuntimeError("egnn_pytorch_amd.EGNN is twice differentiable: a third-order derivative (through the edge MLP's E x H block, "
+                           "autograd.EdgeHidden) is not supported; second-order products (torch.autograd.functional.hvp / vhp / hessian) are")
+
+
+def _edge_hidden_block(layer, feats, scal, idx, drop, graph_offset):
+    """u (B,N,K,m) of `layer_given_neighbors` through `EdgeHidden`: the node tables P_i, P_j and the per-edge scalars in ATen, the
+    E x H work in the op"""
+    b, n, dim = feats.shape
+    k = scal.shape[2]
+    lin, lin2 = layer.edge_mlp[0], layer.edge_mlp[3]
+    w_i, w_j, w_s = lin.weight[:, :dim], lin.weight[:, dim:2 * dim], lin.weight[:, 2 * dim:]
+    p_i = (feats @ w_i.t() + lin.bias).reshape(b * n, -1)
+    p_j = (feats @ w_j.t()).reshape(b * n, -1)
+    s = scal.reshape(b * n * k, scal.shape[-1])                                  # (explicit widths: K = 0 has no elements)
+    i32 = None if idx is None else idx.to(torch.int32).contiguous()
+    dr = None if drop is None else (drop[0], drop[1], graph_offset * n * k)
+    fn = edge_hidden_torch if (_EDGE_HIDDEN_SPEC or not edge_hidden_kernels_fit(s.shape[1], s.dtype)) else EdgeHidden.apply
+    return fn(p_i, p_j, s, w_s, lin2.weight, lin2.bias, i32, dr, (b, n, k)).view(b, n, k, lin2.weight.shape[0])
+
+
+def edge_hidden_kernels_fit(s_dim, dtype):
+    """csrc/edge_hidden.hip keeps an edge's scalars, their cotangents and gradients in three LDS columns of 256 threads (at most 160 KB):
+    up to 53 per-edge scalars in fp32, 26 in float64.  Wider layers run the block as its torch expression under autograd (`edge_hidden_torch`:
+    E x H tensors in ATen)."""
+    return 3 * s_dim * 256 * (8 if dtype == torch.float64 else 4) <= 160 * 1024
 
 
 def _exact_active():
@@ -490,7 +823,9 @@ class EGNNFunction(torch.autograd.Function):
                                    "operation: a parameter of egnn_pytorch_amd.EGNN changed between forward and backward "
                                    f"(version {p._version}, expected {v})")
         ctx.table_inputs, ctx.table_grads = True, (None, None)
-        if ctx.has_u:
+        if torch.is_grad_enabled():                 # create_graph=True (also hvp / hessian): gradients that are functions themselves
+            out = _backward_twice(ctx, g_node, g_coors)
+        elif ctx.has_u:
             from . import _ops
             if getattr(ctx, "exact_native", False):
                 out = _backward_exact(ctx, g_node, g_coors)
@@ -1332,6 +1667,71 @@ def _backward_native(ctx, g_node, g_coors):
                   for i, (p, op) in enumerate(zip(params, orig_params))]
     return (None, None, None, None, g_feats.to(in_dtypes[0]) if need[4] else None, g_coors_in.to(in_dtypes[1]) if need[5] else None,
             lk.outputs() if lk is not None else (g_edges.to(in_dtypes[2]) if want_ge else None), *out_params)
+
+
+def _lookup_rows(lookup, idx, b, n, k):
+    """The (B,N,K,edge_dim) features of the selected pairs, gathered from the caller's tensors behind an EdgeLookup (`live`: the dense
+    float edges, the embedding weights) by differentiable indexing: E x D, what egnn_edge_features_gather_f32 reads, under autograd."""
+    edges, tok_w, deg_w = lookup.live
+    dev = (lookup.tok if lookup.tok is not None else (lookup.deg if lookup.deg is not None else edges)).device
+    j = torch.arange(n, device=dev)[None, None, :].expand(b, n, k) if idx is None else idx.long()
+    pair = (torch.arange(b * n, device=dev).view(b, n, 1) * n + j).reshape(-1)          # (b N + i) N + j
+    cols = []
+    if lookup.d1:
+        cols.append(tok_w[lookup.tok.reshape(-1)[pair]] if lookup.tok is not None else edges.reshape(-1, lookup.d1)[pair])
+    if lookup.d2:
+        cols.append(deg_w[lookup.deg.reshape(-1)[pair].long()])
+    return (torch.cat(cols, dim=-1) if len(cols) > 1 else cols[0]).view(b, n, k, lookup.width)
+
+
+def _backward_twice(ctx, g_node, g_coors):
+    """The backward under create_graph=True: the layer re-evaluated from the saved inputs themselves (not detached copies, so that the
+    graph reaches the caller's tensors) over the neighbour list the forward selected, with the E x H block as `EdgeHidden`
+    (`layer_given_neighbors(edge_hidden=True)`), and differentiated by autograd with create_graph=True.  Everything else -- the node
+    tables, node_norm / node_mlp, the per-edge scalars, the E x m tail -- is ATen under autograd; edge look-up tables are gathered from
+    their live tensors (`_lookup_rows`); training-mode dropout re-uses the forward's hash masks.  fp32 modules compute in plain fp32,
+    float64 modules in float64."""
+    layer = ctx.layer
+    params = list(layer.parameters())
+    pd = params[0].dtype if params else torch.float32
+    if pd not in (torch.float32, torch.float64):
+        raise NotImplementedError(f"second-order autograd (create_graph=True) through egnn_pytorch_amd.EGNN needs a float32 or float64 "
+                                  f"module (its parameters are {pd}); convert it with .float() or .double()")
+    feats, coors, edges, mask, idx32, rank = _unpack(ctx)
+    need = _need(ctx)                                # (layer, order_hint, mask, adj, feats, coors, edges, *params)
+    b, n, _ = feats.shape
+    k = idx32.shape[-1] if idx32 is not None else n
+    idx = None if idx32 is None else idx32.long()
+    by_k = getattr(ctx, "edges_by_k", False)
+    lookup = ctx.lookup
+    e_in = _lookup_rows(lookup, idx, b, n, k).to(pd) if by_k else (None if edges is None else edges.to(pd))
+    out_n, out_c = layer_given_neighbors(layer, feats.to(pd), coors.to(pd), e_in, mask, idx, None if rank is None else rank.to(pd),
+                                         ctx.valid_radius, drop=getattr(ctx, "drop", None), edges_by_k=by_k, edge_hidden=True)
+    unused = _unused_params(layer, ctx)
+    slots = []                                       # (position in the returned layout or table name, tensor)
+    for pos, t in ((4, feats), (5, coors)):
+        if need[pos] and t.requires_grad:
+            slots.append((pos, t))
+    if by_k:
+        for name, pos, t in (("edges", 6, lookup.live[0]), ("tok", 8, lookup.live[1]), ("deg", 9, lookup.live[2])):
+            if t is not None and ctx.needs_input_grad[pos] and t.requires_grad:
+                slots.append((name, t))
+    elif edges is not None and need[6] and edges.requires_grad:
+        slots.append((6, edges))
+    for i, p in enumerate(params):
+        if need[7 + i] and p.requires_grad and id(p) not in unused:
+            slots.append((7 + i, p))
+    outs, gouts = [], []
+    for o, g in ((out_n, g_node), (out_c, g_coors)):
+        if g is not None and o.requires_grad:
+            outs.append(o)
+            gouts.append(g.to(o.dtype))
+    wrt = [t for _, t in slots]
+    grads = torch.autograd.grad(outs, wrt, gouts, create_graph=True, allow_unused=True) if (outs and wrt) else [None] * len(wrt)
+    got = {pos: g for (pos, _), g in zip(slots, grads)}
+    ctx.table_grads = (got.get("tok"), got.get("deg"))
+    return (None, None, None, None, got.get(4), got.get(5), got.get("edges") if by_k else got.get(6)) + tuple(
+        got.get(7 + i) for i in range(len(params)))
 
 
 def _backward_recompute(ctx, g_node, g_coors):

@@ -455,6 +455,7 @@ extern "C" int64_t egnn_struct_bytes(int which)
     case 6: return (int64_t)sizeof(egnn_edge_exact_bwd_args);
     case 7: return (int64_t)sizeof(egnn_edge_tail_exact_args);
     case 8: return (int64_t)sizeof(egnn_forward_opts);
+    case 9: return (int64_t)sizeof(egnn_edge_hidden_args);
     default: return -1;
     }
 }

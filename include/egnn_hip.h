@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define EGNN_ABI_VERSION 40
+#define EGNN_ABI_VERSION 41
 
 enum {
     EGNN_OK = 0,
@@ -55,7 +55,7 @@ enum {
 int egnn_abi_version(void);
 /* sizeof of the argument structs as this library was compiled -- 0: egnn_edge_args, 1: egnn_edge_bwd_args, 2: egnn_edge_tail_args,
  * 3: egnn_layer_desc, 4: the packed-weights info struct, 5: egnn_edge_exact_args, 6: egnn_edge_exact_bwd_args, 7: egnn_edge_tail_exact_args,
- * 8: egnn_forward_opts; -1 otherwise -- so that a binding that mirrors them (ctypes, cgo, JNI) can verify its
+ * 8: egnn_forward_opts, 9: egnn_edge_hidden_args; -1 otherwise -- so that a binding that mirrors them (ctypes, cgo, JNI) can verify its
  * layout at load time instead of corrupting a call. */
 int64_t egnn_struct_bytes(int which);
 /* Hands `nwords` (<= 8) int32 status words to the host without a copy engine and without a stream synchronisation: a one-thread kernel on
@@ -825,6 +825,59 @@ typedef struct egnn_edge_tail_exact_args {
 } egnn_edge_tail_exact_args;
 int egnn_edge_tail_exact_bwd_f32(const egnn_edge_tail_exact_args* args, void* stream);
 int egnn_edge_tail_exact_bwd_f64(const egnn_edge_tail_exact_args* args, void* stream);
+
+/* The E x H block of the layer as a twice-differentiable op (csrc/edge_hidden.hip; egnn_pytorch_amd/autograd.py::EdgeHidden, whose
+ * `edge_hidden_backward_spec` / `edge_hidden_double_backward_spec` are the specification): what second-order autograd (create_graph=True)
+ * differentiates through.  Per edge e = (b, i, k) with neighbour j (idx, or j = k when idx is NULL and K == N) and d the dropout factor
+ * (the forward's hash mask / keep, or 1):
+ *     x = d (P_i[i] + P_j[j] + W_s s_e);  sig = sigmoid(x);  a = x sig;  a1 = sig (1 + x (1 - sig));  a2 = sig (1 - sig) (2 + x (1 - 2 sig))
+ *   egnn_edge_hidden_fwd_*:  u (E, m_dim) = W2 a + b2.
+ *   egnn_edge_hidden_bwd_*:  given gU (E, m_dim):  g_a = W2^T gU_e;  dz = d a1 g_a;  A_T = a, DZ_T = dz (H, E), TRANSPOSED so that the
+ *                            sums over all edges (d/d W2 = gU^T a, d/d W_s = dz^T s) are C = X W^T products of egnn_linear_f32 / _f64
+ *                            with the edges as the contraction and the per-node sums run on egnn_edge_exact_node_sums_*;  g_s (E, S) = W_s^T dz.
+ *   egnn_edge_hidden_bwd2_*: given also the cotangents cPi, cPj (B N, H), cs (E, S), cWs (H, S), cW2 (m_dim, H), cb2 (m_dim) of the
+ *                            first order's d/d P_i, d/d P_j, d/d s, d/d W_s, d/d W2, d/d b2:
+ *                                v = cPi[i] + cPj[j] + cWs s_e + W_s cs_e;  r = d (d a2 g_a v + a1 cW2^T gU_e)
+ *                            g_gU (E, m_dim) = W2 (d a1 v) + cW2 a + cb2;  g_s (E, S) = W_s^T r + cWs^T dz;
+ *                            DAV_T = d a1 v, R_T = r, DZ_T = dz (H, E)  (d/d P_i, P_j = per-node sums of r; d/d W_s = r^T s + dz^T cs;
+ *                            d/d W2 = gU^T (d a1 v); b2 gets nothing).
+ * Every array is dense and row-major: P tables (B N, H), s (E, S), Ws (H, S), W2 (m_dim, H).  Up to 160 KB of LDS per 256 edges: the
+ * scalars in 1 / 2 / 3 columns (forward / first / second order).  The caller bounds the (H, E) tables by cutting the batch into chunks
+ * of graphs.  drop_*: training-mode dropout behind edge_mlp's first Linear, as in `egnn_edge_exact_args`. */
+typedef struct egnn_edge_hidden_args {
+    int32_t B, N, K, m_dim, H, S;
+    const int32_t* idx;         /* (B, N, K) or NULL = dense */
+    /* data pointers: float for the _f32 entries, double for the _f64 entries */
+    const void* Pi;             /* (B N, H) P_i incl. the first Linear's bias */
+    const void* Pj;             /* (B N, H) */
+    const void* s;              /* (E, S) per-edge scalars */
+    const void* Ws;             /* (H, S) */
+    const void* W2;             /* (m_dim, H) */
+    const void* b2;             /* (m_dim) forward */
+    const void* gU;             /* (E, m_dim) d loss / d u: both backward entries */
+    const void* cPi;            /* second order: the cotangents */
+    const void* cPj;
+    const void* cs;
+    const void* cWs;
+    const void* cW2;
+    const void* cb2;
+    void* u;                    /* out (E, m_dim): forward */
+    void* A_T;                  /* out (H, E): first order */
+    void* DZ_T;                 /* out (H, E): both backward entries */
+    void* g_s;                  /* out (E, S): both backward entries */
+    void* g_gU;                 /* out (E, m_dim): second order */
+    void* DAV_T;                /* out (H, E): second order */
+    void* R_T;                  /* out (H, E): second order */
+    uint32_t drop_thr, drop_seed;
+    float drop_inv_keep;
+    int64_t drop_eid0;
+} egnn_edge_hidden_args;
+int egnn_edge_hidden_fwd_f32(const egnn_edge_hidden_args* args, void* stream);
+int egnn_edge_hidden_fwd_f64(const egnn_edge_hidden_args* args, void* stream);
+int egnn_edge_hidden_bwd_f32(const egnn_edge_hidden_args* args, void* stream);
+int egnn_edge_hidden_bwd_f64(const egnn_edge_hidden_args* args, void* stream);
+int egnn_edge_hidden_bwd2_f32(const egnn_edge_hidden_args* args, void* stream);
+int egnn_edge_hidden_bwd2_f64(const egnn_edge_hidden_args* args, void* stream);
 
 /* =============================================================================================
  * The float64 path: a float64 module in float64 arithmetic.
