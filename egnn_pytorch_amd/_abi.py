@@ -16,7 +16,7 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int
 
 import torch  # noqa: F401  (must precede CDLL, see module docstring)
 
-ABI_VERSION = 41
+ABI_VERSION = 42
 _LIB_NAME = "libegnn_hip.so"
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 
@@ -38,6 +38,8 @@ SYMBOLS = (
     "egnn_node_mlp_fused_halves", "egnn_node_mlp_fused_pack_f16", "egnn_node_mlp_fused_f32",
     "egnn_edge_hidden_fwd_f32", "egnn_edge_hidden_fwd_f64", "egnn_edge_hidden_bwd_f32", "egnn_edge_hidden_bwd_f64",
     "egnn_edge_hidden_bwd2_f32", "egnn_edge_hidden_bwd2_f64",
+    "egnn_induced_attn_bwd_f32", "egnn_induced_attn_bwd_work_floats", "egnn_token_attn_bwd_chunks", "egnn_token_attn_bwd_f32", "egnn_gelu_bwd_f32",
+    "egnn_layer_norm_bwd_parts", "egnn_layer_norm_bwd_f32",
 )
 
 
@@ -351,6 +353,23 @@ def load():
     lib.egnn_token_attn_f32.restype = c_int
     lib.egnn_token_attn_f32.argtypes = [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int64,
                                         c_void_p]
+    lib.egnn_induced_attn_bwd_f32.restype = c_int
+    lib.egnn_induced_attn_bwd_f32.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                              c_float, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.egnn_induced_attn_bwd_work_floats.restype = c_int64
+    lib.egnn_induced_attn_bwd_work_floats.argtypes = [c_int, c_int, c_int, c_int, c_int]
+    lib.egnn_token_attn_bwd_chunks.restype = c_int
+    lib.egnn_token_attn_bwd_chunks.argtypes = [c_int]
+    lib.egnn_token_attn_bwd_f32.restype = c_int
+    lib.egnn_token_attn_bwd_f32.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_float,
+                                            c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.egnn_gelu_bwd_f32.restype = c_int
+    lib.egnn_gelu_bwd_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
+    lib.egnn_layer_norm_bwd_parts.restype = c_int
+    lib.egnn_layer_norm_bwd_parts.argtypes = [c_int64]
+    lib.egnn_layer_norm_bwd_f32.restype = c_int
+    lib.egnn_layer_norm_bwd_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                            c_void_p]
     lib.egnn_edge_features_gather_f32.restype = c_int
     lib.egnn_edge_features_gather_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                                   c_int, c_int, c_int, c_void_p, c_void_p]

@@ -763,6 +763,66 @@ def token_attn(q, kv_tok, b, n, heads, dim_head, scale):
     return out
 
 
+def induced_attn_bwd(q, kv, mask, o, g_o, b, n, heads, dim_head, scale):
+    """Backward of `induced_attn`: (d/d q (B,T,inner), d/d kv (B N, 2 inner)) from the forward's inputs, its output o and
+    g_o = d loss / d o -- egnn_induced_attn_bwd_f32 (the nodes in chunks: per-chunk softmax statistics and partial d/d q tables,
+    merged in chunk order)."""
+    t = q.shape[1]
+    inner = heads * dim_head
+    g_q = empty(b, t, inner, dtype=torch.float32, device=kv.device)
+    g_kv = empty(b * n, 2 * inner, dtype=torch.float32, device=kv.device)
+    lib = _abi.load()
+    work = empty(int(lib.egnn_induced_attn_bwd_work_floats(b, n, t, heads, dim_head)), dtype=torch.float32, device=kv.device)
+    with _timed("induced_attn_bwd"):
+        rc = lib.egnn_induced_attn_bwd_f32(_ptr(q.contiguous()), _ptr(kv), kv.stride(0), _ptr(_u8(mask)), _ptr(o.contiguous()),
+                                           _ptr(g_o.contiguous()), b, n, t, heads, dim_head, float(scale), _ptr(work), _ptr(g_q), _ptr(g_kv),
+                                           _stream())
+    _abi.check(rc, "egnn_induced_attn_bwd_f32")
+    return g_q, g_kv
+
+
+def token_attn_bwd(q, kv_tok, g_out, b, n, heads, dim_head, scale):
+    """Backward of `token_attn`: (d/d q (B N, inner), d/d kv_tok (B,T,2 inner)) -- egnn_token_attn_bwd_f32 (the sum over a graph's
+    nodes: per-chunk partial tables added up in chunk order)."""
+    t = kv_tok.shape[1]
+    inner = heads * dim_head
+    lib = _abi.load()
+    g_q = empty(b * n, inner, dtype=torch.float32, device=q.device)
+    g_kv = empty(b, t, 2 * inner, dtype=torch.float32, device=q.device)
+    parts = empty(int(lib.egnn_token_attn_bwd_chunks(n)), b * t * 2 * inner, dtype=torch.float32, device=q.device)
+    g_out = g_out if g_out.stride(-1) == 1 else g_out.contiguous()
+    with _timed("token_attn_bwd"):
+        rc = lib.egnn_token_attn_bwd_f32(_ptr(q), q.stride(0), _ptr(kv_tok.contiguous()), _ptr(g_out), g_out.stride(0), b, n, t, heads,
+                                         dim_head, float(scale), _ptr(g_q), _ptr(parts), _ptr(g_kv), _stream())
+    _abi.check(rc, "egnn_token_attn_bwd_f32")
+    return g_q, g_kv
+
+
+def gelu_bwd_(z, g):
+    """z <- GELU(z) (exact), g <- g * GELU'(z), in place, one pass (egnn_gelu_bwd_f32).  Returns (z, g, bits) as `silu_bwd_`."""
+    bits = torch.empty(2, dtype=torch.int32, device=z.device)
+    with _timed("gelu_bwd"):
+        rc = _abi.load().egnn_gelu_bwd_f32(_ptr(z), _ptr(g), _ptr(z), _ptr(g), z.numel(), _ptr(bits), _stream())
+    _abi.check(rc, "egnn_gelu_bwd_f32")
+    return z, g, bits
+
+
+def layer_norm_bwd(x2d, g2d, gamma, eps, add=None):
+    """Backward of LayerNorm over the rows of x2d (rows, dim <= 1024), statistics recomputed from x2d: (d/d x (+ add), d/d gamma,
+    d/d beta) -- egnn_layer_norm_bwd_f32 (column sums: one partial row per workgroup, added up in workgroup order)."""
+    rows, dim = x2d.shape
+    assert x2d.is_contiguous() and g2d.is_contiguous() and g2d.shape == x2d.shape and (add is None or (add.is_contiguous() and add.shape == x2d.shape))
+    lib = _abi.load()
+    g_x = empty(rows, dim, dtype=torch.float32, device=x2d.device)
+    g_gb = empty(2, dim, dtype=torch.float32, device=x2d.device)
+    parts = empty(int(lib.egnn_layer_norm_bwd_parts(rows)), 2 * dim, dtype=torch.float32, device=x2d.device)
+    with _timed("layer_norm_bwd"):
+        rc = lib.egnn_layer_norm_bwd_f32(_ptr(x2d), _ptr(g2d), _ptr(gamma), float(eps), _ptr(add), rows, dim, _ptr(g_x), _ptr(parts),
+                                         _ptr(g_gb), _stream())
+    _abi.check(rc, "egnn_layer_norm_bwd_f32")
+    return g_x, g_gb[0], g_gb[1]
+
+
 class HostRead:
     """A few words of device memory on their way to the host WITHOUT draining the stream: created right behind the kernel that writes
     them -- a copy to pinned memory and an event behind that copy -- and waited for (`tensor()` / `floats()` / `ints()`) only where the

@@ -776,8 +776,9 @@ class EGNN_Network(nn.Module):
     def forward(self, feats, coors, adj_mat=None, edges=None, mask=None, return_coor_changes=False):
         if _ops.RANGE_CHECK == "deferred" and coors.is_cuda:
             _ops.check_range(coors.device, wait=False)
-        # under autograd the embeddings / attention blocks are ordinary differentiable modules and every EGNN layer records
-        # its own autograd.Function; otherwise nothing is recorded
+        # under autograd the embeddings are ordinary differentiable modules, every EGNN layer records its own autograd.Function and
+        # every attention block its four (attention.py: the node-sized steps on the HIP kernels, the token-sized ones in ATen);
+        # otherwise nothing is recorded
         grad = torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters()) or
                                             any(torch.is_tensor(t) and t.is_floating_point() and t.requires_grad
                                                 for t in (feats, coors, edges)))

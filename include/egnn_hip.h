@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define EGNN_ABI_VERSION 41
+#define EGNN_ABI_VERSION 42
 
 enum {
     EGNN_OK = 0,
@@ -548,6 +548,32 @@ int egnn_induced_attn_f32(const float* q, const float* kv, int64_t ldkv, const u
                           int dim_head, float scale, float* out, void* stream);
 int egnn_token_attn_f32(const float* q, int64_t ldq, const float* kv_tok, int B, int N, int T, int heads, int dim_head,
                         float scale, float* out, int64_t ldo, void* stream);
+
+/* The block's backward (ABI 42; csrc/global_attn_bwd.hip).  fp32, same limits as the forward cores; no float atomics: every sum over
+ * nodes has a fixed order, two runs give the same bits.
+ *   egnn_induced_attn_bwd_f32: from q, kv, mask as the forward read them, the forward's out `o` (B,T,inner) and g_o = d loss / d out:
+ *       g_q (B,T,inner) and g_kv (B*N, 2*inner) contiguous, every row written once (k half in columns [0, inner), v half behind it).
+ *       The nodes are cut into chunks (one workgroup per graph, head and chunk); the softmax statistics are recomputed by a first kernel
+ *       over the k half, g_q is the sum of one partial table per chunk in chunk order; work: egnn_induced_attn_bwd_work_floats(...) floats.  A masked node's logit is a constant: its g_k is 0 and it
+ *       adds nothing to g_q; its g_v is p g_o with p = 0, or p = 1 / N in a graph whose mask is all False.
+ *   egnn_token_attn_bwd_f32: from q (B*N, ldq), kv_tok (B,T,2*inner), g_out (B*N, ldg) = d loss / d out: g_q (B*N, inner) contiguous and
+ *       g_kv_tok (B,T,2*inner) = the sum over each graph's nodes; parts: workspace of egnn_token_attn_bwd_chunks(N) * B*T*2*inner floats
+ *       (one partial table per chunk of nodes, added up in chunk order).
+ *   egnn_gelu_bwd_f32: a_out = GELU(z) (exact, erf), gz_out = g * (Phi(z) + z phi(z)); 16-byte aligned, any count; a_out may be z and
+ *       gz_out may be g; amax_bits as egnn_silu_bwd_f32.
+ *   egnn_layer_norm_bwd_f32: LayerNorm over rows of x (rows, dim), dim <= 1024, statistics recomputed from x:
+ *       g_x = (g gamma - mean(g gamma) - x_hat mean(g gamma x_hat)) / sigma (+ add, (rows, dim) or NULL);
+ *       g_gamma_beta (2, dim) = [sum_rows g x_hat, sum_rows g]; parts: workspace of egnn_layer_norm_bwd_parts(rows) * 2*dim floats. */
+int egnn_induced_attn_bwd_f32(const float* q, const float* kv, int64_t ldkv, const uint8_t* mask, const float* o, const float* g_o,
+                              int B, int N, int T, int heads, int dim_head, float scale, float* work, float* g_q, float* g_kv, void* stream);
+int64_t egnn_induced_attn_bwd_work_floats(int B, int N, int T, int heads, int dim_head);
+int egnn_token_attn_bwd_chunks(int N);
+int egnn_token_attn_bwd_f32(const float* q, int64_t ldq, const float* kv_tok, const float* g_out, int64_t ldg, int B, int N, int T,
+                            int heads, int dim_head, float scale, float* g_q, float* parts, float* g_kv_tok, void* stream);
+int egnn_gelu_bwd_f32(const float* z, const float* g, float* a_out, float* gz_out, int64_t count, uint32_t* amax_bits, void* stream);
+int egnn_layer_norm_bwd_parts(int64_t rows);
+int egnn_layer_norm_bwd_f32(const float* x, const float* g, const float* gamma, float eps, const float* add, int64_t rows, int dim,
+                            float* g_x, float* parts, float* g_gamma_beta, void* stream);
 
 /* =============================================================================================
  * Whole-layer interface: everything a binding that is NOT the shipped Python one needs to
