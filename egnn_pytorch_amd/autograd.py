@@ -832,22 +832,92 @@ class EGNNFunction(torch.autograd.Function):
             else:
                 with _ops.backward_status():        # range bits of these kernels go to the backward's status word
                     out = _backward_native(ctx, g_node, g_coors)
+                out = _w2_in_range_or_recomputed(ctx, g_node, g_coors, out)
         else:
             out = _backward_recompute(ctx, g_node, g_coors)
         return tuple(out[:7]) + (None,) + ctx.table_grads + tuple(out[7:])
 
 
+_W2_RANGE = 65504.0 / 64.0          # |SiLU(z)| that egnn_edge_bwd_pass_f32 carries for d/d W_2: fp16 x 2^6 (csrc/edge_bwd.hip: A_UP)
+backward_reruns = 0                 # native backwards answered by `_backward_recompute` in this process (tests pin where that happens)
+_warned_backward_rerun = False
+
+
+def _silu_hidden_amax(ctx):
+    """max |SiLU(z)| over the pairs as egnn_edge_bwd_pass_f32 evaluates them for d/d W_2 (z = W_i h_i + b + W_j h_j + W_s s; the scalars of
+    pairs the masks remove read as 0; training-mode dropout: every unit taken as kept), one graph at a time.  Only called once a native
+    backward has returned a non-finite d/d W_2."""
+    layer = _f32_shadow(ctx.layer)
+    feats, coors, edges, mask, idx32, rank = _unpack(ctx)
+    feats, coors = feats.float(), coors.float()
+    dim = feats.shape[-1]
+    lin = layer.edge_mlp[0]
+    w = lin.weight.detach()
+    by_k = getattr(ctx, "edges_by_k", False)
+    drop = getattr(ctx, "drop", None)
+    amax = 0.0
+    with torch.no_grad():
+        for g in range(feats.shape[0]):
+            i64 = None if idx32 is None else idx32[g:g + 1].long()
+            e0 = None if edges is None else edges[g:g + 1].float()
+            _, scal = edge_scalars(layer, coors[g:g + 1], e0, i64, by_k)
+            pm = _pair_mask(None if mask is None else mask[g:g + 1], i64, None if rank is None else rank[g:g + 1], ctx.valid_radius)
+            if pm is not None:
+                scal = scal.masked_fill(~pm[..., None], 0.0)
+            p_i = feats[g] @ w[:, :dim].t() + lin.bias.detach()
+            p_j = feats[g] @ w[:, dim:2 * dim].t()
+            z = p_i[:, None, :] + (p_j[None, :, :] if i64 is None else p_j[i64[0]]) + scal[0] @ w[:, 2 * dim:].t()
+            if drop is not None:
+                z = z / (1.0 - drop[0])
+            amax = max(amax, float(torch.nn.functional.silu(z).abs().max()))
+    return amax
+
+
+def _w2_in_range_or_recomputed(ctx, g_node, g_coors, out):
+    """The native backward's result -- or the same backward on `_backward_recompute` when d/d W_2 left the range of its kernel.
+    egnn_edge_bwd_pass_f32 carries SiLU(z) as fp16 x 2^6 for d/d W_2 (up to 1023) where the forward carries it up to 65504: a layer whose
+    forward is in range (a dense layer on 64 collinear nodes at unit spacing with xavier-scale weights: |x_i - x_j|^2 up to 3969,
+    SiLU(z) ~ 1200) left an inf - inf there.  The trigger is exactly that: d/d W_2 non-finite (one word per chunk of graphs, read behind
+    the pass like the max-|x| words: `_ops.HostRead`, no drained stream), finite incoming gradients, AND max |SiLU(z)| -- evaluated
+    then -- beyond the range.  Any other non-finite value is returned as it is.  Like the forward's wide-range re-run: plain fp32
+    arithmetic over the same neighbour list, several times slower, one warning per process, under the range word's rule
+    (EGNN_RANGE_CHECK=sync, no stream capture); `backward_reruns` counts."""
+    global _warned_backward_rerun, backward_reruns
+    from . import _ops
+    flags = getattr(ctx, "w2_finite", None)
+    ctx.w2_finite = None
+    if not flags or _ops.RANGE_CHECK != "sync" or torch.cuda.is_current_stream_capturing():
+        return out
+    if all(f.ints()[0] for f in flags):
+        return out
+    if any(g is not None and not bool(torch.isfinite(g).all()) for g in (g_node, g_coors)):
+        return out                                    # (non-finite gradients came in: non-finite gradients go out, as in any autograd)
+    if not _silu_hidden_amax(ctx) >= _W2_RANGE:
+        return out                                    # (in range: not this limit's doing -- it surfaces)
+    if not _warned_backward_rerun:
+        _warned_backward_rerun = True
+        import warnings
+        warnings.warn("egnn_pytorch_amd: a backward left the range of the split-fp16 kernels (SiLU of edge_mlp's hidden layer beyond 1023) "
+                      "and is being re-run in plain fp32 (several times slower; this warning is issued once).", RuntimeWarning, stacklevel=2)
+    backward_reruns += 1
+    ctx.table_grads = (None, None)
+    return _backward_recompute(ctx, g_node, g_coors)
+
+
+def _pair_mask(m0, i64, r0, valid_radius):
+    """(B,N,K) bool: the pairs that pass the node masks and the radius (egnn_pytorch.py:292-300); None without a mask."""
+    if m0 is None:
+        return None
+    if i64 is None:
+        return m0[:, :, None] & m0[:, None, :]
+    bi = torch.arange(m0.shape[0], device=m0.device)[:, None, None]
+    return m0[:, :, None] & m0[bi, i64] & (r0 <= valid_radius)
+
+
 def _pooled_messages(layer, u, m0, i64, r0, valid_radius):
     """(m_i, pair mask (B,N,K) bool or None, count or None) from u (B,N,K,m): egnn_pytorch.py:287-300, 319-333 on E x m tensors."""
-    b = u.shape[0]
     k = u.shape[2]
-    pm = None
-    if m0 is not None:
-        if i64 is None:
-            pm = m0[:, :, None] & m0[:, None, :]
-        else:
-            bi = torch.arange(b, device=u.device)[:, None, None]
-            pm = m0[:, :, None] & m0[bi, i64] & (r0 <= valid_radius)
+    pm = _pair_mask(m0, i64, r0, valid_radius)
     mm = torch.nn.functional.silu(u)
     if layer.edge_gate is not None:
         gl = layer.edge_gate[0]
@@ -1370,6 +1440,7 @@ def _backward_native(ctx, g_node, g_coors):
     # hidden width <= 64); otherwise that part goes through autograd as well
     tail_kernel = (_TAIL_KERNEL and layer.coors_mlp is not None and layer.node_mlp is not None
                    and m <= 16 and layer.coors_mlp[0].weight.shape[0] <= 64 and coors.shape[-1] == 3)
+    w2_finite = ctx.w2_finite = []
     for lo in range(0, b, step):
         hi_ = min(b, lo + step)
         bc = hi_ - lo
@@ -1381,6 +1452,7 @@ def _backward_native(ctx, g_node, g_coors):
         r0 = None if rank is None else rank[lo:hi_]
         ec = bc * n * k
         dest_lists = None
+        pm = None                                            # (bc, n, k) bool: the pairs that pass the masks (None: all of them)
         hr_f = _ops.absmax_async(f0.view(bc * n, dim)) if (f0.is_cuda and _GRAD_GEMM) else None      # (read in step 3)
 
         def early():
@@ -1398,13 +1470,7 @@ def _backward_native(ctx, g_node, g_coors):
             # egnn_edge_tail_bwd_f32 -- `tail_edge_backward` is its specification
             with torch.no_grad():
                 u16 = u_all[lo:hi_].contiguous()
-                pm = None
-                if m0 is not None:
-                    if i64 is None:
-                        pm = m0[:, :, None] & m0[:, None, :]
-                    else:
-                        bi = torch.arange(bc, device=feats.device)[:, None, None]
-                        pm = m0[:, :, None] & m0[bi, i64] & (r0 <= ctx.valid_radius)
+                pm = _pair_mask(m0, i64, r0, ctx.valid_radius)
                 reduce = f0.is_cuda and _TAIL_REDUCE       # (the kernels pool the messages and sum the parameter gradients' terms themselves)
                 pm8 = None if pm is None else pm.contiguous().view(torch.uint8)
                 gate, mm_pre, mm = None, None, None
@@ -1552,6 +1618,7 @@ def _backward_native(ctx, g_node, g_coors):
                 e = None if e0 is None else e0.detach().requires_grad_(want_ge)
                 u = u_all[lo:hi_, :, :, :m].detach().requires_grad_(True)
                 rel, scal = edge_scalars(layer, c, e, i64, by_k)
+                pm = _pair_mask(m0, i64, r0, ctx.valid_radius)
                 out_n, out_c = layer_tail(layer, f, c, u, rel, m0, i64, r0, ctx.valid_radius)
                 outs, gouts = [], []
                 for o, g in ((out_n, g_node[lo:hi_]), (out_c, g_coors[lo:hi_])):
@@ -1577,7 +1644,14 @@ def _backward_native(ctx, g_node, g_coors):
         gu_scale = _weights.pow2_scale(amax) if amax > 0 else 1.0
         with torch.no_grad():
             f2d = f0.view(bc * n, dim)
-            sc2 = scal.detach().reshape(ec, s_in).contiguous()
+            sc2 = scal.detach().reshape(ec, s_in)
+            if pm is not None:
+                # Pairs the masks remove carry gU = 0, so whatever z they have they add exact zeros -- as long as SiLU(z) is finite where
+                # the pass holds it: as fp16 x 2^6 for d/d W_2, i.e. up to 1023.  A padded node's neighbours are the first K nodes wherever
+                # they are, so its |x_i - x_j|^2 (and with it z) is not bounded by the real pairs': 0 x inf was a NaN in d/d W_2.  Their
+                # scalars are read as 0 instead.
+                sc2 = sc2.masked_fill(~pm.reshape(ec, 1), 0.0)
+            sc2 = sc2.contiguous()
             contract = _edge_contract_fused
             proj = None if proj_all is None else proj_all[lo * n:hi_ * n]
             if drop is not None and mp == 16:
@@ -1610,6 +1684,8 @@ def _backward_native(ctx, g_node, g_coors):
             # ---- 3. node-level products: d/d feats = dP_i W_i + dP_j W_j, d/d W_i = dP_i^T feats, d/d W_j = dP_j^T feats.  On the
             # device: the forward's split-f16 matrix-core GEMM (operands pre-scaled by powers of two, the weight gradients split-K
             # over the B N nodes with the parts summed in fixed order) -- the fp32 library GEMMs they replace ran at 60 - 130 TFLOP/s
+            if g_w2.is_cuda:                                        # (read by `_w2_in_range_or_recomputed`, behind everything below)
+                w2_finite.append(_ops.HostRead(torch.isfinite(g_w2).all().to(torch.int32).view(1)))
             gw1 = grads_by_id[id(lin0.weight)]
             if f2d.is_cuda and _GRAD_GEMM:
                 # (each matrix: one absmax, one read for its plain and transposed images; feats^T split once for both weight gradients)
