@@ -135,6 +135,18 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def aligned(t):
+    """`t` as the kernels take a caller's tensor: contiguous and at a 16-byte boundary (they load four floats at a time, and several
+    entries return EGNN_E_ALIGN otherwise).  `t` itself when it is that already -- two integer tests on the host, no launch -- else a
+    fresh contiguous copy: `.contiguous()` is not enough, it returns a contiguous view at a 4- or 8-byte offset (a `narrow` of a
+    buffer) as it is.  The boundary of the module for every layout a pipeline produces -- sliced, transposed, expanded, offset views
+    -- applied where a caller's memory enters: the forward entries of layer.py / attention.py, the cotangents at the top of every
+    autograd.Function's backward, `absmax_async`.  Under autograd the copy is a differentiable clone.  None passes through."""
+    if t is None or (t.is_contiguous() and t.data_ptr() % 16 == 0):
+        return t
+    return t.clone(memory_format=torch.contiguous_format)
+
+
 def _u8(t):
     """bool tensor -> same storage viewed as bytes."""
     if t is None:
@@ -960,7 +972,7 @@ def absmax_async(x):
     """`absmax` whose host read can wait: the launch now, a HostRead of the bit pattern (`.floats()[0]` = max |x|)."""
     if not x.is_cuda:
         return HostRead(x.abs().max().reshape(1).float())
-    x = x if x.is_contiguous() else x.contiguous()
+    x = aligned(x)                                   # (a chunk of graphs sliced out of a saved tensor starts wherever the chunk does)
     out = torch.empty(1, dtype=torch.int32, device=x.device)
     with _timed("absmax"):
         rc = _abi.load().egnn_absmax_f32(_ptr(x), x.numel(), _ptr(out), _stream())
@@ -1343,9 +1355,9 @@ def forward_c(layer, feats, coors, edges=None, mask=None, adj_mat=None, packed=N
         packed = (desc, info, blob.to(feats.device))
     desc, info, blob_dev = packed
     b, n, _ = feats.shape
-    feats, coors = feats.contiguous(), coors.contiguous()
+    feats, coors = aligned(feats), aligned(coors)
     if edges is not None:
-        edges = edges.contiguous().float()
+        edges = aligned(edges.float())
     m8, a8 = _u8(mask), _u8(adj_mat)
     stride = n * n if (a8 is not None and a8.dim() == 3) else 0
     k = layer.num_nearest_neighbors

@@ -69,6 +69,8 @@ class GlobalLinearAttention(nn.Module):
         if x.is_cuda and x.dtype == torch.float32 and queries.dtype == torch.float32 \
                 and queries.shape[1] <= 8 and self.attn1.to_q.weight.shape[0] // self.attn1.heads <= 256 \
                 and not _layer.exact_active():                    # (plain-fp32 mode: the differentiable module below, in fp32)
+            from . import _ops
+            x = _ops.aligned(x)                                   # (any layout of the caller's; under autograd a differentiable clone)
             if not (torch.is_grad_enabled() and (x.requires_grad or queries.requires_grad or
                                                  any(p.requires_grad for p in self.parameters()))):
                 return self._forward_hip(x, queries, mask)
@@ -235,6 +237,7 @@ class _SeqProj(torch.autograd.Function):
         from . import _ops
         x, gamma, beta, w_kv, w_q = ctx.saved_tensors
         blk = ctx.blk
+        g_kv, g_q2 = _ops.aligned(g_kv), _ops.aligned(g_q2)
         if torch.is_grad_enabled():
             def expr(x, gamma, beta, w_kv, w_q):
                 seq = torch.nn.functional.layer_norm(x, x.shape[-1:], gamma, beta, blk.norm_seq.eps).view(-1, x.shape[-1])
@@ -278,6 +281,7 @@ class _InducedCore(torch.autograd.Function):
         from . import _ops
         q, kv, o = ctx.saved_tensors
         b, n, heads, dh = ctx.dims
+        g_o = _ops.aligned(g_o)
         if torch.is_grad_enabled():
             return _twice(lambda q, kv: attn_core_torch(q, kv.view(b, n, -1), ctx.mask, heads, ctx.scale), (q, kv), (g_o,)) + (None,) * 3
         g_q, g_kv = _ops.induced_attn_bwd(q, kv, ctx.mask, o, g_o, b, n, heads, dh, ctx.scale)
@@ -300,6 +304,7 @@ class _TokenCore(torch.autograd.Function):
         from . import _ops
         q, kv_tok = ctx.saved_tensors
         b, n, heads, dh = ctx.dims
+        g_att = _ops.aligned(g_att)
         if torch.is_grad_enabled():
             return _twice(lambda q, kv_tok: attn_core_torch(q.view(b, n, -1), kv_tok, None, heads, ctx.scale).view(b * n, -1),
                           (q, kv_tok), (g_att,)) + (None,) * 2
@@ -333,6 +338,7 @@ class _OutFF(torch.autograd.Function):
         att, x, w_o, b_o, gamma, beta, w1, b1, w2, b2 = inputs
         blk = ctx.blk
         b, n, dim = x.shape
+        g_x2 = _ops.aligned(g_x2)
         if torch.is_grad_enabled():
             def expr(att, x, w_o, b_o, gamma, beta, w1, b1, w2, b2):
                 F = torch.nn.functional

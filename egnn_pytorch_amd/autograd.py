@@ -629,6 +629,20 @@ class _ThirdOrderGuard(torch.autograd.Function):
                            "autograd.EdgeHidden) is not supported; second-order products (torch.autograd.functional.hvp / vhp / hessian) are")
 
 
+class _AlignedCotangent(torch.autograd.Function):
+    """Identity on a gradient that `_backward_twice` returns; the cotangent a second backward sends into it enters the recorded graph
+    contiguous and at a 16-byte boundary, in whatever layout it arrives (the second backward's share of `_ops.aligned`)."""
+
+    @staticmethod
+    def forward(ctx, t):
+        return t.view_as(t)
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import _ops
+        return _ops.aligned(g)
+
+
 def _edge_hidden_block(layer, feats, scal, idx, drop, graph_offset):
     """u (B,N,K,m) of `layer_given_neighbors` through `EdgeHidden`: the node tables P_i, P_j and the per-edge scalars in ATen, the
     E x H work in the op"""
@@ -823,10 +837,14 @@ class EGNNFunction(torch.autograd.Function):
                                    "operation: a parameter of egnn_pytorch_amd.EGNN changed between forward and backward "
                                    f"(version {p._version}, expected {v})")
         ctx.table_inputs, ctx.table_grads = True, (None, None)
+        # the cotangents in any layout -- the stride-0 one of `.sum()`, a view into the gradient of a torch.cat, a transposed one -- as
+        # the kernels (and, bit for bit, ATen's reductions on the recompute paths) take them: contiguous, at a 16-byte boundary
+        from . import _ops
+        g_node, g_coors = _ops.aligned(g_node), _ops.aligned(g_coors)
         if torch.is_grad_enabled():                 # create_graph=True (also hvp / hessian): gradients that are functions themselves
-            out = _backward_twice(ctx, g_node, g_coors)
+            out = tuple(None if g is None else _AlignedCotangent.apply(g) for g in _backward_twice(ctx, g_node, g_coors))
+            ctx.table_grads = tuple(None if g is None else _AlignedCotangent.apply(g) for g in ctx.table_grads)
         elif ctx.has_u:
-            from . import _ops
             if getattr(ctx, "exact_native", False):
                 out = _backward_exact(ctx, g_node, g_coors)
             else:
@@ -1188,9 +1206,13 @@ def _unused_params(layer, ctx=None):
 
 
 def _unpack(ctx):
+    """(feats, coors, edges, mask, idx, rank) as saved by the forward; the caller's own tensors among them -- saved as they came, so
+    that a backward under create_graph=True reaches them -- contiguous and at a 16-byte boundary (`_ops.aligned`: under create_graph
+    a differentiable clone), whatever their layout."""
+    from . import _ops
     feats, coors, edges, mask, idx, rank = ctx.saved_tensors[:6]
     has_mask, has_idx = ctx.flags
-    return (feats, coors, edges if ctx.has_edges else None, mask if has_mask else None,
+    return (_ops.aligned(feats), _ops.aligned(coors), _ops.aligned(edges) if ctx.has_edges else None, mask if has_mask else None,
             idx if has_idx else None, rank if has_idx else None)
 
 

@@ -332,6 +332,11 @@ extern "C" int egnn_layer_forward_opts_f32(const egnn_layer_desc* desc, const eg
     const Workspace w = carve(desc, x, B, N, K);
     if (workspace_bytes < w.bytes) return EGNN_E_SHAPE;
     if (reinterpret_cast<uintptr_t>(workspace) & 255) return EGNN_E_ALIGN;
+    // egnn_node_mlp_fused_f32 -- the last launch of a layer it serves -- takes feats (its residual) and feats_out at 16-byte boundaries:
+    // said HERE, before anything is enqueued, not by that entry once the selection and the edge pass are on the stream
+    if (desc->update_feats && egnn_node_mlp_fused_halves(x.dim, x.m) > 0 &&
+        ((reinterpret_cast<uintptr_t>(feats) | reinterpret_cast<uintptr_t>(feats_out)) & 15))
+        return EGNN_E_ALIGN;
     hipStream_t s = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
     const char* blob = static_cast<const char*>(blob_dev);

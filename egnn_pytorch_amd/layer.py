@@ -98,7 +98,7 @@ class EdgeLookup:
 
     def __init__(self, edges=None, tok=None, tok_emb=None, deg=None, deg_emb=None):
         self.live = (edges, tok_emb if tok is not None else None, deg_emb if deg is not None else None)
-        self.edges = None if edges is None else edges.detach().contiguous().float()
+        self.edges = None if edges is None else _ops.aligned(edges.detach().float())
         self.tok = None if tok is None else tok.contiguous().long()
         self.tok_emb = None if tok_emb is None else tok_emb.detach().contiguous().float()
         self.deg = None if deg is None else deg.contiguous()
@@ -448,9 +448,9 @@ class EGNN(nn.Module):
         kr = k, valid_radius = self._neighbour_count(n, adj_mat)
         if k == 0:                                                  # (no messages: not covered by the C entry)
             return self._forward_hip(feats, coors, edges, mask, adj_mat, order_hint, kr=kr)
-        feats, coors = feats.contiguous(), coors.contiguous()
+        feats, coors = _ops.aligned(feats), _ops.aligned(coors)     # (any layout of the caller's: `_ops.aligned`)
         if edges is not None:
-            edges = edges.contiguous().float()
+            edges = _ops.aligned(edges.float())
         m8, a8 = _ops._u8(mask), _ops._u8(adj_mat)
         stride = n * n if (a8 is not None and a8.dim() == 3) else 0
         lib = _abi.load()
@@ -500,8 +500,8 @@ class EGNN(nn.Module):
         b, n, dim = feats.shape
         k, valid_radius = kr
         w = self.packed_weights()
-        feats = feats.contiguous()
-        coors = coors.contiguous()
+        feats = _ops.aligned(feats)                                 # (any layout of the caller's: contiguous, at a 16-byte boundary)
+        coors = _ops.aligned(coors)
         # What the neighbour selection reads on the side stream -- coors, mask, adj_mat -- is made contiguous HERE, before the fork event
         # below, and every `_u8` of it is a view from then on: a copy enqueued behind that event (a sliced or expanded mask) would be a
         # kernel the side stream does not wait for, and the selection could read its output before it is written.
@@ -513,7 +513,7 @@ class EGNN(nn.Module):
         if lookup is not None:
             edges = lookup.edges
         elif edges is not None:
-            edges = edges.contiguous().float()
+            edges = _ops.aligned(edges.float())
 
         # ---- neighbour selection (egnn_pytorch.py:230-260)
         use_nearest = self._use_nearest()
@@ -631,14 +631,14 @@ class EGNN(nn.Module):
         egnn_drop_silu_*)."""
         esz = 8 if dtype == torch.float64 else 4
         b, n, dim = feats.shape
-        feats = feats.contiguous()
-        coors = coors.contiguous()
+        feats = _ops.aligned(feats)
+        coors = _ops.aligned(coors)
         feats2d = feats.view(b * n, dim)
         lookup = edges if isinstance(edges, EdgeLookup) else None
         if lookup is not None:
             edges = lookup.edges
         elif edges is not None:
-            edges = edges.contiguous().to(dtype)
+            edges = _ops.aligned(edges.to(dtype))
         mask8 = _ops._u8(mask)
         k, valid_radius = kr
         idx = rank = None

@@ -642,6 +642,10 @@ size_t egnn_workspace_bytes(const egnn_layer_desc* desc, int B, int N, int K);
  *      pass the largest adjacency row sum (egnn_adj_max_degree_u8; that device read is the host sync the reference has
  *      too, :249) -- workspace_bytes must be >= egnn_workspace_bytes(desc, B, N, K);
  *   status: optional range status word (EGNN_RANGE_*).
+ * Alignment: the workspace at a 256-byte boundary; feats and feats_out at 16-byte boundaries for the layers whose node_mlp is one
+ * launch (update_feats with egnn_node_mlp_fused_halves(dim, m_dim) > 0: m_dim = 16, dim 32 / 64 / 128 / 256) -- any allocation's
+ * start is, a view 4 or 8 bytes into one is not.  Both are checked before the first launch: EGNN_E_ALIGN, nothing enqueued, the
+ * outputs untouched.  Every other tensor may sit at any element boundary.
  * Returns EGNN_E_K_GT_N when K > N (the reference's topk error). */
 int egnn_layer_forward_f32(const egnn_layer_desc* desc, const egnn_packed_info* info, const void* blob_dev,
                            const float* feats, const float* coors, const float* edges, const uint8_t* mask,

@@ -121,6 +121,62 @@ def test_c_layer_forward_matches_module(kw, n, flags):
     assert torch.equal(mod[0], want[0]) and torch.equal(mod[1], want[1])
 
 
+@pytest.mark.parametrize("which", ["feats", "feats_out"])
+@pytest.mark.parametrize("offset", [1, 2])
+def test_c_layer_forward_rejects_misaligned_feats_before_the_first_launch(which, offset):
+    """egnn_layer_forward_f32 on a layer the fused node_mlp kernel serves (m_dim 16, dim 32), with feats -- or feats_out -- 4 / 8 bytes
+    past a 16-byte boundary: EGNN_E_ALIGN, and nothing was enqueued -- the output buffers, filled with a sentinel, are untouched after
+    a synchronisation (the kernel's own check would speak only after the selection and the edge pass, which writes coors_out, had been
+    queued).  The same buffers at the boundary: the module's outputs, bit for bit."""
+    from ctypes import byref
+    from egnn_pytorch_amd import EGNN, _abi, _ops
+    torch.manual_seed(3)
+    layer = EGNN(dim=32, num_nearest_neighbors=8).cuda().eval()
+    with torch.no_grad():
+        for p in layer.parameters():
+            p.mul_(100.0)
+    g = torch.Generator().manual_seed(1)
+    b, n, k, dim = 2, 40, 8, 32
+    feats, coors = torch.randn(b, n, dim, generator=g).cuda(), torch.randn(b, n, 3, generator=g).cuda()
+    desc, info, blob = _ops.pack_weights_c(layer)
+    blob = blob.cuda()
+    lib = _abi.load()
+    nbytes = lib.egnn_workspace_bytes(byref(desc), b, n, k)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    sentinel = -7.25
+
+    def at(t, off):
+        buf = torch.full((t.numel() + 4,), sentinel, device="cuda")
+        assert buf.data_ptr() % 16 == 0
+        view = buf[off:off + t.numel()].view(t.shape)
+        return buf, view
+
+    def call(f_in, f_out, c_out):
+        return lib.egnn_layer_forward_f32(byref(desc), byref(info), blob.data_ptr(), f_in.data_ptr(), coors.data_ptr(), None, None, None, 0,
+                                          b, n, k, 3, f_out.data_ptr(), c_out.data_ptr(), ws.data_ptr(), nbytes,
+                                          _ops._status_ptr(feats.device), _ops._stream())
+
+    _, f_in = at(feats, offset if which == "feats" else 0)
+    f_in.copy_(feats)
+    out_buf, f_out = at(feats, offset if which == "feats_out" else 0)
+    c_buf, c_out = at(coors, 0)
+    assert (f_in if which == "feats" else f_out).data_ptr() % 16 == 4 * offset and f_in.is_contiguous() and f_out.is_contiguous()
+    rc = call(f_in, f_out, c_out)
+    torch.cuda.synchronize()
+    assert rc == -4, rc                                              # EGNN_E_ALIGN (include/egnn_hip.h)
+    assert bool((out_buf == sentinel).all()) and bool((c_buf == sentinel).all())
+    # the control: the same call with both at the boundary
+    _, f_ok = at(feats, 0)
+    f_ok.copy_(feats)
+    out_buf, f_out = at(feats, 0)
+    assert call(f_ok, f_out, c_out) == 0
+    torch.cuda.synchronize()
+    with torch.no_grad():
+        want = layer(feats, coors)
+    assert torch.equal(f_out, want[0]) and torch.equal(c_out, want[1])
+    assert bool((out_buf[feats.numel():] == sentinel).all()) and bool((c_buf[coors.numel():] == sentinel).all())
+
+
 def test_one_call_forward_in_a_network_reuses_the_first_layers_order():
     """EGNN_Network on the one-call path: layer 0 writes the Morton order into a buffer of the caller, the next layers read it as a hint
     (egnn_forward_opts.order / order_is_hint) -- same outputs, bit for bit, as the Python launch sequence (EGNN_C_FORWARD=0)."""

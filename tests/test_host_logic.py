@@ -357,6 +357,38 @@ def test_host_read_and_lazy_destination_lists_on_the_cpu():
     assert _ops.DestLists(ent[:256], None, None, None).ent.numel() == 256
 
 
+def test_aligned_returns_the_tensor_itself_or_an_aligned_contiguous_copy():
+    """_ops.aligned, the boundary for the callers' memory layouts: identity -- the same object, no copy -- for a contiguous tensor at a
+    16-byte boundary; for a contiguous view 4 bytes into a buffer (which `.contiguous()` returns as it is), a slice of a wider tensor
+    and a stride-0 expansion a copy with the same values, contiguous, at a 16-byte boundary, that leaves the source alone."""
+    from egnn_pytorch_amd import _ops
+    g = torch.Generator().manual_seed(0)
+    base = torch.randn(3, 10, 8, generator=g)
+    assert base.data_ptr() % 16 == 0 and _ops.aligned(base) is base and _ops.aligned(None) is None
+    view16 = torch.randn(4 + base.numel(), generator=g)[4:].view(base.shape)        # an offset view at a 16-byte boundary: itself
+    assert view16.data_ptr() % 16 == 0 and _ops.aligned(view16) is view16
+    buf = torch.zeros(base.numel() + 1)
+    off4 = buf[1:].view(base.shape).copy_(base)
+    sliced_last = torch.randn(3, 10, 4, generator=g)[..., :3]
+    expanded = torch.randn(1, 10, 8, generator=g).expand(3, 10, 8)
+    scalar = torch.ones(()).expand(3, 10, 8)
+    flags = torch.zeros(31, dtype=torch.bool)[1:].view(3, 10)                       # one-byte elements at an odd address
+    assert off4.is_contiguous() and off4.data_ptr() % 16 == 4 and off4.contiguous() is off4
+    assert not sliced_last.is_contiguous() and not expanded.is_contiguous() and not scalar.is_contiguous() and flags.data_ptr() % 2 == 1
+    for t in (off4, sliced_last, expanded, scalar, flags):
+        before = t.clone()
+        out = _ops.aligned(t)
+        assert out is not t and out.is_contiguous() and out.data_ptr() % 16 == 0 and out.stride() == before.contiguous().stride()
+        assert out.dtype == t.dtype and torch.equal(out, before) and torch.equal(t, before)
+        assert out.untyped_storage().data_ptr() != t.untyped_storage().data_ptr()
+        assert _ops.aligned(out) is out
+    leaf = off4.clone().requires_grad_(True)                                        # under autograd: a differentiable copy
+    view = leaf[..., :5]
+    out = _ops.aligned(view)
+    out.sum().backward()
+    assert torch.equal(leaf.grad[..., :5], torch.ones(3, 10, 5)) and torch.equal(leaf.grad[..., 5:], torch.zeros(3, 10, 3))
+
+
 def test_copies_and_pickles_of_a_module_leave_the_kernel_side_caches_behind():
     """copy.deepcopy / pickle / torch.save of an EGNN carry the reference's state only: the re-laid-out weights, the C entry's blob and
     the cached parameter list (device tensors, ctypes structs, references to the ORIGINAL's Parameter objects) are rebuilt by the copy."""
