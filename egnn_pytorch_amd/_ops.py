@@ -704,52 +704,66 @@ def edge_fused(args: _abi.EdgeArgs, device):
     _abi.check(rc, "egnn_edge_fused_f32")
 
 
+def _lookup_dtype(lookup, what):
+    """The one dtype of an EdgeLookup's detached tables (float32 or float64): which of the _f32 / _f64 entries reads them."""
+    dts = {t.dtype for t in (lookup.edges, lookup.tok_emb, lookup.deg_emb) if t is not None}
+    if len(dts) != 1 or not dts <= {torch.float32, torch.float64}:
+        raise TypeError(f"{what}: the look-up tables must all be float32 or all float64 (got {sorted(str(d) for d in dts)})")
+    return dts.pop()
+
+
 def edge_features_gather(lookup, idx, b, n, k):
-    """(B,N,K,edge_dim) features of the selected pairs from EGNN_Network's look-up tables -- egnn_edge_features_gather_f32."""
+    """(B,N,K,edge_dim) features of the selected pairs from EGNN_Network's look-up tables, in the tables' dtype --
+    egnn_edge_features_gather_f32 / _f64."""
     dev = (lookup.deg if lookup.deg is not None else (lookup.tok if lookup.tok is not None else lookup.edges)).device
-    out = empty(b, n, k, lookup.width, dtype=torch.float32, device=dev)
+    dtype = _lookup_dtype(lookup, "edge_features_gather")
+    name = "egnn_edge_features_gather_f64" if dtype == torch.float64 else "egnn_edge_features_gather_f32"
+    out = empty(b, n, k, lookup.width, dtype=dtype, device=dev)
     with _timed("edge_features"):
-        rc = _abi.load().egnn_edge_features_gather_f32(_ptr(lookup.edges), _ptr(lookup.tok), _ptr(lookup.tok_emb), lookup.d1,
-                                                       _ptr(lookup.deg), _ptr(lookup.deg_emb), lookup.d2, _ptr(idx), b, n, k,
-                                                       _ptr(out), _stream())
-    _abi.check(rc, "egnn_edge_features_gather_f32")
+        rc = getattr(_abi.load(), name)(_ptr(lookup.edges), _ptr(lookup.tok), _ptr(lookup.tok_emb), lookup.d1,
+                                        _ptr(lookup.deg), _ptr(lookup.deg_emb), lookup.d2, _ptr(idx), b, n, k,
+                                        _ptr(out), _stream())
+    _abi.check(rc, name)
     return out
 
 
 def edge_features_grad(lookup, idx, b, n, k, g, want_tok=True, want_deg=True, g_edges=None):
-    """The transpose of `edge_features_gather` -- egnn_edge_features_grad_f32: g (B N K, >= edge_dim) fp32 rows whose first
-    lookup.width columns are d loss / d the gathered features (row stride g.stride(0)) -> (g_tok_emb (V1, d1) or None,
-    g_deg_emb (V2, d2) or None), sums in a fixed order.  g_edges: a zeroed (B,N,N,d1) fp32 tensor for dense float edges, which
-    receives its rows in place.  lookup's label tensors are read for graphs [0, b): pass a lookup sliced to the graphs of g."""
+    """The transpose of `edge_features_gather` -- egnn_edge_features_grad_f32 / _f64: g (B N K, >= edge_dim) rows in the tables' dtype
+    whose first lookup.width columns are d loss / d the gathered features (row stride g.stride(0)) -> (g_tok_emb (V1, d1) or None,
+    g_deg_emb (V2, d2) or None) in that dtype, sums in a fixed order.  g_edges: a zeroed (B,N,N,d1) tensor of that dtype for dense
+    float edges, which receives its rows in place.  lookup's label tensors are read for graphs [0, b): pass a lookup sliced to the
+    graphs of g."""
     dev = g.device
     if g.dim() != 2 or g.stride(1) != 1 or g.shape[0] != b * n * k or g.shape[1] < lookup.width:
         raise ValueError(f"edge_features_grad: g {tuple(g.shape)} / strides {g.stride()} for {b * n * k} edges of width {lookup.width}")
-    if g.dtype != torch.float32:
-        raise TypeError("edge_features_grad: g must be float32")
+    dtype = _lookup_dtype(lookup, "edge_features_grad")
+    if g.dtype != dtype:
+        raise TypeError(f"edge_features_grad: g must be float32 or float64, matching the tables (g is {g.dtype}, the tables {dtype})")
+    name = "egnn_edge_features_grad_f64" if dtype == torch.float64 else "egnn_edge_features_grad_f32"
     on1 = want_tok and lookup.tok is not None
     on2 = want_deg and lookup.deg is not None
     v1 = lookup.tok_emb.shape[0] if on1 else 0
     v2 = lookup.deg_emb.shape[0] if on2 else 0
-    g_tok = empty(v1, lookup.d1, dtype=torch.float32, device=dev) if on1 else None
-    g_deg = empty(v2, lookup.d2, dtype=torch.float32, device=dev) if on2 else None
-    if g_edges is not None and (g_edges.dtype != torch.float32 or not g_edges.is_contiguous()
+    g_tok = empty(v1, lookup.d1, dtype=dtype, device=dev) if on1 else None
+    g_deg = empty(v2, lookup.d2, dtype=dtype, device=dev) if on2 else None
+    if g_edges is not None and (g_edges.dtype != dtype or not g_edges.is_contiguous()
                                 or tuple(g_edges.shape) != (b, n, n, lookup.d1)):
-        raise ValueError("edge_features_grad: g_edges must be a contiguous (B,N,N,d1) float32 tensor")
+        raise ValueError(f"edge_features_grad: g_edges must be a contiguous (B,N,N,d1) {dtype} tensor")
     if idx is not None and (idx.dtype != torch.int32 or not idx.is_contiguous() or tuple(idx.shape) != (b, n, k)):
         raise ValueError(f"edge_features_grad: idx must be a contiguous ({b}, {n}, {k}) int32 tensor")
     for lab in ((lookup.tok,) if on1 else ()) + ((lookup.deg,) if on2 else ()):
         if not lab.is_contiguous() or tuple(lab.shape) != (b, n, n):
             raise ValueError(f"edge_features_grad: labels {tuple(lab.shape)} != {(b, n, n)}")
-    lib = _abi.load()
+    entry = getattr(_abi.load(), name)
     args = (_ptr(g), g.stride(0), _ptr(lookup.tok) if on1 else None, v1, lookup.d1, _ptr(lookup.deg) if on2 else None, v2,
             lookup.d2, _ptr(idx), b, n, k, _ptr(g_tok), _ptr(g_deg), _ptr(g_edges))
     nw = c_int64(0)
-    _abi.check(lib.egnn_edge_features_grad_f32(*args, None, byref(nw), _stream()), "egnn_edge_features_grad_f32")
-    work = empty(max(1, nw.value), dtype=torch.float32, device=dev)
+    _abi.check(entry(*args, None, byref(nw), _stream()), name)
+    work = empty(max(1, nw.value), dtype=dtype, device=dev)
     nw = c_int64(work.numel())
     with _timed("edge_features_grad"):
-        rc = lib.egnn_edge_features_grad_f32(*args, _ptr(work), byref(nw), _stream())
-    _abi.check(rc, "egnn_edge_features_grad_f32")
+        rc = entry(*args, _ptr(work), byref(nw), _stream())
+    _abi.check(rc, name)
     return g_tok, g_deg
 
 

@@ -708,16 +708,19 @@ def _need(ctx):
 
 class _LookupGrads:
     """The gradients of an EdgeLookup's tables (EGNNFunction inputs 6, 8, 9) in the backward: per chunk of graphs `add` hands the
-    edge columns of d loss / d per-edge scalars to egnn_edge_features_grad_f32; the embedding gradients of the chunks are summed in
-    chunk order, the dense float edges' rows are stored into a zeroed (B,N,N,d1) tensor.  Nothing else of size B N^2 is allocated."""
+    edge columns of d loss / d per-edge scalars to egnn_edge_features_grad_f32 / _f64; the embedding gradients of the chunks are summed
+    in chunk order, the dense float edges' rows are stored into a zeroed (B,N,N,d1) tensor.  Nothing else of size B N^2 is allocated.
+    Everything is kept in the look-up's compute dtype (`dtype`: float64 for a float64 module) until `outputs` hands it back in the
+    dtypes of the caller's tensors."""
 
     def __init__(self, ctx, b, n, device):
         self.ctx = ctx
         self.lookup = ctx.lookup
+        self.dtype = self.lookup.dtype
         self.dtypes = ctx.table_dtypes
         need = ctx.needs_input_grad                         # (EGNNFunction's own layout: the tables are inputs 6, 8, 9)
         self.want = (bool(need[6]) and self.lookup.edges is not None, bool(need[8]), bool(need[9]))
-        self.g_edges = torch.zeros(b, n, n, self.lookup.d1, dtype=torch.float32, device=device) if self.want[0] else None
+        self.g_edges = torch.zeros(b, n, n, self.lookup.d1, dtype=self.dtype, device=device) if self.want[0] else None
         self.tok = self.deg = None
 
     @property
@@ -743,7 +746,7 @@ class _LookupGrads:
         live = self.lookup.live
         tables = []
         for on, g, w, dt in ((self.want[1], self.tok, live[1], self.dtypes[1]), (self.want[2], self.deg, live[2], self.dtypes[2])):
-            tables.append((torch.zeros(w.shape, dtype=torch.float32, device=w.device) if g is None else g).to(dt) if on else None)
+            tables.append((torch.zeros(w.shape, dtype=self.dtype, device=w.device) if g is None else g).to(dt) if on else None)
         self.ctx.table_grads = tuple(tables)
         return self.g_edges.to(self.dtypes[0]) if self.want[0] else None
 
@@ -793,12 +796,12 @@ class EGNNFunction(torch.autograd.Function):
         ctx.lookup = lookup
         if lookup is not None:
             # the backward differentiates from the (B,N,K,edge_dim) features of the selected pairs, as the edge pass read them -- E x D,
-            # not B N^2 D -- and hands d loss / d them to egnn_edge_features_grad_f32 (`_LookupGrads`)
+            # not B N^2 D, in the look-up's compute dtype -- and hands d loss / d them to egnn_edge_features_grad_f32 / _f64 (`_LookupGrads`)
             b, n = feats.shape[:2]
             k = n if idx is None else idx.shape[-1]
             with torch.no_grad():
                 edges = (_ops_mod().edge_features_gather(lookup, idx, b, n, k) if k > 0 else
-                         torch.empty(b, n, 0, lookup.width, dtype=torch.float32, device=feats.device))
+                         torch.empty(b, n, 0, lookup.width, dtype=lookup.dtype, device=feats.device))
             ctx.table_dtypes = tuple(None if t is None else t.dtype for t in lookup.live)
         ctx.layer = layer
         ctx.has_u = u_pre is not None                    # (E, 16 ceil(m_dim / 16)) fp32: E x m, not E x H
@@ -1892,7 +1895,7 @@ def _backward_recompute(ctx, g_node, g_coors):
         if e is not None and e.requires_grad:
             g = next(it)
             if g is not None and by_k:
-                lk.add(lo, hi, None if idx is None else idx[lo:hi].int().contiguous(), n, k, g.float().reshape(-1, g.shape[-1]))
+                lk.add(lo, hi, None if idx is None else idx[lo:hi].int().contiguous(), n, k, g.to(lk.dtype).reshape(-1, g.shape[-1]))
             elif g is not None:
                 g_edges[lo:hi] = g
         for i, gp in enumerate(g_params):

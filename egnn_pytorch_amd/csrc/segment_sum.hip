@@ -57,14 +57,16 @@ extern "C" int egnn_rows_gather_sum_f32(const float* rows, int64_t ld, const int
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // EGNN_Network front-end (egnn_pytorch.py:410-432): the per-pair edge features of the K selected pairs of every node, looked up
-// from the embedding tables -- see include/egnn_hip.h::egnn_edge_features_gather_f32.  One thread per (edge, column).
+// from the embedding tables -- see include/egnn_hip.h::egnn_edge_features_gather_f32 / _f64 (T = float / double: a copy, the same
+// kernel for both).  One thread per (edge, column).
 namespace {
 
-__global__ __launch_bounds__(256) void edge_features_gather_kernel(const float* __restrict__ edges, const int64_t* __restrict__ tok,
-                                                                   const float* __restrict__ tok_emb, int d1,
-                                                                   const uint8_t* __restrict__ deg, const float* __restrict__ deg_emb,
+template <typename T>
+__global__ __launch_bounds__(256) void edge_features_gather_kernel(const T* __restrict__ edges, const int64_t* __restrict__ tok,
+                                                                   const T* __restrict__ tok_emb, int d1,
+                                                                   const uint8_t* __restrict__ deg, const T* __restrict__ deg_emb,
                                                                    int d2, const int32_t* __restrict__ idx, int N, int K, int64_t total,
-                                                                   float* __restrict__ out)
+                                                                   T* __restrict__ out)
 {
     const int w = d1 + d2;
     for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (int64_t)gridDim.x * 256) {
@@ -74,18 +76,16 @@ __global__ __launch_bounds__(256) void edge_features_gather_kernel(const float* 
         const int k = (int)(edge - node * K);
         const int j = idx ? idx[edge] : k;
         const int64_t pair = node * N + j;
-        float v;
+        T v;
         if (col < d1) v = tok ? tok_emb[tok[pair] * d1 + col] : edges[pair * d1 + col];
         else v = deg_emb[(int64_t)deg[pair] * d2 + (col - d1)];
         out[o] = v;
     }
 }
 
-}  // namespace
-
-extern "C" int egnn_edge_features_gather_f32(const float* edges, const int64_t* edge_tok, const float* edge_tok_emb, int d1,
-                                             const uint8_t* adj_deg, const float* adj_deg_emb, int d2, const int32_t* idx,
-                                             int B, int N, int K, float* out, void* stream)
+template <typename T>
+int edge_features_gather(const T* edges, const int64_t* edge_tok, const T* edge_tok_emb, int d1, const uint8_t* adj_deg,
+                         const T* adj_deg_emb, int d2, const int32_t* idx, int B, int N, int K, T* out, void* stream)
 {
     if (!out) return EGNN_E_NULLPTR;
     if (B <= 0 || N <= 0 || K <= 0 || d1 < 0 || d2 < 0 || d1 + d2 <= 0) return EGNN_E_SHAPE;
@@ -95,27 +95,46 @@ extern "C" int egnn_edge_features_gather_f32(const float* edges, const int64_t* 
     const int64_t total = (int64_t)B * N * K * (d1 + d2);
     int64_t blocks = (total + 255) / 256;
     if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(edge_features_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), edges,
+    hipLaunchKernelGGL(edge_features_gather_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), edges,
                        edge_tok, edge_tok_emb, d1, adj_deg, adj_deg_emb, d2, idx, N, K, total, out);
     return egnn_launch_status();
+}
+
+}  // namespace
+
+extern "C" int egnn_edge_features_gather_f32(const float* edges, const int64_t* edge_tok, const float* edge_tok_emb, int d1,
+                                             const uint8_t* adj_deg, const float* adj_deg_emb, int d2, const int32_t* idx,
+                                             int B, int N, int K, float* out, void* stream)
+{
+    return edge_features_gather<float>(edges, edge_tok, edge_tok_emb, d1, adj_deg, adj_deg_emb, d2, idx, B, N, K, out, stream);
+}
+
+extern "C" int egnn_edge_features_gather_f64(const double* edges, const int64_t* edge_tok, const double* edge_tok_emb, int d1,
+                                             const uint8_t* adj_deg, const double* adj_deg_emb, int d2, const int32_t* idx,
+                                             int B, int N, int K, double* out, void* stream)
+{
+    return edge_features_gather<double>(edges, edge_tok, edge_tok_emb, d1, adj_deg, adj_deg_emb, d2, idx, B, N, K, out, stream);
 }
 
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // Its transpose, the backward of EGNN_Network's per-pair edge features under autograd -- see
-// include/egnn_hip.h::egnn_edge_features_grad_f32.  The gradient of an embedding table is a sum over the edges that carry each
+// include/egnn_hip.h::egnn_edge_features_grad_f32 / _f64.  The gradient of an embedding table is a sum over the edges that carry each
 // label; like every sum over edges here it has a fixed order and no float atomics:
 //   launch 1: G workgroups (G a function of E and the table sizes only), each reduces a contiguous range of edges into a (V, D)
 //             partial.  Its four waves take consecutive quarters of the range; a wave splits into P = 64 / D lane groups (one lane
 //             per column), group p walks edges p, p + P, ... of the quarter in order into an LDS table of its own; the 4 P tables
-//             are then summed in (wave, group) order.  Vocabularies whose tables do not fit LDS_WAVE_FLOATS per wave run in label
+//             are then summed in (wave, group) order.  Vocabularies whose tables do not fit the wave's LDS table run in label
 //             blocks, one blockIdx.y per block: every label's sum still visits the same edges in the same order, so the bits do not
 //             depend on the block size.
 //   launch 2: one thread per output element sums the G partials in index order.
 // Dense float edges (no token table) have no reduction: the pairs of one row are distinct, so their gradient rows are stored.
+// T = float / double: the same kernels.  The LDS budget is the same in bytes, so a wave's table holds half as many doubles (label
+// blocks half as large); G, the walk and the order of every sum do not depend on T.
 namespace {
 
-constexpr int FGRAD_LDS_WAVE_FLOATS = 2048;                    // 8 KB per wave, 32 KB per workgroup
+constexpr int FGRAD_LDS_WAVE_BYTES = 8192;                     // 8 KB per wave, 32 KB per workgroup
+template <typename T> constexpr int FGRAD_LDS_WAVE_ELEMS = FGRAD_LDS_WAVE_BYTES / (int)sizeof(T);   // float: 2048, double: 1024
 constexpr int FGRAD_EDGES_PER_GROUP = 2048;                    // edges per workgroup of launch 1 at most, before the G cap
 
 struct FeatGradTable {
@@ -125,13 +144,15 @@ struct FeatGradTable {
 
 __device__ __forceinline__ int fgrad_groups(int D) { return D <= 64 ? 64 / D : 1; }
 
-__global__ __launch_bounds__(256) void edge_features_grad_part_kernel(const float* __restrict__ g, int64_t ld,
+template <typename T>
+__global__ __launch_bounds__(256) void edge_features_grad_part_kernel(const T* __restrict__ g, int64_t ld,
                                                                       const int64_t* __restrict__ tok, const uint8_t* __restrict__ deg,
                                                                       const int32_t* __restrict__ idx, int N, int K, int64_t E,
                                                                       int64_t per, FeatGradTable t1, FeatGradTable t2,
-                                                                      float* __restrict__ part, int64_t stride)
+                                                                      T* __restrict__ part, int64_t stride)
 {
-    __shared__ float tab[4 * FGRAD_LDS_WAVE_FLOATS];
+    constexpr int WAVE_ELEMS = FGRAD_LDS_WAVE_ELEMS<T>;
+    __shared__ T tab[4 * WAVE_ELEMS];
     const bool second = (int)blockIdx.y >= t1.nb;
     const FeatGradTable t = second ? t2 : t1;
     const int blk = second ? (int)blockIdx.y - t1.nb : (int)blockIdx.y;
@@ -139,7 +160,7 @@ __global__ __launch_bounds__(256) void edge_features_grad_part_kernel(const floa
     const int vb0 = blk * Vb;
     const int vn = min(Vb, t.V - vb0);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int o = threadIdx.x; o < 4 * FGRAD_LDS_WAVE_FLOATS; o += 256) tab[o] = 0.f;
+    for (int o = threadIdx.x; o < 4 * WAVE_ELEMS; o += 256) tab[o] = T(0);
     __syncthreads();
 
     const int64_t e0 = (int64_t)blockIdx.x * per;
@@ -149,8 +170,8 @@ __global__ __launch_bounds__(256) void edge_features_grad_part_kernel(const floa
     const int64_t we = min(e1, ws + q);
     const int p = D <= 64 ? lane / D : 0;
     const int c0 = D <= 64 ? lane - p * D : lane;
-    float* mine = tab + wave * FGRAD_LDS_WAVE_FLOATS + p * Vb * D;
-    const float* gcol = g + t.col0;
+    T* mine = tab + wave * WAVE_ELEMS + p * Vb * D;
+    const T* gcol = g + t.col0;
     auto label = [&](int64_t e) -> int {                       // this block's row of edge e's label, or -1
         const int64_t node = e / K;                            // b * N + i
         const int k = (int)(e - node * K);
@@ -167,7 +188,7 @@ __global__ __launch_bounds__(256) void edge_features_grad_part_kernel(const floa
 #pragma unroll
             for (int u = 0; u < 4; ++u) r[u] = label(e + u * (int64_t)P);
             for (int c = c0; c < D; c += 64) {
-                float x[4];
+                T x[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) x[u] = gcol[(e + u * (int64_t)P) * ld + c];
 #pragma unroll
@@ -183,24 +204,25 @@ __global__ __launch_bounds__(256) void edge_features_grad_part_kernel(const floa
     }
     __syncthreads();
     const int tables = 4 * P;
-    float* out = part + (int64_t)blockIdx.x * stride + t.off + (int64_t)vb0 * D;
+    T* out = part + (int64_t)blockIdx.x * stride + t.off + (int64_t)vb0 * D;
     for (int o = threadIdx.x; o < vn * D; o += 256) {
-        float s = 0.f;
-        for (int w = 0; w < tables; ++w) s += tab[(w / P) * FGRAD_LDS_WAVE_FLOATS + (w % P) * Vb * D + o];
+        T s = T(0);
+        for (int w = 0; w < tables; ++w) s += tab[(w / P) * WAVE_ELEMS + (w % P) * Vb * D + o];
         out[o] = s;
     }
 }
 
-__global__ __launch_bounds__(256) void edge_features_grad_sum_kernel(const float* __restrict__ part, int64_t stride, int G,
-                                                                     int64_t n1, float* __restrict__ out1, float* __restrict__ out2)
+template <typename T>
+__global__ __launch_bounds__(256) void edge_features_grad_sum_kernel(const T* __restrict__ part, int64_t stride, int G,
+                                                                     int64_t n1, T* __restrict__ out1, T* __restrict__ out2)
 {
     const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (o >= stride) return;
-    float s = 0.f;
+    T s = T(0);
     int gi = 0;
     for (; gi + 4 <= G; gi += 4) {                             // four loads in flight, added in index order
-        const float a = part[(int64_t)gi * stride + o], b = part[(int64_t)(gi + 1) * stride + o];
-        const float c = part[(int64_t)(gi + 2) * stride + o], d = part[(int64_t)(gi + 3) * stride + o];
+        const T a = part[(int64_t)gi * stride + o], b = part[(int64_t)(gi + 1) * stride + o];
+        const T c = part[(int64_t)(gi + 2) * stride + o], d = part[(int64_t)(gi + 3) * stride + o];
         s += a;
         s += b;
         s += c;
@@ -211,9 +233,10 @@ __global__ __launch_bounds__(256) void edge_features_grad_sum_kernel(const float
     else out2[o - n1] = s;
 }
 
-__global__ __launch_bounds__(256) void edge_features_grad_dense_kernel(const float* __restrict__ g, int64_t ld,
+template <typename T>
+__global__ __launch_bounds__(256) void edge_features_grad_dense_kernel(const T* __restrict__ g, int64_t ld,
                                                                        const int32_t* __restrict__ idx, int N, int K, int d1,
-                                                                       int64_t total, float* __restrict__ g_edges)
+                                                                       int64_t total, T* __restrict__ g_edges)
 {
     for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (int64_t)gridDim.x * 256) {
         const int64_t e = o / d1;
@@ -226,35 +249,35 @@ __global__ __launch_bounds__(256) void edge_features_grad_dense_kernel(const flo
     }
 }
 
-FeatGradTable fgrad_table(bool on, int V, int D, int col0, int64_t off)
+FeatGradTable fgrad_table(bool on, int V, int D, int col0, int64_t off, int wave_elems)
 {
     FeatGradTable t{};
     if (!on) return t;
     const int P = D <= 64 ? 64 / D : 1;
     t.V = V;
     t.D = D;
-    t.Vb = FGRAD_LDS_WAVE_FLOATS / (P * D) > 1 ? FGRAD_LDS_WAVE_FLOATS / (P * D) : 1;
+    t.Vb = wave_elems / (P * D) > 1 ? wave_elems / (P * D) : 1;
     t.nb = (V + t.Vb - 1) / t.Vb;
     t.col0 = col0;
     t.off = off;
     return t;
 }
 
-}  // namespace
-
-extern "C" int egnn_edge_features_grad_f32(const float* g, int64_t ld, const int64_t* edge_tok, int V1, int d1,
-                                           const uint8_t* adj_deg, int V2, int d2, const int32_t* idx, int B, int N, int K,
-                                           float* g_tok_emb, float* g_deg_emb, float* g_edges, float* work, int64_t* work_floats,
-                                           void* stream)
+template <typename T>
+int edge_features_grad(const T* g, int64_t ld, const int64_t* edge_tok, int V1, int d1, const uint8_t* adj_deg, int V2, int d2,
+                       const int32_t* idx, int B, int N, int K, T* g_tok_emb, T* g_deg_emb, T* g_edges, T* work,
+                       int64_t* work_floats, void* stream)
 {
+    constexpr int WAVE_ELEMS = FGRAD_LDS_WAVE_ELEMS<T>;
     if (!work_floats) return EGNN_E_NULLPTR;
     if (B <= 0 || N <= 0 || K <= 0 || d1 < 0 || d2 < 0 || d1 + d2 <= 0 || ld < d1 + d2) return EGNN_E_SHAPE;
     if (!idx && K != N) return EGNN_E_SHAPE;
     const bool on1 = g_tok_emb != nullptr, on2 = g_deg_emb != nullptr;
     if ((on1 && (!edge_tok || V1 <= 0 || d1 <= 0)) || (on2 && (!adj_deg || V2 <= 0 || d2 <= 0))) return EGNN_E_SHAPE;
     if (g_edges && (edge_tok || d1 <= 0)) return EGNN_E_SHAPE;
-    if ((on1 && d1 > FGRAD_LDS_WAVE_FLOATS) || (on2 && d2 > FGRAD_LDS_WAVE_FLOATS)) return EGNN_E_UNSUPPORTED;
-    const FeatGradTable t1 = fgrad_table(on1, V1, d1, 0, 0), t2 = fgrad_table(on2, V2, d2, d1, on1 ? (int64_t)V1 * d1 : 0);
+    if ((on1 && d1 > WAVE_ELEMS) || (on2 && d2 > WAVE_ELEMS)) return EGNN_E_UNSUPPORTED;
+    const FeatGradTable t1 = fgrad_table(on1, V1, d1, 0, 0, WAVE_ELEMS),
+                        t2 = fgrad_table(on2, V2, d2, d1, on1 ? (int64_t)V1 * d1 : 0, WAVE_ELEMS);
     if ((int64_t)t1.nb + t2.nb > 65535) return EGNN_E_UNSUPPORTED;
     const int64_t E = (int64_t)B * N * K;
     const int64_t n1 = on1 ? (int64_t)V1 * d1 : 0, n2 = on2 ? (int64_t)V2 * d2 : 0;
@@ -278,18 +301,38 @@ extern "C" int egnn_edge_features_grad_f32(const float* g, int64_t ld, const int
         const int64_t total = E * d1;
         int64_t blocks = (total + 255) / 256;
         if (blocks > 65536) blocks = 65536;
-        hipLaunchKernelGGL(edge_features_grad_dense_kernel, dim3((unsigned)blocks), dim3(256), 0, st, g, ld, idx, N, K, d1, total,
+        hipLaunchKernelGGL(edge_features_grad_dense_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, g, ld, idx, N, K, d1, total,
                            g_edges);
         const int rc = egnn_launch_status();
         if (rc) return rc;
     }
     if (stride == 0) return EGNN_OK;
     const int64_t per = (E + G - 1) / G;
-    hipLaunchKernelGGL(edge_features_grad_part_kernel, dim3((unsigned)G, (unsigned)(t1.nb + t2.nb)), dim3(256), 0, st, g, ld,
+    hipLaunchKernelGGL(edge_features_grad_part_kernel<T>, dim3((unsigned)G, (unsigned)(t1.nb + t2.nb)), dim3(256), 0, st, g, ld,
                        edge_tok, adj_deg, idx, N, K, E, per, t1, t2, work, stride);
     int rc = egnn_launch_status();
     if (rc) return rc;
-    hipLaunchKernelGGL(edge_features_grad_sum_kernel, dim3((unsigned)((stride + 255) / 256)), dim3(256), 0, st, work, stride, (int)G,
+    hipLaunchKernelGGL(edge_features_grad_sum_kernel<T>, dim3((unsigned)((stride + 255) / 256)), dim3(256), 0, st, work, stride, (int)G,
                        n1, g_tok_emb, g_deg_emb);
     return egnn_launch_status();
+}
+
+}  // namespace
+
+extern "C" int egnn_edge_features_grad_f32(const float* g, int64_t ld, const int64_t* edge_tok, int V1, int d1,
+                                           const uint8_t* adj_deg, int V2, int d2, const int32_t* idx, int B, int N, int K,
+                                           float* g_tok_emb, float* g_deg_emb, float* g_edges, float* work, int64_t* work_floats,
+                                           void* stream)
+{
+    return edge_features_grad<float>(g, ld, edge_tok, V1, d1, adj_deg, V2, d2, idx, B, N, K, g_tok_emb, g_deg_emb, g_edges, work,
+                                     work_floats, stream);
+}
+
+extern "C" int egnn_edge_features_grad_f64(const double* g, int64_t ld, const int64_t* edge_tok, int V1, int d1,
+                                           const uint8_t* adj_deg, int V2, int d2, const int32_t* idx, int B, int N, int K,
+                                           double* g_tok_emb, double* g_deg_emb, double* g_edges, double* work, int64_t* work_floats,
+                                           void* stream)
+{
+    return edge_features_grad<double>(g, ld, edge_tok, V1, d1, adj_deg, V2, d2, idx, B, N, K, g_tok_emb, g_deg_emb, g_edges, work,
+                                      work_floats, stream);
 }

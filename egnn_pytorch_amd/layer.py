@@ -92,27 +92,50 @@ class EdgeLookup:
     """Per-pair edge features given as look-up tables instead of a materialised (B,N,N,edge_dim) tensor: what EGNN_Network's
     front-end produces (egnn_pytorch.py:410-432) -- [edge_emb(edge tokens) or float edges | adj_emb(adjacency-degree labels)].
     The edge kernel reads the tables for the K selected pairs of each node (egnn_edge_features_gather_f32).  `edges`, `tok_emb` and
-    `deg_emb` (`live`) are the caller's tensors -- the dense float edges and the embedding weights -- and the kernels read detached fp32
-    copies of them.  Under autograd the layer hands the live ones to autograd.EGNNFunction as differentiable inputs: their gradients
-    come from egnn_edge_features_grad_f32, a reduction over the selected pairs only."""
+    `deg_emb` (`live`) are the caller's tensors -- the dense float edges and the embedding weights -- and the kernels read detached
+    copies of them in `dtype`, the compute dtype of the layers that consume them: float32, or float64 for float64 modules
+    (egnn_edge_features_gather_f64).  Under autograd the layer hands the live ones to autograd.EGNNFunction as differentiable inputs:
+    their gradients come from egnn_edge_features_grad_f32 / _f64, a reduction over the selected pairs only."""
 
-    def __init__(self, edges=None, tok=None, tok_emb=None, deg=None, deg_emb=None):
+    def __init__(self, edges=None, tok=None, tok_emb=None, deg=None, deg_emb=None, dtype=torch.float32):
         self.live = (edges, tok_emb if tok is not None else None, deg_emb if deg is not None else None)
-        self.edges = None if edges is None else _ops.aligned(edges.detach().float())
         self.tok = None if tok is None else tok.contiguous().long()
-        self.tok_emb = None if tok_emb is None else tok_emb.detach().contiguous().float()
         self.deg = None if deg is None else deg.contiguous()
-        self.deg_emb = None if deg_emb is None else deg_emb.detach().contiguous().float()
+        self._copy_tables(dtype)
         self.d1 = self.tok_emb.shape[1] if self.tok is not None else (self.edges.shape[-1] if self.edges is not None else 0)
         self.d2 = self.deg_emb.shape[1] if self.deg is not None else 0
+
+    def _copy_tables(self, dtype):
+        """the kernel-side copies of `live` in `dtype` (converted from the caller's tensors themselves, never from another copy)"""
+        edges, tok_emb, deg_emb = self.live
+        self.dtype = dtype
+        self.edges = None if edges is None else _ops.aligned(edges.detach().to(dtype))
+        self.tok_emb = None if tok_emb is None else tok_emb.detach().contiguous().to(dtype)
+        self.deg_emb = None if deg_emb is None else deg_emb.detach().contiguous().to(dtype)
+        self._casts = {}                                        # (dtype -> a copy in that dtype; never holds the object itself)
 
     @property
     def width(self):
         return self.d1 + self.d2
 
+    def to(self, dtype):
+        """The same look-up with its table copies in `dtype`: itself when they are already, else a copy made once from `live` and kept
+        (the layers of a network share one EdgeLookup: one conversion per forward, not one per layer).  The copy does not point back, so
+        an EdgeLookup is freed by its reference count like any tensor holder: it pins N^2-sized label maps."""
+        if dtype == self.dtype:
+            return self
+        out = self._casts.get(dtype)
+        if out is None:
+            out = copy.copy(self)
+            out._copy_tables(dtype)
+            self._casts[dtype] = out
+        return out
+
     def graphs(self, lo, hi):
         """The same tables for graphs [lo, hi) of the batch (the labels and dense edges sliced, the embedding tables shared)."""
         out = copy.copy(self)
+        out._casts = {}
+        out.live = (None if self.live[0] is None else self.live[0][lo:hi],) + tuple(self.live[1:])
         out.edges = None if self.edges is None else self.edges[lo:hi]
         out.tok = None if self.tok is None else self.tok[lo:hi]
         out.deg = None if self.deg is None else self.deg[lo:hi]
@@ -247,6 +270,8 @@ class EGNN(nn.Module):
         autograd.EGNNFunction (HIP forward, recompute-in-backward)."""
         if _ops.RANGE_CHECK == "deferred" and feats.is_cuda:
             _ops.check_range(feats.device, wait=False)              # an earlier call's status, if it has arrived
+        if isinstance(edges, EdgeLookup):
+            edges = edges.to(self.compute_dtype())                  # (the table copies in the dtype this layer's kernels read)
         lookup = edges if isinstance(edges, EdgeLookup) else None
         # (edge look-up tables: the dense float edges and the two embedding weights they were built from are differentiable inputs)
         dense, tok_w, deg_w = lookup.live if lookup is not None else (edges, None, None)
@@ -276,8 +301,6 @@ class EGNN(nn.Module):
         _abi.load()
         f_dtype, c_dtype = feats.dtype, coors.dtype
         f64 = self.float64_kernels()
-        if f64 and isinstance(edges, EdgeLookup):
-            raise NotImplementedError("float64 modules take the materialised (B,N,N,edge_dim) edge features")
         if not f64 and torch.float64 in (f_dtype, c_dtype):
             _warn_float64_once()
         b, n = feats.shape[:2]
@@ -290,7 +313,8 @@ class EGNN(nn.Module):
             with torch.cuda.device(feats.device):
                 if self.dropout_active() and drop_seed is None:
                     drop_seed = _dropout.draw_seed()
-                out = self._forward_exact(feats.double(), coors.double(), None if edges is None else edges.double(), mask, adj_mat,
+                out = self._forward_exact(feats.double(), coors.double(),
+                                          edges if (edges is None or isinstance(edges, EdgeLookup)) else edges.double(), mask, adj_mat,
                                           self._neighbour_count(n, adj_mat),
                                           dtype=torch.float64, want_u=want_u,
                                           drop=(self.dropout_p, drop_seed) if self.dropout_active() else None)
@@ -714,9 +738,11 @@ _FP64_WARNED = False
 
 
 def _embed_pairs(emb, idx):
-    """emb(idx) for a (B,N,N) index tensor of any size.  torch's device embedding fails to launch (invalid configuration) on
-    (1, 8192, 8192) indices on the MI355X; up to 2^24 indices it is one call, as before, beyond that chunks of at most 2^24 indices
-    and 2^26 outputs (the sizes it handles), concatenated.  Under autograd: the weight's gradient sums the chunks' in turn."""
+    """emb(idx) for a (B,N,N) index tensor of any size: the materialised (B,N,N,D) recipe of egnn_pytorch.py:410-432, which no module
+    here runs any more (EGNN_Network reads look-up tables in every dtype) -- kept for the timing tools under tools/ only.
+    torch's device embedding fails to launch (invalid configuration) on (1, 8192, 8192) indices on the MI355X; up to 2^24 indices it is
+    one call, beyond that chunks of at most 2^24 indices and 2^26 outputs (the sizes it handles), concatenated.  Under autograd: the
+    weight's gradient sums the chunks' in turn."""
     n = idx.numel()
     if n <= 1 << 24:
         return emb(idx)
@@ -806,14 +832,12 @@ class EGNN_Network(nn.Module):
         # Edge features for the layers: look-up tables (EdgeLookup) -- the (B,N,N,edge_dim+adj_dim) tensor of :410-432 is never
         # materialised, the edge kernel reads the embedding rows of the K selected pairs of each node.  Under autograd the embedding
         # weights (and dense float edges) are inputs of each layer's autograd.EGNNFunction, whose backward reduces their gradients over
-        # the same pairs (egnn_edge_features_grad_f32).  Float64 modules take the materialised tensor, in inference and training.
-        lazy = not any(l.float64_kernels() for _, l in self.layers)       # (depth = 0: an empty loop, as upstream)
+        # the same pairs (egnn_edge_features_grad_f32 / _f64).  The tables' kernel-side copies take the layers' compute dtype, made once
+        # here for all of them: float64 for a float64 network, which runs on the tables like any other.
+        lookup_dtype = self.layers[0][1].compute_dtype() if len(self.layers) else torch.float32
         tok = tok_emb = None
         if edges is not None and self.edge_emb is not None:
-            if lazy:
-                tok, tok_emb, edges = edges, self.edge_emb.weight, None
-            else:
-                edges = _embed_pairs(self.edge_emb, edges)
+            tok, tok_emb, edges = edges, self.edge_emb.weight, None
 
         if self.num_adj_degrees is not None:
             assert adj_mat is not None, "adjacency matrix must be passed in (keyword argument adj_mat)"
@@ -822,14 +846,10 @@ class EGNN_Network(nn.Module):
             # N-degree expansion (egnn_pytorch.py:414-427) as bit-set algebra on the device instead of float matmuls
             adj_mat, adj_indices = _ops.adj_expand(adj_mat, b, self.num_adj_degrees)
             if self.adj_emb is not None:
-                if lazy:
-                    edges = EdgeLookup(edges=edges, tok=tok, tok_emb=tok_emb, deg=adj_indices, deg_emb=self.adj_emb.weight)
-                    tok = None
-                else:
-                    adj_emb = _embed_pairs(self.adj_emb, adj_indices.long())
-                    edges = torch.cat((edges, adj_emb), dim=-1) if edges is not None else adj_emb
+                edges = EdgeLookup(edges=edges, tok=tok, tok_emb=tok_emb, deg=adj_indices, deg_emb=self.adj_emb.weight, dtype=lookup_dtype)
+                tok = None
         if tok is not None:                                         # edge tokens without adjacency degrees
-            edges = EdgeLookup(tok=tok, tok_emb=tok_emb)
+            edges = EdgeLookup(tok=tok, tok_emb=tok_emb, dtype=lookup_dtype)
 
         global_tokens = None
         if self.global_tokens is not None:

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define EGNN_ABI_VERSION 42
+#define EGNN_ABI_VERSION 43
 
 enum {
     EGNN_OK = 0,
@@ -390,6 +390,11 @@ int egnn_edge_fused_f32(const egnn_edge_args* args, void* stream);
 int egnn_edge_features_gather_f32(const float* edges, const int64_t* edge_tok, const float* edge_tok_emb, int d1,
                                   const uint8_t* adj_deg, const float* adj_deg_emb, int d2, const int32_t* idx,
                                   int B, int N, int K, float* out, void* stream);
+/* The same for float64 modules: edges, both embedding tables and out are double (the same kernel: a copy, so out holds the tables'
+ * own bits), fed to egnn_edge_exact_f64 with edges_by_k = 1.  Labels and idx as above. */
+int egnn_edge_features_gather_f64(const double* edges, const int64_t* edge_tok, const double* edge_tok_emb, int d1,
+                                  const uint8_t* adj_deg, const double* adj_deg_emb, int d2, const int32_t* idx,
+                                  int B, int N, int K, double* out, void* stream);
 
 /* Its transpose: the gradients of the look-up tables under autograd, from the per-edge gradient rows g (E x ld fp32, E = B*N*K;
  * columns [0, d1) belong to the first table, [d1, d1+d2) to adj_deg_emb -- the edge columns of d loss / d per-edge scalars):
@@ -406,6 +411,14 @@ int egnn_edge_features_gather_f32(const float* edges, const int64_t* edge_tok, c
 int egnn_edge_features_grad_f32(const float* g, int64_t ld, const int64_t* edge_tok, int V1, int d1,
                                 const uint8_t* adj_deg, int V2, int d2, const int32_t* idx, int B, int N, int K,
                                 float* g_tok_emb, float* g_deg_emb, float* g_edges, float* work, int64_t* work_floats,
+                                void* stream);
+/* The same for float64 modules: g, the three gradient outputs and work are double, *work_floats counts doubles.  The same kernels:
+ * the same G, the same walk over the edges and the same order of every sum as _f32 (launch 1 keeps its 32 KB of LDS, so a wave's
+ * table holds half as many elements and label blocks are half as large, which the bits do not depend on); no float atomics, two
+ * runs give the same bits.  d1, d2 <= 1024 (one row of a table must fit a wave's LDS table); EGNN_E_UNSUPPORTED beyond. */
+int egnn_edge_features_grad_f64(const double* g, int64_t ld, const int64_t* edge_tok, int V1, int d1,
+                                const uint8_t* adj_deg, int V2, int d2, const int32_t* idx, int B, int N, int K,
+                                double* g_tok_emb, double* g_deg_emb, double* g_edges, double* work, int64_t* work_floats,
                                 void* stream);
 
 /* Backward of the edge pass without anything of size E x H in memory (autograd of egnn_pytorch.py:279-287;
