@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests._masks import PATTERNS, mask_pattern
 from tests._reference import case_key, check_state, pack_grads, reference_result, state_digest, unpack_grads
 from tests._util import golden_names, layer_kwargs, load_golden
 
@@ -106,6 +107,78 @@ def test_restatement_gradients_match_reference_autograd(name):
             if g is not None:
                 scale = max(1.0, float(w.abs().max()))
                 np.testing.assert_allclose(g.numpy(), w.numpy(), atol=1e-7 * scale, rtol=0)
+
+
+MASK_LAYERS = {
+    "knn6": dict(dim=16, num_nearest_neighbors=6),
+    "all_flags": dict(dim=16, num_nearest_neighbors=6, norm_coors=True, soft_edges=True, m_pool_method="mean", coor_weights_clamp_value=2.0,
+                      norm_feats=True),
+    "dense": dict(dim=16),
+}
+
+
+@pytest.mark.parametrize("pattern", PATTERNS)
+@pytest.mark.parametrize("lname", list(MASK_LAYERS))
+def test_restatement_gradients_match_reference_autograd_on_mask_patterns(lname, pattern):
+    """The sibling of the test above on masks that are no prefixes (tests/_masks.py): scattered, padding in front, blocks of four, an
+    empty graph, fewer real nodes than neighbours, interleaved.  The neighbour list restates the reference's ranking in float64
+    (egnn_pytorch.py:238-258: masked pairs rank 1e5, topk(largest=False)); the loss is one over real nodes (zero cotangent on padded
+    rows), for which the reference's own gradients of the padded rows' feats and coors are exactly 0.0."""
+    import zlib
+    from egnn_pytorch_amd import EGNN
+    from egnn_pytorch_amd.autograd import layer_given_neighbors
+    kw = MASK_LAYERS[lname]
+    b, n, dim = 4, 24, kw["dim"]
+    k = kw.get("num_nearest_neighbors", 0)
+    seed = zlib.crc32(f"{lname}/{pattern}".encode())
+    mask_np = mask_pattern(pattern, b, n, k or None, np.random.default_rng(seed))
+    mask = torch.from_numpy(mask_np)
+
+    def xavier(cls):                                         # (as the baseline-width tests: weights of a trained network's size, so that
+        torch.manual_seed(seed % 1000)                       #  the gate, the clamp and the norms are all partly active)
+        m = cls(**kw)
+        for mod in m.modules():
+            if isinstance(mod, torch.nn.Linear):
+                torch.nn.init.xavier_normal_(mod.weight)
+        return m
+    g = torch.Generator().manual_seed(seed + 1)
+    feats = torch.randn(b, n, dim, generator=g, dtype=torch.float64)
+    coors = torch.randn(b, n, 3, generator=g, dtype=torch.float64)
+    rn = torch.randn(b, n, dim, generator=g, dtype=torch.float64) * mask[..., None]
+    rc = torch.randn(b, n, 3, generator=g, dtype=torch.float64) * mask[..., None]
+
+    def grads_of(module, call):
+        f, c = feats.clone().requires_grad_(True), coors.clone().requires_grad_(True)
+        node, co = call(f, c)
+        return torch.autograd.grad((node * rn).sum() + (co * rc).sum(), [f, c] + list(module.parameters()), allow_unused=True)
+
+    def reference(ref):
+        rlayer = xavier(ref.EGNN)
+        digest = state_digest(rlayer)
+        rlayer = rlayer.double()
+        return dict(pack_grads(grads_of(rlayer, lambda f, c: rlayer(f, c, None, mask))), state_sha256=digest)
+    stored = reference_result(f"restatement_grads_masks_{lname}_{pattern}", reference)
+    layer = xavier(EGNN)
+    check_state(layer, stored)
+    layer = layer.double()
+    want = unpack_grads(stored)
+    for w in want[:2]:                                       # the reference itself: padded rows of d/d feats, d/d coors are exact zeros
+        assert float(w[~mask].abs().max()) == 0.0 and bool(torch.isfinite(w).all())
+    idx = rank = None
+    if k:
+        with torch.no_grad():
+            ranking = ((coors[:, :, None, :] - coors[:, None, :, :]) ** 2).sum(dim=-1)
+            ranking = ranking.masked_fill(~(mask[:, :, None] & mask[:, None, :]), 1e5)
+            rank, idx = ranking.topk(k, dim=-1, largest=False)
+    for factorised in (True, False):
+        got = grads_of(layer, lambda f, c: layer_given_neighbors(layer, f, c, None, mask, idx, rank, float("inf"), factorised))
+        assert len(got) == len(want)
+        for pos, (gg, w) in enumerate(zip(got, want)):
+            assert (gg is None) == (w is None)
+            if gg is not None:
+                assert float(w.abs().max()) > 0, pos
+                scale = max(1.0, float(w.abs().max()))
+                np.testing.assert_allclose(gg.numpy(), w.numpy(), atol=1e-7 * scale, rtol=0)
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU
@@ -836,7 +909,9 @@ def _emulated_backward(layer, feats, coors, mask, idx, rank, radius, g_node, g_c
             rows = rows.view(-1, 2, rows.shape[1]).sum(dim=1)
         out = {"rows": rows}
         if want_w2:
-            out["w2"] = gu16.t() @ a
+            # (the pass carries SiLU(z) for d/d W_2 as fp16 x 2^6, csrc/edge_bwd.hip: beyond 65504 / 64 it is inf there, and an edge
+            # whose gU is 0 then adds 0 x inf)
+            out["w2"] = gu16.t() @ a.masked_fill(a.abs() > 65504.0 / 64.0, float("inf"))
         if ws_nat is not None:
             out["ws"] = dz.t() @ scal
             out["scal"] = dz @ ws_nat
@@ -893,23 +968,33 @@ def _emulated_backward(layer, feats, coors, mask, idx, rank, radius, g_node, g_c
     return [out[4], out[5]] + list(out[7:])
 
 
-@pytest.mark.parametrize("kw,use_mask,max_graphs", [(dict(dim=8, num_nearest_neighbors=5), False, 0),
-                                                    (dict(dim=8, num_nearest_neighbors=6, norm_coors=True, coor_weights_clamp_value=0.6), True, 0),
-                                                    (dict(dim=8, num_nearest_neighbors=20, m_pool_method="mean", norm_feats=True), True, 2),
-                                                    (dict(dim=8, num_nearest_neighbors=7, soft_edges=True, m_dim=12), True, 0),
-                                                    (dict(dim=8, num_nearest_neighbors=7, m_dim=20), True, 0),          # two blocks of 16 channels
-                                                    (dict(dim=8, num_nearest_neighbors=9, m_dim=40, soft_edges=True), False, 2)])
-def test_native_backward_host_logic_with_emulated_kernels(kw, use_mask, max_graphs):
+_HOST_LOGIC = [(dict(dim=8, num_nearest_neighbors=5), False, 0),
+               (dict(dim=8, num_nearest_neighbors=6, norm_coors=True, coor_weights_clamp_value=0.6), True, 0),
+               (dict(dim=8, num_nearest_neighbors=20, m_pool_method="mean", norm_feats=True), True, 2),
+               (dict(dim=8, num_nearest_neighbors=7, soft_edges=True, m_dim=12), True, 0),
+               (dict(dim=8, num_nearest_neighbors=7, m_dim=20), True, 0),          # two blocks of 16 channels
+               (dict(dim=8, num_nearest_neighbors=9, m_dim=40, soft_edges=True), False, 2)]
+# the prefix-mask / no-mask cases under the ids they always had, then every masked configuration on every pattern of tests/_masks.py,
+# whole and in chunks of two graphs
+_HOST_LOGIC_CASES = [pytest.param(kw, um, mg, None, id=f"kw{i}-{um}-{mg}") for i, (kw, um, mg) in enumerate(_HOST_LOGIC)] + \
+                    [pytest.param(kw, True, mg, pat, id=f"kw{i}-{pat}-{mg}")
+                     for i, (kw, um, _) in enumerate(_HOST_LOGIC) if um for pat in PATTERNS for mg in (0, 2)]
+
+
+@pytest.mark.parametrize("kw,use_mask,max_graphs,pattern", _HOST_LOGIC_CASES)
+def test_native_backward_host_logic_with_emulated_kernels(kw, use_mask, max_graphs, pattern):
     """autograd._backward_native on the CPU with its three kernels emulated in torch from their header contracts: what remains
     under test is the host side -- entry lists, partial rows, fixed-order sums, chunking over graphs, the node-level products,
-    the parameter bookkeeping -- against autograd of the restated layer."""
+    the parameter bookkeeping -- against autograd of the restated layer.  `pattern`: a mask of tests/_masks.py instead of the prefix
+    one (four graphs); the padded rows' coordinates are then three orders of magnitude above the real ones', so that a pair the masks
+    remove has an edge_mlp hidden activation far beyond what the E x H pass can hold -- the host side must keep that away from it."""
     from egnn_pytorch_amd import EGNN, autograd as A
     torch.manual_seed(5)
     layer = EGNN(**kw)
     with torch.no_grad():
         for p in layer.parameters():
             p.mul_(40.0)
-    b, n = 3, 24
+    b, n = (3, 24) if pattern is None else (4, 24)
     k = kw["num_nearest_neighbors"]
     g = torch.Generator().manual_seed(6)
     feats, coors = torch.randn(b, n, kw["dim"], generator=g), torch.randn(b, n, 3, generator=g)
@@ -917,6 +1002,9 @@ def test_native_backward_host_logic_with_emulated_kernels(kw, use_mask, max_grap
     idx[:, :, 0] = torch.arange(n)[None, :]                                          # the self pair, as the selection always has it
     rank = torch.rand(b, n, k, generator=g)
     mask = (torch.arange(n)[None] < torch.tensor([n, n - 5, n // 2])[:, None]) if use_mask else None
+    if pattern is not None:
+        mask = torch.from_numpy(mask_pattern(pattern, b, n, k, np.random.default_rng(7)))
+        coors = torch.where(mask[..., None], coors, 1e3 * coors)
     gn, gc = torch.randn(b, n, kw["dim"], generator=g), torch.randn(b, n, 3, generator=g)
     got = _emulated_backward(layer, feats, coors, mask, idx, rank, 0.8, gn, gc, max_graphs)
     l64 = __import__("copy").deepcopy(layer).double()
@@ -927,6 +1015,7 @@ def test_native_backward_host_logic_with_emulated_kernels(kw, use_mask, max_grap
         if r is None:
             assert a is None or float(a.abs().max()) == 0.0
             continue
+        assert bool(torch.isfinite(a).all()), pos
         scale = max(1e-12, float(r.abs().max()))
         assert float((a.double() - r).abs().max()) <= 2e-4 * scale, (pos, float((a.double() - r).abs().max()), scale)
 
