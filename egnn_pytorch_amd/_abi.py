@@ -16,7 +16,7 @@ from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int
 
 import torch  # noqa: F401  (must precede CDLL, see module docstring)
 
-ABI_VERSION = 43
+ABI_VERSION = 44
 _LIB_NAME = "libegnn_hip.so"
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 
@@ -185,7 +185,8 @@ class PackedInfo(Structure):
 class ForwardOpts(Structure):
     """Mirror of `struct egnn_forward_opts`."""
     _fields_ = [("side_stream", c_void_p), ("ev_fork", c_void_p), ("ev_join", c_void_p), ("order", c_void_p), ("nmf_img", c_void_p),
-                ("order_is_hint", c_int32), ("reserved", c_int32)]
+                ("order_is_hint", c_int32), ("status_words", c_int32), ("status_pub", c_void_p), ("status_seq", c_int32),
+                ("reserved", c_int32)]
 
 
 def layer_desc(layer) -> "LayerDesc":

@@ -219,10 +219,89 @@ def _raise_range(bits, when, origin="call"):
     raise err
 
 
+class _EarlyPublish:
+    """One forward's hand-over between the module entry whose range check follows it (`early_publish`), the one C whole-layer call that
+    may publish the status words itself (`status_request`) and `range_check_after_forward`, which then only spins."""
+    __slots__ = ("last", "pending")
+
+    def __init__(self):
+        self.last = True           # the next EGNN layer call is the last one that can write the status word before the check
+        self.pending = None        # (status, sequence number) requested from the C entry; the status's lock is held while set
+
+
+_early = contextvars.ContextVar("egnn_early_publish", default=None)
+
+
+def _early_publish_on():
+    """EGNN_STATUS_EARLY=0: the status words are published behind the whole forward again (read at every call; A/B and tests)."""
+    return os.environ.get("EGNN_STATUS_EARLY", "1") != "0"
+
+
+@contextlib.contextmanager
+def early_publish(last=True):
+    """Around a module forward AND the `range_check_after_forward` that follows it: the C whole-layer entry may publish the status words
+    from inside the forward, directly behind its last launch that can write them (egnn_forward_opts.status_pub), instead of this
+    module publishing them behind the forward's last kernel.  `last`: False while layers that can still write the word follow
+    (EGNN_Network sets it in front of its last layer).  A request the check never consumed (an exception in between) is dropped here."""
+    ep = _EarlyPublish()
+    ep.last = last
+    tok = _early.set(ep)
+    try:
+        yield ep
+    finally:
+        _early.reset(tok)
+        if ep.pending is not None:
+            st, ep.pending = ep.pending[0], None
+            st.lock.release()
+
+
+def status_request(device):
+    """(pinned words, word count, sequence number) for egnn_forward_opts when THIS call's launches are the last that can write the status
+    word before `range_check_after_forward` reads it -- sync mode, spinning on, no stream capture, inside `early_publish` with `last`
+    set, the forward's status word current -- else None.  Takes the device's lock: `range_check_after_forward` (or `early_publish`'s
+    exit) releases it, so the sequence number and the pinned words stay this thread's from the request to the end of the spin."""
+    ep = _early.get()
+    if (ep is None or not ep.last or ep.pending is not None or RANGE_CHECK != "sync" or not _SPIN or _status_slot.get() != 0
+            or not _early_publish_on() or torch.cuda.is_current_stream_capturing()):
+        return None
+    st = status_word(device)
+    st.lock.acquire()
+    st.seq = (st.seq % 0x7ffffff0) + 1
+    ep.pending = (st, st.seq)
+    return st.pub.data_ptr(), 2, st.seq
+
+
+def _spin_for(st, seq):
+    """Spin on the pinned sequence number (bounded by TIME: a count of Python iterations is seconds on one host and minutes on another);
+    (forward word, backward word), or (None, None) past the limit."""
+    view, spins = st.pub_np, 0
+    deadline = None
+    while view[2] != seq:
+        spins += 1
+        if (spins & 0xFFF) == 0:
+            now = time.perf_counter()
+            if deadline is None:
+                deadline = now + _SPIN_SECONDS
+            elif now > deadline:
+                break
+    if view[2] == seq:
+        return int(view[0]), int(view[1])
+    return None, None
+
+
 def range_check_after_forward(device, mode=None):
     """Called by the modules when a forward has been enqueued."""
     mode = mode or RANGE_CHECK
+    ep = _early.get()
+    pending = None
+    if ep is not None and ep.pending is not None:
+        pending, ep.pending = ep.pending, None          # (whatever happens below, the lock taken by `status_request` is released once)
+    if pending is not None and mode != "sync":          # (requests are made in sync mode only: a mode flipped in between)
+        pending[0].lock.release()
+        pending = None
     if mode == "off" or torch.cuda.is_current_stream_capturing():      # (graph capture: graphed() checks after each replay)
+        if pending is not None:
+            pending[0].lock.release()
         return
     st = status_word(device)
     if mode == "sync":
@@ -230,7 +309,15 @@ def range_check_after_forward(device, mode=None):
         # through a staged pageable copy: slower per forward; a one-thread kernel writing the words into pinned memory for the host to spin
         # on was measured too: no faster -- what the synchronisation costs is the host time from forward() entry to its first launch)
         fwd = bwd = None
-        if _SPIN:
+        if pending is not None:
+            # the C whole-layer entry has published already, behind its last launch that can write the word: nothing to launch, the
+            # sequence number requested there is the one to wait for (the lock has been held since that request)
+            try:
+                if pending[0] is st:
+                    fwd, bwd = _spin_for(st, pending[1])
+            finally:
+                pending[0].lock.release()
+        elif _SPIN:
             # publish + spin under the device's lock: the sequence number and the pinned words are per device, and two threads running
             # forwards on one device would overwrite each other's (one of them then spun out its whole limit).  The spin is bounded by
             # TIME (a count of Python iterations is seconds on one host and minutes on another); past it: the copy + synchronise below.
@@ -239,18 +326,7 @@ def range_check_after_forward(device, mode=None):
                 with torch.cuda.device(st.dev.device):
                     rc = _abi.load().egnn_status_publish(st.dev.data_ptr(), st.pub.data_ptr(), 2, st.seq, _stream())
                 _abi.check(rc, "egnn_status_publish")
-                view, seq, spins = st.pub_np, st.seq, 0
-                deadline = None
-                while view[2] != seq:
-                    spins += 1
-                    if (spins & 0xFFF) == 0:
-                        now = time.perf_counter()
-                        if deadline is None:
-                            deadline = now + _SPIN_SECONDS
-                        elif now > deadline:
-                            break
-                if view[2] == seq:
-                    fwd, bwd = int(view[0]), int(view[1])
+                fwd, bwd = _spin_for(st, st.seq)
         if fwd is None:                                 # (EGNN_RANGE_SPIN=0, or the pinned word never changed: copy + synchronise)
             st.host.copy_(st.dev, non_blocking=True)
             torch.cuda.current_stream(st.dev.device).synchronize()

@@ -321,6 +321,10 @@ extern "C" int egnn_layer_forward_opts_f32(const egnn_layer_desc* desc, const eg
     // (ev_fork, recorded before the node-level launches) and is joined in front of the edge pass (ev_join)
     hipStream_t side = opts ? static_cast<hipStream_t>(opts->side_stream) : nullptr;
     if (side && (!opts->ev_fork || !opts->ev_join)) return EGNN_E_NULLPTR;
+    // the range status handed to the host by this call (opts->status_pub): checked before anything is enqueued
+    const bool publish = opts && opts->status_pub;
+    if (publish && !status) return EGNN_E_NULLPTR;
+    if (publish && (opts->status_words < 1 || opts->status_words > 8)) return EGNN_E_SHAPE;
     const Dims x = dims_of(desc);
     if (!x.ok) return EGNN_E_UNSUPPORTED;
     if (B <= 0 || N <= 0 || K < 0 || coor_dim < 1 || coor_dim > 8) return EGNN_E_SHAPE;
@@ -441,6 +445,7 @@ extern "C" int egnn_layer_forward_opts_f32(const egnn_layer_desc* desc, const eg
     }
 
     // ---- node update (:335-337)
+    bool published = false;
     if (desc->update_feats && egnn_node_mlp_fused_halves(dim, x.m) > 0) {
         // (the Python module packs the fused image once per parameter version; this entry keeps no state between calls and re-derives
         // it -- ~1 MB -- from the blob's two packed images)
@@ -458,9 +463,20 @@ extern "C" int egnn_layer_forward_opts_f32(const egnn_layer_desc* desc, const eg
         EGNN_TRY(egnn_linear_hl_f32(node_hi, node_lo, blob + info->w5_hi, blob + info->w5_lo, info->w5_inv_scale, F(info->b5), nullptr, 0,
                                     nullptr, 0, ws + w.hid_hi, ws + w.hid_lo, x.kp_hid, rows, 2 * dim, x.kp_node, info->w5_rows, 1, 0,
                                     status, stream));
+        // The status words go to the host HERE, behind the first Linear: it is the last launch of this path that can write them.  A
+        // linear_hl launch raises EGNN_RANGE_PROJ only for columns below split_cols and EGNN_RANGE_A_OPERAND only where it packs an
+        // fp16 image (Chi); the second Linear below has split_cols = 0 and writes plain fp32 rows, so it has no cast site.  The host's
+        // round trip -- see the sequence number, enqueue the next forward -- then runs under that GEMM instead of behind it.
+        if (publish) {
+            EGNN_TRY(egnn_status_publish(status, opts->status_pub, opts->status_words, opts->status_seq, stream));
+            published = true;
+        }
         EGNN_TRY(egnn_linear_hl_f32(ws + w.hid_hi, ws + w.hid_lo, blob + info->w6_hi, blob + info->w6_lo, info->w6_inv_scale, F(info->b6),
                                     feats, dim, feats_out, dim, nullptr, nullptr, 0, rows, dim, x.kp_hid, info->w6_rows, 0, 0, status,
                                     stream));
     }
+    // every other path -- the fused node_mlp (its one launch casts the hidden activation), update_feats = False (the edge pass is the
+    // last launch), K = 0 -- publishes behind its last launch
+    if (publish && !published) EGNN_TRY(egnn_status_publish(status, opts->status_pub, opts->status_words, opts->status_seq, stream));
     return EGNN_OK;
 }

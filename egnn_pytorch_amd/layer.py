@@ -254,8 +254,9 @@ class EGNN(nn.Module):
     def forward(self, feats, coors, edges=None, mask=None, adj_mat=None):
         out = None
         try:
-            out = self._call(feats, coors, edges, mask, adj_mat, None)[:2]
-            _ops.range_check_after_forward(feats.device)            # EGNN_RANGE_CHECK: sync (default) | deferred | off
+            with _ops.early_publish():                              # (the one-call C forward may publish the status words itself)
+                out = self._call(feats, coors, edges, mask, adj_mat, None)[:2]
+                _ops.range_check_after_forward(feats.device)        # EGNN_RANGE_CHECK: sync (default) | deferred | off
         except _abi.EGNNRangeError as err:
             if err.origin == "backward" or not _rerun_exact_ok(self, feats, coors, edges):
                 raise
@@ -492,6 +493,11 @@ class EGNN(nn.Module):
             opts.side_stream, opts.ev_fork, opts.ev_join = _ops.side_handles(dev)
         if img is not None:
             opts.nmf_img = img.data_ptr()
+        # the range check that follows this call (sync mode): the status words are published by the C entry, behind its last launch that
+        # can write them, and `_ops.range_check_after_forward` only waits for the sequence number requested here
+        pub = _ops.status_request(dev)
+        if pub is not None:
+            opts.status_pub, opts.status_words, opts.status_seq = pub
         rc = lib.egnn_layer_forward_opts_f32(desc, info, blob_dev.data_ptr(), feats.data_ptr(), coors.data_ptr(), _ops._ptr(edges), _ops._ptr(m8),
                                              _ops._ptr(a8), stride, b, n, k, cdim, node_out.data_ptr(), coors_out.data_ptr(), ws.data_ptr(),
                                              nbytes, _ops._status_ptr(dev), _ops._stream(), opts)
@@ -809,9 +815,10 @@ class EGNN_Network(nn.Module):
                                             any(torch.is_tensor(t) and t.is_floating_point() and t.requires_grad
                                                 for t in (feats, coors, edges)))
         try:
-            with torch.enable_grad() if grad else torch.no_grad():
-                out = self._forward(feats, coors, adj_mat, edges, mask, return_coor_changes)
-            _ops.range_check_after_forward(coors.device)            # once per network forward, not per layer
+            with _ops.early_publish(last=False) as early:           # (`_forward` sets `last` in front of the last layer)
+                with torch.enable_grad() if grad else torch.no_grad():
+                    out = self._forward(feats, coors, adj_mat, edges, mask, return_coor_changes, early)
+                _ops.range_check_after_forward(coors.device)        # once per network forward, not per layer
         except _abi.EGNNRangeError as err:
             if err.origin == "backward" or not _rerun_exact_ok(self, feats, coors, edges):
                 raise
@@ -820,7 +827,7 @@ class EGNN_Network(nn.Module):
                 out = self._forward(feats, coors, adj_mat, edges, mask, return_coor_changes)
         return out
 
-    def _forward(self, feats, coors, adj_mat, edges, mask, return_coor_changes):
+    def _forward(self, feats, coors, adj_mat, edges, mask, return_coor_changes, early=None):
         b = feats.shape[0]
         if self.token_emb is not None:
             feats = self.token_emb(feats)
@@ -856,9 +863,11 @@ class EGNN_Network(nn.Module):
             global_tokens = self.global_tokens[None].expand(b, -1, -1)
         coor_changes = [coors]
         order = None
-        for global_attn, egnn in self.layers:
+        for ind, (global_attn, egnn) in enumerate(self.layers):
             if global_attn is not None:
                 feats, global_tokens = global_attn(feats, global_tokens, mask=mask)           # :445-446
+            if early is not None:
+                early.last = ind == len(self.layers) - 1            # nothing behind the last layer writes the status word
             feats, coors, order = egnn._call(feats, coors, edges, mask, adj_mat, order)
             coor_changes.append(coors)
         if return_coor_changes:

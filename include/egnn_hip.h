@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define EGNN_ABI_VERSION 43
+#define EGNN_ABI_VERSION 44
 
 enum {
     EGNN_OK = 0,
@@ -679,7 +679,15 @@ int egnn_layer_forward_f32(const egnn_layer_desc* desc, const egnn_packed_info* 
  *                order_is_hint = 1, read as is (a stack of layers reuses the first layer's order: scheduling only, any permutation
  *                of each graph's nodes is valid);
  *   nmf_img:     the fused node_mlp weight image (egnn_node_mlp_fused_pack_f16) kept by the caller across calls; NULL: re-derived
- *                from the blob into the workspace at every call. */
+ *                from the blob into the workspace at every call;
+ *   status_pub / status_words / status_seq (ABI 44): with status_pub set, this call hands the range status to the host itself --
+ *                egnn_status_publish(status, status_pub, status_words, status_seq, stream): status_words (1 .. 8) words starting at
+ *                `status` (required then) into the pinned words status_pub[0 .. status_words), then status_seq into
+ *                status_pub[status_words] -- directly behind the LAST launch of the call that can write `status`, not behind the call.
+ *                Where node_mlp is two GEMMs that is in front of the second one (it packs no fp16 image and splits no columns, so it
+ *                has no cast site that could raise a bit): a host that spins on status_seq sees the words while that GEMM still runs
+ *                and has the next call enqueued before the device runs dry.  Every other path publishes behind its last launch.
+ *                The words are final for this call either way; the outputs are complete only in `stream`'s order, as always. */
 typedef struct egnn_forward_opts {
     void* side_stream;
     void* ev_fork;
@@ -687,6 +695,9 @@ typedef struct egnn_forward_opts {
     int32_t* order;
     const void* nmf_img;
     int32_t order_is_hint;
+    int32_t status_words;
+    int32_t* status_pub;
+    int32_t status_seq;
     int32_t reserved;
 } egnn_forward_opts;
 

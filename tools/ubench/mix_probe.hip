@@ -6,6 +6,8 @@
 #include "../../egnn_pytorch_amd/csrc/linear_hl.hip"
 
 int egnn_edge_fused_generic_c(const egnn_edge_args*, void*) { return EGNN_E_UNSUPPORTED; }   // (not built into the probe)
+int egnn_edge_fused_c3_drop(const egnn_edge_args*, void*) { return EGNN_E_UNSUPPORTED; }
+int egnn_edge_pw_launch(const egnn_edge_args*, void*) { return EGNN_E_UNSUPPORTED; }
 
 namespace {
 
@@ -63,7 +65,7 @@ extern "C" int egnn_mix_probe(const egnn_edge_args* ea, const void* A_hi, const 
     const int n_gemm = (which & 2) ? g.ntm * g.ntn : 0;
     const int mx = n_edge > n_gemm ? n_edge : n_gemm;
     const int nblk = mode == 0 ? ((mx + 7) / 8) * 16 : n_edge + n_gemm;
-    const size_t lds_edge = (size_t)256 * 64 + sizeof(float) * ((size_t)SLOTS_PER_ROUND * XLD + (size_t)G * NCH) + (size_t)256 * 16;
+    const size_t lds_edge = (size_t)256 * 64 + sizeof(float) * ((size_t)SLOTS_PER_ROUND * XLD + (size_t)G * nch_of(1)) + (size_t)256 * 16;
     const size_t lds_gemm = (size_t)Cfg<6>::STAGES * (2 * 128 + 2 * 128) * ROWB;
     const size_t lds = lds_edge > lds_gemm ? lds_edge : lds_gemm;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mix_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
