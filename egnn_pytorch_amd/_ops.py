@@ -385,6 +385,35 @@ def knn_select_stream(coors, mask, adj_mat, k, out=None):
     return _knn_select(coors, mask, adj_mat, k, out, "egnn_knn_select_stream")
 
 
+KNN_GRID_KMAX = 128           # the K limit of egnn_knn_select_grid_f32 (csrc/knn_grid.hip: KG_KMAX)
+
+
+def knn_grid_workspace(b, n, k, device):
+    """the workspace of `knn_select_grid` for (B, N, K): egnn_knn_grid_workspace_bytes bytes, allocated on the current stream"""
+    return empty(_abi.load().egnn_knn_grid_workspace_bytes(b, n, k), dtype=torch.uint8, device=device)
+
+
+def knn_select_grid(coors, mask, k, out=None, ws=None):
+    """knn_select on the cell-grid kernels (egnn_knn_select_grid_f32): fp32 coordinates, coor_dim == 3, no adjacency, K <= 128; the
+    same outputs bit for bit at a cost per row bounded by its neighbourhood, not by N.  ws: the workspace (`knn_grid_workspace`), allocated
+    here on the current stream when None -- a caller that runs this on a side stream allocates `out` and `ws` on its launch stream."""
+    b, n, cdim = coors.shape
+    if coors.dtype != torch.float32:
+        raise TypeError(f"knn_select_grid takes float32 coordinates (got {coors.dtype})")
+    if out is not None:
+        idx, rank = out
+    else:
+        idx = empty(b, n, k, dtype=torch.int32, device=coors.device)
+        rank = empty(b, n, k, dtype=torch.float32, device=coors.device)
+    m8 = _u8(mask)
+    if ws is None:
+        ws = knn_grid_workspace(b, n, k, coors.device)
+    with _timed("knn_select_grid"):
+        rc = _abi.load().egnn_knn_select_grid_f32(_ptr(coors), _ptr(m8), b, n, k, cdim, _ptr(idx), _ptr(rank), _ptr(ws), ws.numel(), _stream())
+    _abi.check(rc, "egnn_knn_select_grid_f32")
+    return idx, rank
+
+
 def _knn_select(coors, mask, adj_mat, k, out, entry):
     b, n, cdim = coors.shape
     f64 = coors.dtype == torch.float64

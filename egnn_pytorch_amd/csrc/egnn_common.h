@@ -303,6 +303,11 @@ int egnn_pack_rows_launch(const float* X, int64_t ldx, const float* m_i, const f
                           void* hi, void* lo, int Kp, void* raw_hi, void* raw_lo, int raw_Kp, int64_t rows, int dim, int m_dim,
                           int32_t* status, void* stream);
 
+// internal (knn_stream.hip): the streaming selection (C == 3, no adjacency) for the rows with rowflag[b N + i] != 0 only -- the rows the
+// cell-grid selection (knn_grid.hip) hands over; the other rows of idx_out / rank_out are left as they are
+int egnn_knn_stream_flagged_f32(const float* coors, const uint8_t* mask, int B, int N, int K, const uint8_t* rowflag, int32_t* idx_out,
+                                float* rank_out, void* stream);
+
 static inline int egnn_launch_status() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? EGNN_OK : (int)e;

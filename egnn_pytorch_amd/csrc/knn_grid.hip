@@ -1,0 +1,464 @@
+// Cell-grid k-NN selection (gfx950): fp32 coordinates, coor_dim == 3, no adjacency, optional mask.  Outputs bit-identical to the
+// streaming selection (knn_stream.hip) for every input with finite coordinates, at a cost per row that is bounded by the row's
+// neighbourhood instead of N.  Distances are egnn_sqdist and keys egnn_knn_rank / egnn_rank_key (egnn_common.h), like every
+// other selection kernel: equality is by construction.
+//
+// Per graph (no host read-back anywhere; every launch is unconditional, so the sequence can be captured):
+//   bbox    partial sums over fixed chunks of the nodes: bounding box, first and second moments, valid count, non-finite flag
+//   setup   one workgroup: the robust box [max(min, mean - 4 sd), min(max, mean + 4 sd)] per axis, the cell edge h for a mean
+//           occupancy of KG_OCC nodes per cell (axes thinner than h get one cell: h is then chosen over the remaining axes),
+//           at most KG_GMAX cells per axis; nodes outside the box are clamped into its border cells.  Clears the cell counters.
+//   count   cell id per valid node, integer atomic count per cell
+//   scan    one workgroup: cell starts; a graph whose fullest cell holds more than max(4096, N / 64) nodes is flagged
+//   place   (x, y, z, index) of every valid node into its cell's range (an integer cursor per cell: the order inside a cell
+//           varies from run to run, the outputs do not depend on it -- the search selects by the unique composite (key, index))
+//   search  one wave per valid query, queries in cell order.  The cube of Chebyshev radius 1 around the query's cell first, then the
+//           shells r = 2, 3, ...; a cube or shell is a list of x-runs of cells, i.e. of contiguous ranges of the sorted nodes, whose
+//           bounds 64 lanes fetch at once.  The K best composites are kept in LDS: a candidate below the current K-th best is
+//           appended, and a full buffer is ranked by counting, which leaves the K best sorted.
+//   finish  rows the grid does not answer are flagged and finished by the streaming kernel (knn_stream.hip, its flagged
+//           instantiation: workgroups without a flagged row return at once).  Flagged: every row of a graph with a non-finite
+//           coordinate, an extent beyond 1e18, fewer than K valid nodes or an overfull cell; a valid row whose K-th best d^2 is
+//           >= 1e5 while the graph has masked nodes (the reference interleaves them at exactly 1e5).  Masked rows of other graphs
+//           are written here: the first K indices at rank 1e5.
+//
+// The stop rule and its margin.  Cells are c = trunc(fl(fl(x - x0) * inv_h)) per axis, clamped to [0, G - 1], G <= 1024.  Both
+// roundings are relative (2^-24 each; a denormal difference is exact), so with u = (x - x0) * inv_h exact, |fl - u| <= 2^-23 u
+// <= 2^-12 inside the box, and a node in cell c has u in [c - 2^-12, c + 1 + 2^-12); a clamped node lies beyond its border cell, on
+// the far side.  After ring r every unvisited node differs from the query's cell by >= r + 1 on some axis, so |u_j - u_q| > r - 2^-11
+// there and the true squared distance is >= (r h')^2 (1 - 2^-10), h' = 1 / inv_h.  egnn_sqdist computes fl(fl(fl(dx)^2 + fl(dy)^2)
+// + fl(dz)^2) with dx = fl(xi - xj): five roundings on non-negative terms, relative error < 2^-21 (h >= 1e-15 keeps (r h)^2 far
+// above the denormal range; extents <= 1e18 keep every term finite).  The bound itself -- fl(fl(r h) fl(r h)) with h = fl(1 / inv_h)
+// -- is off by < 2^-21.  Together < 2^-9; the kernel uses (r h)^2 (1 - 2^-8).  A row stops once its K-th best d^2 is STRICTLY below
+// that: every unvisited node then has a computed d^2 above the K-th key, so none can equal it and the lowest-index tie policy is
+// decided among visited nodes only.  A row that never stops has visited every cell.
+#include "egnn_common.h"
+
+namespace {
+
+constexpr int KG_KMAX = 128;                 // K limit (the candidate buffer of a wave: 2 K entries)
+constexpr int KG_OCC = 16;                   // target mean occupancy of a cell
+constexpr int KG_GMAX = 1024;                // cells per axis
+constexpr int KG_THREADS = 256;
+constexpr int KG_SLOTS = 16;                 // query slots per search workgroup (4 per wave)
+constexpr int KG_PARTS = 64;                 // chunks of the bbox pass
+constexpr int KG_PW = 16;                    // doubles per chunk record
+constexpr int KG_CAP = 2 * KG_KMAX;          // candidate buffer entries per wave
+
+struct KgHdr {
+    float x0, y0, z0, inv_h, h;
+    int gx, gy, gz, nvalid, flag;
+    int pad[6];
+};
+
+__host__ __device__ inline int kg_cell_cap(int N) { return N / 4 + 64; }
+
+struct KgLayout { size_t hdr, part, flag, cell, cnt, start, sorted, total; };
+
+inline KgLayout kg_layout(int B, int N)
+{
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    KgLayout L;
+    size_t o = 0;
+    L.hdr = o; o = up(o + (size_t)B * sizeof(KgHdr));
+    L.part = o; o = up(o + (size_t)B * KG_PARTS * KG_PW * sizeof(double));
+    L.flag = o; o = up(o + (size_t)B * N);
+    L.cell = o; o = up(o + (size_t)B * N * 4);
+    L.cnt = o; o = up(o + (size_t)B * kg_cell_cap(N) * 4);
+    L.start = o; o = up(o + (size_t)B * (kg_cell_cap(N) + 1) * 4);
+    L.sorted = o; o = up(o + (size_t)B * N * 16);
+    L.total = o;
+    return L;
+}
+
+__device__ __forceinline__ void kg_wave_sync()
+{
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// ---- bbox: chunk p of graph b -> 16 doubles: sum x y z, sum x^2 y^2 z^2, min x y z, max x y z, valid count, non-finite count
+__global__ __launch_bounds__(KG_THREADS) void kg_bbox_kernel(const float* __restrict__ coors, const uint8_t* __restrict__ mask, int N,
+                                                             int P, double* __restrict__ part)
+{
+    __shared__ double sd[6][KG_THREADS];
+    __shared__ float sf[6][KG_THREADS];
+    __shared__ int si[2][KG_THREADS];
+    const int tid = threadIdx.x, b = blockIdx.y, p = blockIdx.x;
+    const int chunk = (N + P - 1) / P;
+    const int lo = p * chunk, hi = min(N, lo + chunk);
+    const float* cb = coors + (size_t)b * N * 3;
+    const uint8_t* mb = mask ? mask + (size_t)b * N : nullptr;
+    double s[6] = {0, 0, 0, 0, 0, 0};
+    float mn[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
+    float mx[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+    int cnt = 0, bad = 0;
+    for (int i = lo + tid; i < hi; i += KG_THREADS) {
+        if (mb && !mb[i]) continue;
+        ++cnt;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float v = cb[(size_t)i * 3 + a];
+            if (!(fabsf(v) < __builtin_inff())) { ++bad; continue; }
+            s[a] += (double)v;
+            s[3 + a] += (double)v * (double)v;
+            mn[a] = fminf(mn[a], v);
+            mx[a] = fmaxf(mx[a], v);
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 6; ++a) sd[a][tid] = s[a];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { sf[a][tid] = mn[a]; sf[3 + a][tid] = mx[a]; }
+    si[0][tid] = cnt;
+    si[1][tid] = bad;
+    __syncthreads();
+    for (int w = KG_THREADS / 2; w > 0; w >>= 1) {               // fixed tree: the same sums on every run
+        if (tid < w) {
+#pragma unroll
+            for (int a = 0; a < 6; ++a) sd[a][tid] += sd[a][tid + w];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                sf[a][tid] = fminf(sf[a][tid], sf[a][tid + w]);
+                sf[3 + a][tid] = fmaxf(sf[3 + a][tid], sf[3 + a][tid + w]);
+            }
+            si[0][tid] += si[0][tid + w];
+            si[1][tid] += si[1][tid + w];
+        }
+        __syncthreads();
+    }
+    if (tid < KG_PW) {
+        double v = 0.0;
+        if (tid < 6) v = sd[tid][0];
+        else if (tid < 12) v = (double)sf[tid - 6][0];
+        else if (tid == 12) v = (double)si[0][0];
+        else if (tid == 13) v = (double)si[1][0];
+        part[((size_t)b * KG_PARTS + p) * KG_PW + tid] = v;
+    }
+}
+
+// ---- setup: the graph's header from its chunk records (thread 0, fixed order), then the cell counters cleared
+__global__ __launch_bounds__(KG_THREADS) void kg_setup_kernel(const double* __restrict__ part, int N, int K, int P, KgHdr* __restrict__ hdr,
+                                                              int* __restrict__ cnt)
+{
+    __shared__ int ncells;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (tid == 0) {
+        const double* pb = part + (size_t)b * KG_PARTS * KG_PW;
+        double s[6] = {0, 0, 0, 0, 0, 0}, mn[3], mx[3], n = 0, bad = 0;
+        for (int a = 0; a < 3; ++a) { mn[a] = __builtin_inf(); mx[a] = -__builtin_inf(); }
+        for (int p = 0; p < P; ++p) {
+            const double* r = pb + (size_t)p * KG_PW;
+            for (int a = 0; a < 6; ++a) s[a] += r[a];
+            for (int a = 0; a < 3; ++a) { mn[a] = fmin(mn[a], r[6 + a]); mx[a] = fmax(mx[a], r[9 + a]); }
+            n += r[12];
+            bad += r[13];
+        }
+        KgHdr H;
+        H.x0 = H.y0 = H.z0 = 0.f;
+        H.inv_h = H.h = 1.f;
+        H.gx = H.gy = H.gz = 1;
+        H.nvalid = (int)n;
+        H.flag = (bad > 0 || n < (double)K || n < 1) ? 1 : 0;
+        for (int a = 0; a < 6; ++a) H.pad[a] = 0;
+        if (!H.flag) {
+            double lo[3], ext[3], emax = 0;
+            for (int a = 0; a < 3; ++a) {
+                const double mean = s[a] / n;
+                const double var = fmax(s[3 + a] / n - mean * mean, 0.0);
+                const double sdv = sqrt(var);
+                lo[a] = fmax(mn[a], mean - 4.0 * sdv);
+                const double hi = fmin(mx[a], mean + 4.0 * sdv);
+                ext[a] = fmax(hi - lo[a], 0.0);
+                emax = fmax(emax, ext[a]);
+                if (!(mx[a] - mn[a] <= 1e18)) H.flag = 1;
+            }
+            // the cell edge for KG_OCC nodes per cell over the axes that are at least one cell thick
+            bool act[3] = {ext[0] > 0, ext[1] > 0, ext[2] > 0};
+            double h = emax > 0 ? emax : 1.0;
+            for (int it = 0; it < 3; ++it) {
+                int d = 0;
+                double V = 1.0;
+                for (int a = 0; a < 3; ++a) if (act[a]) { ++d; V *= ext[a]; }
+                if (d == 0) break;
+                h = pow(V * (double)KG_OCC / n, 1.0 / (double)d);
+                bool changed = false;
+                for (int a = 0; a < 3; ++a) if (act[a] && ext[a] < h) { act[a] = false; changed = true; }
+                if (!changed) break;
+            }
+            h = fmax(h, emax / (double)(KG_GMAX - 1));
+            h = fmax(h, 1e-15);
+            int g[3];
+            const double cap = (double)kg_cell_cap(N);
+            for (int it = 0; it < 64; ++it) {
+                for (int a = 0; a < 3; ++a) g[a] = (int)fmin((double)KG_GMAX, floor(ext[a] / h) + 1.0);
+                if ((double)g[0] * (double)g[1] * (double)g[2] <= cap) break;
+                h *= 1.2599210498948732;
+            }
+            if ((double)g[0] * (double)g[1] * (double)g[2] > cap) g[0] = g[1] = g[2] = 1;
+            H.inv_h = (float)(1.0 / h);
+            H.h = (float)(1.0 / (double)H.inv_h);
+            H.x0 = (float)lo[0]; H.y0 = (float)lo[1]; H.z0 = (float)lo[2];
+            H.gx = g[0]; H.gy = g[1]; H.gz = g[2];
+        }
+        hdr[b] = H;
+        ncells = H.gx * H.gy * H.gz;
+    }
+    __syncthreads();
+    int* cb = cnt + (size_t)b * kg_cell_cap(N);
+    for (int c = tid; c < ncells; c += KG_THREADS) cb[c] = 0;
+}
+
+__device__ __forceinline__ int kg_axis_cell(float x, float x0, float inv_h, int g)
+{
+    const float t = (x - x0) * inv_h;
+    return t > 0.f ? (int)fminf(t, (float)(g - 1)) : 0;
+}
+
+// ---- count: the cell of every valid node (-1: masked), one integer atomic per node
+__global__ __launch_bounds__(KG_THREADS) void kg_count_kernel(const float* __restrict__ coors, const uint8_t* __restrict__ mask, int N,
+                                                              const KgHdr* __restrict__ hdr, int* __restrict__ cell_of, int* __restrict__ cnt)
+{
+    const int b = blockIdx.y, i = blockIdx.x * KG_THREADS + threadIdx.x;
+    const KgHdr H = hdr[b];
+    if (H.flag || i >= N) return;
+    int c = -1;
+    if (!mask || mask[(size_t)b * N + i]) {
+        const float* p = coors + ((size_t)b * N + i) * 3;
+        const int cx = kg_axis_cell(p[0], H.x0, H.inv_h, H.gx), cy = kg_axis_cell(p[1], H.y0, H.inv_h, H.gy),
+                  cz = kg_axis_cell(p[2], H.z0, H.inv_h, H.gz);
+        c = (cz * H.gy + cy) * H.gx + cx;
+        atomicAdd(&cnt[(size_t)b * kg_cell_cap(N) + c], 1);
+    }
+    cell_of[(size_t)b * N + i] = c;
+}
+
+// ---- scan: cell starts (exclusive prefix sums of the counts), the fullest cell against the fallback limit
+__global__ __launch_bounds__(1024) void kg_scan_kernel(int N, KgHdr* __restrict__ hdr, const int* __restrict__ cnt, int* __restrict__ start)
+{
+    __shared__ int sums[1024];
+    __shared__ int smax;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (hdr[b].flag) return;                                              // (uniform: written by an earlier launch)
+    const int nc = hdr[b].gx * hdr[b].gy * hdr[b].gz;
+    const int* cb = cnt + (size_t)b * kg_cell_cap(N);
+    int* sb = start + (size_t)b * (kg_cell_cap(N) + 1);
+    const int per = (nc + 1023) / 1024;
+    const int lo = min(nc, tid * per), hi = min(nc, lo + per);
+    int sum = 0, m = 0;
+    for (int c = lo; c < hi; ++c) { sum += cb[c]; m = max(m, cb[c]); }
+    sums[tid] = sum;
+    if (tid == 0) smax = 0;
+    __syncthreads();
+    atomicMax(&smax, m);
+    for (int w = 1; w < 1024; w <<= 1) {
+        const int v = tid >= w ? sums[tid - w] : 0;
+        __syncthreads();
+        sums[tid] += v;
+        __syncthreads();
+    }
+    int run = sums[tid] - sum;
+    for (int c = lo; c < hi; ++c) { sb[c] = run; run += cb[c]; }
+    if (tid == 1023) sb[nc] = sums[1023];
+    if (tid == 0 && smax > max(4096, N / 64)) hdr[b].flag = 1;
+}
+
+// ---- place: (x, y, z, index) into the cell's range; the counter of a cell doubles as its cursor (it counts back down to 0)
+__global__ __launch_bounds__(KG_THREADS) void kg_place_kernel(const float* __restrict__ coors, int N, const KgHdr* __restrict__ hdr,
+                                                              const int* __restrict__ cell_of, int* __restrict__ cnt,
+                                                              const int* __restrict__ start, float4* __restrict__ sorted)
+{
+    const int b = blockIdx.y, i = blockIdx.x * KG_THREADS + threadIdx.x;
+    if (hdr[b].flag || i >= N) return;
+    const int c = cell_of[(size_t)b * N + i];
+    if (c < 0) return;
+    const int pos = start[(size_t)b * (kg_cell_cap(N) + 1) + c] + atomicSub(&cnt[(size_t)b * kg_cell_cap(N) + c], 1) - 1;
+    const float* p = coors + ((size_t)b * N + i) * 3;
+    if (pos >= 0 && pos < N) sorted[(size_t)b * N + pos] = make_float4(p[0], p[1], p[2], __int_as_float(i));
+}
+
+// the cnt entries of buf ranked by counting: the min(cnt, K) smallest end up sorted in buf[0 ..), tau = the K-th once there are K
+__device__ __forceinline__ void kg_compact(uint64_t* buf, uint64_t* tmp, int& cnt, uint64_t& tau, int K, int lane)
+{
+    kg_wave_sync();
+    for (int t = lane; t < cnt; t += 64) {
+        const uint64_t c = buf[t];
+        int rnk = 0;
+        for (int u = 0; u < cnt; ++u) rnk += buf[u] < c ? 1 : 0;
+        if (rnk < K) tmp[rnk] = c;
+    }
+    kg_wave_sync();
+    const int n = cnt < K ? cnt : K;
+    for (int t = lane; t < n; t += 64) buf[t] = tmp[t];
+    kg_wave_sync();
+    cnt = n;
+    if (n == K) tau = buf[K - 1];
+}
+
+__global__ __launch_bounds__(KG_THREADS) void kg_search_kernel(const uint8_t* __restrict__ mask, const KgHdr* __restrict__ hdr,
+                                                               const int* __restrict__ cell_of, const int* __restrict__ start,
+                                                               const float4* __restrict__ sorted, uint8_t* __restrict__ rowflag, int N, int K,
+                                                               int32_t* __restrict__ idx_out, float* __restrict__ rank_out)
+{
+    __shared__ uint64_t sbuf[KG_THREADS / 64][KG_CAP];
+    __shared__ uint64_t stmp[KG_THREADS / 64][KG_KMAX];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = blockIdx.y, base = blockIdx.x * KG_SLOTS;
+    const KgHdr H = hdr[b];
+    uint8_t* fb = rowflag + (size_t)b * N;
+    if (H.flag) {                                                         // the whole graph goes to the streaming kernel
+        if (tid < KG_SLOTS && base + tid < N) fb[base + tid] = 1;
+        return;
+    }
+    if (mask) {                                                           // masked rows: the first K indices at rank 1e5
+        const uint8_t* mb = mask + (size_t)b * N;
+        for (int o = tid; o < KG_SLOTS * K; o += KG_THREADS) {
+            const int rr = o / K, k = o - rr * K, i = base + rr;
+            if (i < N && !mb[i]) {
+                const size_t ob = ((size_t)b * N + i) * K;
+                idx_out[ob + k] = k;
+                rank_out[ob + k] = 1e5f;
+                if (k == 0) fb[i] = 0;
+            }
+        }
+    }
+    uint64_t* buf = sbuf[wave];
+    uint64_t* tmp = stmp[wave];
+    const int* st = start + (size_t)b * (kg_cell_cap(N) + 1);
+    const float4* srt = sorted + (size_t)b * N;
+    const int cap = K + 64 > 2 * K ? (K + 64 + 63) / 64 * 64 : 2 * K;      // (<= KG_CAP: K <= KG_KMAX)
+    const int qend = min(base + KG_SLOTS, H.nvalid);
+    for (int q = base + wave; q < qend; q += KG_THREADS / 64) {
+        const float4 me = srt[q];
+        const int i = __builtin_amdgcn_readfirstlane(__float_as_int(me.w));
+        const int c = __builtin_amdgcn_readfirstlane(cell_of[(size_t)b * N + i]);
+        const int cx = c % H.gx, cy = (c / H.gx) % H.gy, cz = c / (H.gx * H.gy);
+        const int rmax = max(max(max(cx, H.gx - 1 - cx), max(cy, H.gy - 1 - cy)), max(max(cz, H.gz - 1 - cz), 1));
+        int cnt = 0;
+        bool dirty = false;
+        uint64_t tau = ~0ull;
+        for (int r = 1;; ++r) {
+            const int nrow = 2 * r + 1;
+            const int nouter = nrow * nrow;
+            const int nseg = r == 1 ? 9 : nouter + (nrow - 2) * (nrow - 2);
+            for (int sb = 0; sb < nseg; sb += 64) {
+                // 64 x-runs of cells at once: the bounds of their ranges in the sorted nodes
+                const int sg = sb + lane;
+                int s = 0, e = 0;
+                if (sg < nseg) {
+                    int dz, dy, xa, xb;
+                    if (sg < nouter) {
+                        dz = sg / nrow - r;
+                        dy = sg % nrow - r;
+                        const bool face = r == 1 || dz == r || dz == -r || dy == r || dy == -r;
+                        xa = cx - r;
+                        xb = face ? cx + r : cx - r;
+                    } else {
+                        const int t = sg - nouter, w = nrow - 2;
+                        dz = t / w - (r - 1);
+                        dy = t % w - (r - 1);
+                        xa = xb = cx + r;
+                    }
+                    const int z = cz + dz, y = cy + dy;
+                    xa = max(xa, 0);
+                    xb = min(xb, H.gx - 1);
+                    if (z >= 0 && z < H.gz && y >= 0 && y < H.gy && xa <= xb) {
+                        const int row = (z * H.gy + y) * H.gx;
+                        s = st[row + xa];
+                        e = st[row + xb + 1];
+                    }
+                }
+                const int nl = min(64, nseg - sb);
+                for (int t = 0; t < nl; ++t) {
+                    const int s_t = __builtin_amdgcn_readlane(s, t), e_t = min(__builtin_amdgcn_readlane(e, t), H.nvalid);
+                    for (int p0 = s_t; p0 < e_t; p0 += 64) {
+                        if (cnt + 64 > cap) kg_compact(buf, tmp, cnt, tau, K, lane);
+                        const int p = p0 + lane;
+                        bool pass = false;
+                        uint64_t comp = 0;
+                        if (p < e_t) {
+                            const float4 cj = srt[p];
+                            float dx, dy, dz;
+                            const float d = egnn_sqdist(me.x, me.y, me.z, cj.x, cj.y, cj.z, dx, dy, dz);
+                            const int j = __float_as_int(cj.w);
+                            const uint32_t key = egnn_rank_key(egnn_knn_rank<float>(d, true, true, nullptr, i, j));
+                            comp = ((uint64_t)key << 32) | (uint32_t)j;
+                            pass = comp < tau;
+                        }
+                        const uint64_t bal = __ballot(pass);
+                        if (pass) {
+                            const int below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
+                            buf[cnt + below] = comp;
+                        }
+                        const int add = __builtin_popcountll(bal);
+                        cnt += add;
+                        dirty = dirty || add > 0;
+                    }
+                }
+            }
+            if (cnt >= K) {
+                if (dirty) { kg_compact(buf, tmp, cnt, tau, K, lane); dirty = false; }
+                const float d2k = egnn_rank_from_key((uint32_t)(tau >> 32));
+                const float rh = (float)r * H.h;
+                if (d2k < rh * rh * (1.f - 0.00390625f)) break;
+            }
+            if (r >= rmax) break;
+        }
+        // (every cell visited or the rule above met; nvalid >= K, so K entries, sorted)
+        kg_wave_sync();
+        const float d2k = egnn_rank_from_key((uint32_t)(tau >> 32));
+        const bool hand_over = cnt < K || (d2k >= 1e5f && H.nvalid < N);
+        if (!hand_over) {
+            const size_t ob = ((size_t)b * N + i) * K;
+            for (int t = lane; t < K; t += 64) {
+                const uint64_t cc = buf[t];
+                idx_out[ob + t] = (int32_t)(uint32_t)cc;
+                rank_out[ob + t] = egnn_rank_from_key((uint32_t)(cc >> 32));
+            }
+        }
+        if (lane == 0) fb[i] = hand_over ? 1 : 0;
+        kg_wave_sync();
+    }
+}
+
+}  // namespace
+
+extern "C" size_t egnn_knn_grid_workspace_bytes(int B, int N, int K)
+{
+    (void)K;
+    if (B <= 0 || N <= 0) return 256;
+    return kg_layout(B, N).total;
+}
+
+extern "C" int egnn_knn_select_grid_f32(const float* coors, const uint8_t* mask, int B, int N, int K, int coor_dim, int32_t* idx_out,
+                                        float* rank_out, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!coors || !idx_out || !rank_out || !workspace) return EGNN_E_NULLPTR;
+    if (B <= 0 || N <= 0 || K <= 0 || K > N) return EGNN_E_SHAPE;
+    if (coor_dim != 3 || K > KG_KMAX || B > 65535) return EGNN_E_UNSUPPORTED;
+    const KgLayout L = kg_layout(B, N);
+    if (workspace_bytes < L.total) return EGNN_E_SHAPE;
+    if (reinterpret_cast<uintptr_t>(workspace) % 16) return EGNN_E_ALIGN;
+    char* ws = static_cast<char*>(workspace);
+    KgHdr* hdr = reinterpret_cast<KgHdr*>(ws + L.hdr);
+    double* part = reinterpret_cast<double*>(ws + L.part);
+    uint8_t* rowflag = reinterpret_cast<uint8_t*>(ws + L.flag);
+    int* cell_of = reinterpret_cast<int*>(ws + L.cell);
+    int* cnt = reinterpret_cast<int*>(ws + L.cnt);
+    int* start = reinterpret_cast<int*>(ws + L.start);
+    float4* sorted = reinterpret_cast<float4*>(ws + L.sorted);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int P = min(KG_PARTS, (N + 4095) / 4096);
+    const dim3 nodes((unsigned)((N + KG_THREADS - 1) / KG_THREADS), (unsigned)B);
+    hipLaunchKernelGGL(kg_bbox_kernel, dim3((unsigned)P, (unsigned)B), dim3(KG_THREADS), 0, st, coors, mask, N, P, part);
+    hipLaunchKernelGGL(kg_setup_kernel, dim3((unsigned)B), dim3(KG_THREADS), 0, st, part, N, K, P, hdr, cnt);
+    hipLaunchKernelGGL(kg_count_kernel, nodes, dim3(KG_THREADS), 0, st, coors, mask, N, hdr, cell_of, cnt);
+    hipLaunchKernelGGL(kg_scan_kernel, dim3((unsigned)B), dim3(1024), 0, st, N, hdr, cnt, start);
+    hipLaunchKernelGGL(kg_place_kernel, nodes, dim3(KG_THREADS), 0, st, coors, N, hdr, cell_of, cnt, start, sorted);
+    hipLaunchKernelGGL(kg_search_kernel, dim3((unsigned)((N + KG_SLOTS - 1) / KG_SLOTS), (unsigned)B), dim3(KG_THREADS), 0, st, mask, hdr,
+                       cell_of, start, sorted, rowflag, N, K, idx_out, rank_out);
+    int rc = egnn_launch_status();
+    if (rc != EGNN_OK) return rc;
+    return egnn_knn_stream_flagged_f32(coors, mask, B, N, K, rowflag, idx_out, rank_out, stream);
+}

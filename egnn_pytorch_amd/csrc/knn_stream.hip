@@ -29,10 +29,12 @@ template <> struct KsKey<float> { typedef uint32_t type; static constexpr int V 
 template <> struct KsKey<double> { typedef uint64_t type; static constexpr int V = 4; };
 
 // CDM: 3 = egnn_sqdist (float, C == 3), 8 = egnn_sqdist_n (float, C <= 8), 0 = egnn_sqdist_any (float C > 8, every double C)
-template <typename T, int CDM>
+// FL: only the rows with rowflag[b N + i] != 0 are selected and written (the rows the cell-grid selection hands over, knn_grid.hip); a
+// workgroup without such a row returns at once.
+template <typename T, int CDM, bool FL = false>
 __global__ __launch_bounds__(KS_THREADS) void knn_select_stream_kernel(
     const T* __restrict__ coors, const uint8_t* __restrict__ mask, const uint8_t* __restrict__ adj, int64_t adj_bstride,
-    int N, int K, int C, int R, int IBP, int32_t* __restrict__ idx_out, T* __restrict__ rank_out)
+    int N, int K, int C, int R, int IBP, int32_t* __restrict__ idx_out, T* __restrict__ rank_out, const uint8_t* __restrict__ rowflag)
 {
     typedef typename KsKey<T>::type key_t;
     constexpr int KB = 8 * (int)sizeof(key_t);           // key bits
@@ -59,6 +61,16 @@ __global__ __launch_bounds__(KS_THREADS) void knn_select_stream_kernel(
     const T* cb = coors + (size_t)b * N * C;
     const uint8_t* mb = mask ? mask + (size_t)b * N : nullptr;
     const bool mi = (i < N && mb) ? mb[i] != 0 : true;
+    bool fl = true;
+    if constexpr (FL) {
+        bool any = false;
+        for (int rr = 0; rr < R; ++rr) {
+            const int ir = blockIdx.x * R + rr;
+            any = any || (ir < N && rowflag[(size_t)b * N + ir] != 0);
+        }
+        if (!any) return;                                                // (the same for every thread of the workgroup)
+        fl = i < N && rowflag[(size_t)b * N + i] != 0;
+    }
     const uint8_t* adjrow = (adj && i < N) ? adj + (size_t)b * adj_bstride + (size_t)i * N : nullptr;
 
     for (int o = tid; o < R * KS_HSTRIDE; o += KS_THREADS) hist[o] = 0;
@@ -68,7 +80,7 @@ __global__ __launch_bounds__(KS_THREADS) void knn_select_stream_kernel(
         lvl[r] = 0;
         need[r] = K;
         cnt[r] = 0;
-        state[r] = (i >= N || (!mi && !adjrow)) ? 2 : 0;
+        state[r] = (i >= N || !fl || (!mi && !adjrow)) ? 2 : 0;
     }
     if (tid == 0) *active = 0;
     if constexpr (CDM == 0) {
@@ -80,7 +92,7 @@ __global__ __launch_bounds__(KS_THREADS) void knn_select_stream_kernel(
     __syncthreads();
     if (s == 0 && state[r] == 0) atomicAdd(active, 1);
     // a masked row without an adjacency: every pair is masked, the ranking row is all 1e5 and the selection the first K indices
-    if (i < N && !mi && !adjrow) {
+    if (i < N && fl && !mi && !adjrow) {
         const size_t ob = ((size_t)b * N + i) * K;
         for (int k = s; k < K; k += S) { idx_out[ob + k] = k; rank_out[ob + k] = (T)1e5; }
     }
@@ -197,7 +209,7 @@ __global__ __launch_bounds__(KS_THREADS) void knn_select_stream_kernel(
 
 template <typename T>
 int knn_stream_launch(const T* coors, const uint8_t* mask, const uint8_t* adj, int64_t adj_bstride, int B, int N, int K, int C,
-                      int32_t* idx_out, T* rank_out, void* stream)
+                      int32_t* idx_out, T* rank_out, void* stream, const uint8_t* rowflag = nullptr)
 {
     if (!coors || !idx_out || !rank_out) return EGNN_E_NULLPTR;
     if (B <= 0 || N <= 0 || K <= 0) return EGNN_E_SHAPE;
@@ -218,6 +230,10 @@ int knn_stream_launch(const T* coors, const uint8_t* mask, const uint8_t* adj, i
     if constexpr (sizeof(T) == 4) {
         if (C == 3) kern = knn_select_stream_kernel<T, 3>;
         else if (C <= 8) kern = knn_select_stream_kernel<T, 8>;
+        if (rowflag) {
+            if (C != 3) return EGNN_E_UNSUPPORTED;
+            kern = knn_select_stream_kernel<T, 3, true>;
+        }
     }
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -225,11 +241,18 @@ int knn_stream_launch(const T* coors, const uint8_t* mask, const uint8_t* adj, i
     }
     const dim3 grid((unsigned)((N + R - 1) / R), (unsigned)B);
     hipLaunchKernelGGL(kern, grid, dim3(KS_THREADS), lds, static_cast<hipStream_t>(stream), coors, mask, adj, adj_bstride, N, K, C, R,
-                       IBP, idx_out, rank_out);
+                       IBP, idx_out, rank_out, rowflag);
     return egnn_launch_status();
 }
 
 }  // namespace
+
+int egnn_knn_stream_flagged_f32(const float* coors, const uint8_t* mask, int B, int N, int K, const uint8_t* rowflag, int32_t* idx_out,
+                                float* rank_out, void* stream)
+{
+    if (!rowflag) return EGNN_E_NULLPTR;
+    return knn_stream_launch<float>(coors, mask, nullptr, 0, B, N, K, 3, idx_out, rank_out, stream, rowflag);
+}
 
 extern "C" int egnn_knn_select_stream_f32(const float* coors, const uint8_t* mask, const uint8_t* adj, int64_t adj_batch_stride, int B,
                                           int N, int K, int coor_dim, int32_t* idx_out, float* rank_out, void* stream)

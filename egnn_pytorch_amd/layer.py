@@ -40,6 +40,10 @@ _DENSE_PW = os.environ.get("EGNN_DENSE_PW", "1") != "0"            # dense layer
 # C) instead of a dozen Python-side launches: ~200 us of host time per forward become a few tens.  Only with every scheduling switch
 # above at its default -- the C entry implements the default policy -- and never while per-kernel timing is on.
 _C_FORWARD = os.environ.get("EGNN_C_FORWARD", "1") != "0"
+# k-NN graphs of at least this many nodes select their neighbours on the cell grid (csrc/knn_grid.hip: fp32, 3-D, no adjacency,
+# K <= 128; the same neighbour list bit for bit) instead of the all-pairs kernels.  The default moves no graph up to 65 536 nodes
+# (DESIGN.md section 4.1 has the measurements).
+_KNN_GRID_MIN_N = int(os.environ.get("EGNN_KNN_GRID_MIN_N", "65537"))
 
 
 def _default_policy():
@@ -386,6 +390,11 @@ class EGNN(nn.Module):
         return (_SLOT_PREP and _DENSE_PW and b * n >= 8192 and n % 32 == 0 and 32 <= n <= 4096 and cdim == 3 and self.m_dim <= 16
                 and self.edge_dim == 0 and self.fourier_features == 0 and not self.dropout_active() and b * n * n * 16 <= (1 << 28))
 
+    def _use_grid(self, coors, adj_mat, k):
+        """the neighbour selection of this call on the cell grid (egnn_knn_select_grid_f32) rather than the all-pairs kernels"""
+        return (coors.dtype == torch.float32 and coors.shape[-1] == 3 and adj_mat is None and 0 < k <= _ops.KNN_GRID_KMAX
+                and coors.shape[1] >= _KNN_GRID_MIN_N)
+
     def _proj_row_mask(self, mask8, b, n, k, cdim, w, want_u, drop):
         """The projection GEMM's row mask (M-tiles of padded nodes are not computed), or None.  Only where the rows of padded nodes are
         read by masked-out edges alone: a k-NN layer whose edge pass is the wave-per-node kernel.  Not under autograd or dropout: the
@@ -396,7 +405,8 @@ class EGNN(nn.Module):
         return mask8.view(-1)
 
     def _select_outputs(self, coors, adj_mat, order_hint, k):
-        """The four outputs of the k-NN selection (idx, rank, order or None, slots or None), allocated on the LAUNCH stream: the launch
+        """The four outputs of the k-NN selection (idx, rank, order or None, slots or None) and the workspace of the cell-grid selection
+        (None where the all-pairs kernels select: `_use_grid`), allocated on the LAUNCH stream: the launch
         stream waits for the side stream before it reads them, so when they are freed every use is ordered before the launch stream's
         later work and the allocator may reuse the blocks at once.  (Allocated inside the fork they belonged to the side stream's pool
         and needed record_stream(): four calls per forward and frees deferred to events.)  order is the taken hint, if any."""
@@ -404,7 +414,8 @@ class EGNN(nn.Module):
         dev = coors.device
         return (_ops.empty(b, n, k, dtype=torch.int32, device=dev), _ops.empty(b, n, k, dtype=torch.float32, device=dev),
                 self._order(coors, adj_mat, order_hint),
-                _ops.empty(b * n * k, 4, dtype=torch.int32, device=dev) if (_SLOT_PREP and coors.shape[-1] == 3) else None)
+                _ops.empty(b * n * k, 4, dtype=torch.int32, device=dev) if (_SLOT_PREP and coors.shape[-1] == 3) else None,
+                _ops.knn_grid_workspace(b, n, k, dev) if self._use_grid(coors, adj_mat, k) else None)
 
     def _select_neighbors(self, coors, mask, adj_mat, order_hint, k, valid_radius, outs, fork=None):
         """(idx, rank, order, slots) of egnn_pytorch.py:230-260 for fp32 coordinates on the device, K > 0: the K nearest neighbours, the
@@ -414,12 +425,15 @@ class EGNN(nn.Module):
         result joins that stream first.  fork: an event of the launch stream -- recorded at the layer's entry, before its node-level
         launches -- the side stream waits for instead of the stream's tail, so the selection runs beside node_prep and the projection
         although it is enqueued behind them.  It reads only what existed at that event: coors, mask, adj_mat and `outs`."""
-        idx_o, rank_o, order_o, slots_o = outs
+        idx_o, rank_o, order_o, slots_o, grid_ws = outs
         mask8 = _ops._u8(mask)                                      # (a view: the caller made the mask contiguous before the fork)
 
         def select():
             # (the Morton order launched AHEAD of the selection was measured in round 6: +- 0.3 %, not kept)
-            idx_, rank_ = _ops.knn_select(coors, mask, adj_mat, k, out=(idx_o, rank_o))
+            if grid_ws is not None:
+                idx_, rank_ = _ops.knn_select_grid(coors, mask, k, out=(idx_o, rank_o), ws=grid_ws)
+            else:
+                idx_, rank_ = _ops.knn_select(coors, mask, adj_mat, k, out=(idx_o, rank_o))
             order_ = order_o if order_o is None or order_o is order_hint else _ops.spatial_order(coors, out=order_o, mask8=mask8)
             # the edge pass's setup as one coalesced record per slot instead of a chain of dependent loads
             slots_ = _ops.slot_prep(coors, mask8, idx_, rank_, order_, valid_radius, out=slots_o) if slots_o is not None else None
@@ -456,7 +470,7 @@ class EGNN(nn.Module):
         """The fp32 inference forward as one call of egnn_layer_forward_opts_f32 (include/egnn_hip.h; csrc/layer_api.hip mirrors
         `_forward_hip_impl` launch for launch, so the outputs are the same bits).  Returns `_forward_hip`'s tuple, or None when the call is
         outside what the C entry covers (edge look-up tables, wide shapes, the wave-per-node kernel on dense batches, another current
-        device): the Python launch sequence then runs it.  K is read after those checks, and a call with K = 0 goes to the Python launch
+        device, a graph whose neighbours the cell grid selects -- the C entry keeps its streaming selection): the Python launch sequence then runs it.  K is read after those checks, and a call with K = 0 goes to the Python launch
         sequence from here, with that K: the adjacency's maximum degree is read once per call."""
         b, n, dim = feats.shape
         cdim = coors.shape[-1]
@@ -464,7 +478,8 @@ class EGNN(nn.Module):
         dev = feats.device
         if (isinstance(edges, EdgeLookup) or cdim > 8 or self.m_dim > 64 or 2 * self.fourier_features + 1 + self.edge_dim > 16
                 or dev.index != torch.cuda.current_device() or (adj_mat is not None and adj_mat.dtype != torch.bool)
-                or (not use_nearest and self._dense_pw(b, n, cdim))):
+                or (not use_nearest and self._dense_pw(b, n, cdim))
+                or (use_nearest and self._use_grid(coors, adj_mat, self.num_nearest_neighbors))):
             return None
         st = self._c_state(dev)
         if st is None:

@@ -98,6 +98,23 @@ int egnn_knn_select_stream_f32(const float* coors, const uint8_t* mask, const ui
                                int B, int N, int K, int coor_dim, int32_t* idx_out, float* rank_out, void* stream);
 int egnn_knn_select_stream_f64(const double* coors, const uint8_t* mask, const uint8_t* adj, int64_t adj_batch_stride,
                                int B, int N, int K, int coor_dim, int32_t* idx_out, double* rank_out, void* stream);
+/* The cell-grid selection (csrc/knn_grid.hip): fp32 coordinates, coor_dim == 3, no adjacency, K <= 128, any B <= 65 535 and N.  Outputs
+ * bit-identical to egnn_knn_select_stream_f32 for every input with finite coordinates (the same distances and keys, ties to the lowest
+ * index), at a cost per row bounded by the row's neighbourhood instead of N: the valid nodes are counting-sorted into a uniform grid of
+ * cells (16 nodes per cell on average, outliers clamped into the border cells of a mean +- 4 sd box) and each row visits the cells at
+ * Chebyshev ring 1, 2, ... around its own until its K-th best squared distance is strictly below the distance of every unvisited cell,
+ * less a margin for fp32 rounding.  Rows a grid cannot answer are finished on the device by the streaming kernel, which skips every other
+ * row: graphs with a non-finite coordinate, an extent beyond 1e18, fewer than K valid nodes or more than max(4096, N / 64) nodes in one
+ * cell, and valid rows whose K-th neighbour lies at 1e5 or beyond in a graph with masked nodes.  No host read-back; seven launches on
+ * `stream`; deterministic (only integer counters are atomic).  workspace: egnn_knn_grid_workspace_bytes bytes (positive, non-decreasing
+ * in each argument), 256-byte aligned, contents undefined before and after.
+ * Errors: EGNN_E_UNSUPPORTED for coor_dim != 3 or K > 128, EGNN_E_SHAPE for K > N, non-positive sizes or a workspace that is too small,
+ * EGNN_E_NULLPTR.  The whole-layer entries (egnn_layer_forward_f32, egnn_layer_forward_opts_f32) keep the streaming selection: a
+ * binding that wants the grid on large graphs calls this entry itself and runs the layer's launches one by one, as the shipped Python
+ * binding does from 65 537 nodes. */
+size_t egnn_knn_grid_workspace_bytes(int B, int N, int K);
+int egnn_knn_select_grid_f32(const float* coors, const uint8_t* mask, int B, int N, int K, int coor_dim, int32_t* idx_out,
+                             float* rank_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Replaces `int(adj_mat.float().sum(dim=-1).max().item())` (egnn_pytorch.py:249; the diagonal is
  * counted when set).  adj: (rows, N) bytes.  *out_dev (device int32) receives the maximum row sum;
