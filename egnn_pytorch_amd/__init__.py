@@ -8,9 +8,10 @@ include/egnn_hip.h).  PyTorch is used for device memory, streams and torch.distr
 from .layer import EGNN, EGNN_Network, CoorsNorm, exact_arithmetic
 from ._ops import phase_timer, check_range
 from ._abi import EGNNHipError, EGNNRangeError
+from .sparse_adj import SparseAdjacency
 from . import sharding
 from .graph import graphed
 
 __all__ = ["EGNN", "EGNN_Network", "CoorsNorm", "phase_timer", "sharding", "graphed", "check_range", "EGNNHipError",
-           "EGNNRangeError", "exact_arithmetic"]
+           "EGNNRangeError", "exact_arithmetic", "SparseAdjacency"]
 __version__ = "0.1.0"

@@ -41,6 +41,10 @@ SYMBOLS = (
     "egnn_edge_hidden_bwd2_f32", "egnn_edge_hidden_bwd2_f64",
     "egnn_induced_attn_bwd_f32", "egnn_induced_attn_bwd_work_floats", "egnn_token_attn_bwd_chunks", "egnn_token_attn_bwd_f32", "egnn_gelu_bwd_f32",
     "egnn_layer_norm_bwd_parts", "egnn_layer_norm_bwd_f32",
+    "egnn_knn_select_csr_f32", "egnn_knn_select_csr_f64",
+    "egnn_adj_csr_workspace_bytes", "egnn_adj_csr_square_count", "egnn_adj_csr_square_fill", "egnn_csr_slot_labels_u8",
+    "egnn_edge_features_gather_slot_f32", "egnn_edge_features_gather_slot_f64", "egnn_edge_features_grad_slot_f32",
+    "egnn_edge_features_grad_slot_f64",
 )
 
 
@@ -373,7 +377,9 @@ def load():
     lib.egnn_layer_norm_bwd_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                             c_void_p]
     for gather, grad in ((lib.egnn_edge_features_gather_f32, lib.egnn_edge_features_grad_f32),
-                         (lib.egnn_edge_features_gather_f64, lib.egnn_edge_features_grad_f64)):     # (pointers only: one signature)
+                         (lib.egnn_edge_features_gather_f64, lib.egnn_edge_features_grad_f64),      # (pointers only: one signature)
+                         (lib.egnn_edge_features_gather_slot_f32, lib.egnn_edge_features_grad_slot_f32),
+                         (lib.egnn_edge_features_gather_slot_f64, lib.egnn_edge_features_grad_slot_f64)):
         gather.restype = c_int
         gather.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
         grad.restype = c_int
@@ -411,6 +417,19 @@ def load():
     for name in ("egnn_knn_select_stream_f32", "egnn_knn_select_stream_f64"):
         getattr(lib, name).restype = c_int
         getattr(lib, name).argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    for name in ("egnn_knn_select_csr_f32", "egnn_knn_select_csr_f64"):
+        getattr(lib, name).restype = c_int
+        getattr(lib, name).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    lib.egnn_adj_csr_workspace_bytes.restype = c_size_t
+    lib.egnn_adj_csr_workspace_bytes.argtypes = [c_int, c_int]
+    lib.egnn_adj_csr_square_count.restype = c_int
+    lib.egnn_adj_csr_square_count.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_size_t, c_int, c_void_p]
+    lib.egnn_adj_csr_square_fill.restype = c_int
+    lib.egnn_adj_csr_square_fill.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                             c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_void_p]
+    lib.egnn_csr_slot_labels_u8.restype = c_int
+    lib.egnn_csr_slot_labels_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
     lib.egnn_knn_grid_workspace_bytes.restype = c_size_t
     lib.egnn_knn_grid_workspace_bytes.argtypes = [c_int, c_int, c_int]
     lib.egnn_knn_select_grid_f32.restype = c_int

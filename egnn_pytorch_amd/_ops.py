@@ -15,6 +15,7 @@ from ctypes import byref, c_int64
 import torch
 
 from . import _abi
+from .sparse_adj import SparseAdjacency, SparseLabels
 
 
 class PhaseTimer:
@@ -376,7 +377,32 @@ def check_range(device=None, wait=True):
 def knn_select(coors, mask, adj_mat, k, out=None):
     """(idx int32 (B,N,K), rank (B,N,K) in the coordinates' dtype) -- egnn_knn_select_f32; float64 coordinates (a float64 module):
     egnn_knn_select_f64.  out = (idx, rank): caller-allocated outputs (the side-stream fork allocates them on the launch stream)."""
+    if isinstance(adj_mat, SparseAdjacency):
+        return knn_select_csr(coors, mask, adj_mat, k, out)
     return _knn_select(coors, mask, adj_mat, k, out, "egnn_knn_select")
+
+
+def knn_select_csr(coors, mask, adj, k, out=None):
+    """knn_select with the adjacency as a SparseAdjacency -- egnn_knn_select_csr_f32 / _f64: the streaming kernel on sorted column ranges
+    at every N; the same outputs bit for bit as knn_select with `adj.to_dense()`, without the (N, N) map."""
+    b, n, cdim = coors.shape
+    if adj.n != n or (adj.batched and adj.num_graphs != b):
+        raise ValueError(f"adj_mat shape {tuple(adj.shape)} != {(b, n, n)} or {(n, n)}")
+    if adj.device != coors.device:
+        raise RuntimeError(f"Expected all tensors to be on the same device: coors is on {coors.device}, adj_mat on {adj.device}")
+    f64 = coors.dtype == torch.float64
+    if out is not None:
+        idx, rank = out
+    else:
+        idx = empty(b, n, k, dtype=torch.int32, device=coors.device)
+        rank = empty(b, n, k, dtype=coors.dtype, device=coors.device)
+    m8 = _u8(mask)
+    name = "egnn_knn_select_csr" + ("_f64" if f64 else "_f32")
+    with _timed("knn_select"):
+        rc = getattr(_abi.load(), name)(_ptr(coors), _ptr(m8), _ptr(adj.rowptr), _ptr(adj.col) if adj.col.numel() else None,
+                                        0 if adj.shared else n + 1, b, n, k, cdim, _ptr(idx), _ptr(rank), _stream())
+    _abi.check(rc, name)
+    return idx, rank
 
 
 def knn_select_stream(coors, mask, adj_mat, k, out=None):
@@ -493,8 +519,66 @@ def _adj_expand(adj_mat, b, num_adj_degrees, entry):
     return adj_out.view(torch.bool), deg
 
 
+def adj_expand_csr(adj, b, num_adj_degrees, force_global=False):
+    """adj_expand on a SparseAdjacency (csrc/adj_csr.hip): (expanded adjacency as a SparseAdjacency, labels as a SparseLabels), whose
+    dense images are adj_expand(adj.to_dense(), b, D)'s outputs bit for bit; a shared adjacency (G = 1) stays shared.  Per degree a
+    count and a fill call, with ONE device->host read between them (the two totals that size the column arrays): not capturable in a
+    HIP graph.  force_global: every row on the kernels' global-memory bit maps (tests)."""
+    n, g = adj.n, adj.num_graphs
+    if adj.batched and g != b:
+        raise ValueError(f"adj_mat batch {g} != {b}")
+    dev = adj.device
+    labels = SparseLabels(adj.rowptr, adj.col, torch.ones(adj.col.numel(), dtype=torch.uint8, device=dev), n)
+    if num_adj_degrees == 1 or n == 0:
+        return adj, labels
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("EGNN_Network(num_adj_degrees > 1) with a SparseAdjacency cannot be captured in a HIP graph: the CSR expansion "
+                           "reads each degree's entry count back to size the next buffers (expand outside the capture, or pass the "
+                           "dense adjacency)")
+    lib = _abi.load()
+    ws = empty(max(1, lib.egnn_adj_csr_workspace_bytes(g, n)), dtype=torch.uint8, device=dev)
+    flags = 1 if force_global else 0
+    cur = adj
+    for degree in range(2, num_adj_degrees + 1):
+        nxt_rp = empty(g, n + 1, dtype=torch.int64, device=dev)
+        lab_rp = empty(g, n + 1, dtype=torch.int64, device=dev)
+        totals = empty(2, dtype=torch.int64, device=dev)
+        with _timed("adj_expand"):
+            rc = lib.egnn_adj_csr_square_count(_ptr(cur.rowptr), _ptr(cur.col), _ptr(labels.rowptr), _ptr(labels.col), g, n, _ptr(nxt_rp),
+                                               _ptr(lab_rp), _ptr(totals), _ptr(ws), ws.numel(), flags, _stream())
+        _abi.check(rc, "egnn_adj_csr_square_count")
+        nnz, lnz = totals.tolist()                                  # the one read of this degree
+        nxt_col = empty(max(1, min(nnz, 2 ** 31 - 1)), dtype=torch.int32, device=dev)[:nnz]
+        lab_col = empty(max(1, min(lnz, 2 ** 31 - 1)), dtype=torch.int32, device=dev)[:lnz]
+        lab_val = empty(max(1, min(lnz, 2 ** 31 - 1)), dtype=torch.uint8, device=dev)[:lnz]
+        with _timed("adj_expand"):
+            rc = lib.egnn_adj_csr_square_fill(_ptr(cur.rowptr), _ptr(cur.col), _ptr(labels.rowptr), _ptr(labels.col), _ptr(labels.val), g, n,
+                                              degree, _ptr(nxt_rp), _ptr(nxt_col), nnz, _ptr(lab_rp), _ptr(lab_col), _ptr(lab_val), lnz,
+                                              _ptr(ws), ws.numel(), flags, _stream())
+        _abi.check(rc, "egnn_adj_csr_square_fill")
+        cur = SparseAdjacency(nxt_rp, nxt_col, n, validate=False, batched=adj.batched)
+        labels = SparseLabels(lab_rp, lab_col, lab_val, n)
+    return cur, labels
+
+
+def csr_slot_labels(labels, idx, b, n, k):
+    """(B,N,K) bytes: the label of every selected pair (i, idx[b,i,k]) (idx None: the dense layer, j = k) from a SparseLabels --
+    egnn_csr_slot_labels_u8; what the _slot gather / gradient entries read in place of the (B,N,N) map."""
+    if labels.n != n or labels.num_graphs not in (1, b):
+        raise ValueError(f"labels for {labels.num_graphs} graphs of {labels.n} nodes, call on {b} graphs of {n}")
+    if idx is not None and (idx.dtype != torch.int32 or not idx.is_contiguous() or tuple(idx.shape) != (b, n, k)):
+        raise ValueError(f"csr_slot_labels: idx must be a contiguous ({b}, {n}, {k}) int32 tensor (got {tuple(idx.shape)} {idx.dtype})")
+    out = empty(b, n, k, dtype=torch.uint8, device=labels.device)
+    rc = _abi.load().egnn_csr_slot_labels_u8(_ptr(labels.rowptr), _ptr(labels.col), _ptr(labels.val), 0 if labels.shared else n + 1,
+                                             _ptr(idx), b, n, k, _ptr(out), _stream())
+    _abi.check(rc, "egnn_csr_slot_labels_u8")
+    return out
+
+
 def adj_max_degree(adj_mat):
     """int(adj_mat.float().sum(-1).max()) -- one device->host read, like the reference's .item() (:249)."""
+    if isinstance(adj_mat, SparseAdjacency):
+        return adj_mat.max_degree()
     a8 = _u8(adj_mat)
     n = a8.shape[-1]
     rows = a8.numel() // n
@@ -817,16 +901,25 @@ def _lookup_dtype(lookup, what):
     return dts.pop()
 
 
+def _deg_labels(deg, idx, b, n, k):
+    """(label bytes, entry infix) of an EdgeLookup's degree labels: the (B,N,N) map itself, or -- a SparseLabels -- the (B,N,K) labels of
+    the selected pairs and the _slot entries that read them"""
+    if isinstance(deg, SparseLabels):
+        return csr_slot_labels(deg, idx, b, n, k), "_slot"
+    return deg, ""
+
+
 def edge_features_gather(lookup, idx, b, n, k):
     """(B,N,K,edge_dim) features of the selected pairs from EGNN_Network's look-up tables, in the tables' dtype --
     egnn_edge_features_gather_f32 / _f64."""
     dev = (lookup.deg if lookup.deg is not None else (lookup.tok if lookup.tok is not None else lookup.edges)).device
     dtype = _lookup_dtype(lookup, "edge_features_gather")
-    name = "egnn_edge_features_gather_f64" if dtype == torch.float64 else "egnn_edge_features_gather_f32"
+    deg, slot = _deg_labels(lookup.deg, idx, b, n, k)
+    name = "egnn_edge_features_gather" + slot + ("_f64" if dtype == torch.float64 else "_f32")
     out = empty(b, n, k, lookup.width, dtype=dtype, device=dev)
     with _timed("edge_features"):
         rc = getattr(_abi.load(), name)(_ptr(lookup.edges), _ptr(lookup.tok), _ptr(lookup.tok_emb), lookup.d1,
-                                        _ptr(lookup.deg), _ptr(lookup.deg_emb), lookup.d2, _ptr(idx), b, n, k,
+                                        _ptr(deg), _ptr(lookup.deg_emb), lookup.d2, _ptr(idx), b, n, k,
                                         _ptr(out), _stream())
     _abi.check(rc, name)
     return out
@@ -844,9 +937,10 @@ def edge_features_grad(lookup, idx, b, n, k, g, want_tok=True, want_deg=True, g_
     dtype = _lookup_dtype(lookup, "edge_features_grad")
     if g.dtype != dtype:
         raise TypeError(f"edge_features_grad: g must be float32 or float64, matching the tables (g is {g.dtype}, the tables {dtype})")
-    name = "egnn_edge_features_grad_f64" if dtype == torch.float64 else "egnn_edge_features_grad_f32"
     on1 = want_tok and lookup.tok is not None
     on2 = want_deg and lookup.deg is not None
+    deg, slot = _deg_labels(lookup.deg, idx, b, n, k) if on2 else (None, "_slot" if isinstance(lookup.deg, SparseLabels) else "")
+    name = "egnn_edge_features_grad" + slot + ("_f64" if dtype == torch.float64 else "_f32")
     v1 = lookup.tok_emb.shape[0] if on1 else 0
     v2 = lookup.deg_emb.shape[0] if on2 else 0
     g_tok = empty(v1, lookup.d1, dtype=dtype, device=dev) if on1 else None
@@ -856,11 +950,11 @@ def edge_features_grad(lookup, idx, b, n, k, g, want_tok=True, want_deg=True, g_
         raise ValueError(f"edge_features_grad: g_edges must be a contiguous (B,N,N,d1) {dtype} tensor")
     if idx is not None and (idx.dtype != torch.int32 or not idx.is_contiguous() or tuple(idx.shape) != (b, n, k)):
         raise ValueError(f"edge_features_grad: idx must be a contiguous ({b}, {n}, {k}) int32 tensor")
-    for lab in ((lookup.tok,) if on1 else ()) + ((lookup.deg,) if on2 else ()):
-        if not lab.is_contiguous() or tuple(lab.shape) != (b, n, n):
+    for lab in ((lookup.tok,) if on1 else ()) + ((deg,) if on2 else ()):
+        if not lab.is_contiguous() or tuple(lab.shape) != ((b, n, k) if (slot and lab is deg) else (b, n, n)):
             raise ValueError(f"edge_features_grad: labels {tuple(lab.shape)} != {(b, n, n)}")
     entry = getattr(_abi.load(), name)
-    args = (_ptr(g), g.stride(0), _ptr(lookup.tok) if on1 else None, v1, lookup.d1, _ptr(lookup.deg) if on2 else None, v2,
+    args = (_ptr(g), g.stride(0), _ptr(lookup.tok) if on1 else None, v1, lookup.d1, _ptr(deg) if on2 else None, v2,
             lookup.d2, _ptr(idx), b, n, k, _ptr(g_tok), _ptr(g_deg), _ptr(g_edges))
     nw = c_int64(0)
     _abi.check(entry(*args, None, byref(nw), _stream()), name)

@@ -42,6 +42,8 @@ import os
 import torch
 from torch import nn
 
+from .sparse_adj import SparseLabels
+
 # EGNN_NATIVE_BACKWARD=0: always the pure-ATen recompute (the reference implementation of the backward)
 _NATIVE_MODE = os.environ.get("EGNN_NATIVE_BACKWARD", "1")
 _NATIVE = _NATIVE_MODE != "0"
@@ -1781,7 +1783,11 @@ def _lookup_rows(lookup, idx, b, n, k):
     if lookup.d1:
         cols.append(tok_w[lookup.tok.reshape(-1)[pair]] if lookup.tok is not None else edges.reshape(-1, lookup.d1)[pair])
     if lookup.d2:
-        cols.append(deg_w[lookup.deg.reshape(-1)[pair].long()])
+        if isinstance(lookup.deg, SparseLabels):                # (label CSR: the labels of the selected pairs, per slot)
+            i32 = None if idx is None else idx.to(torch.int32).contiguous()      # (the kernel reads int32; `idx` may be the long copy)
+            cols.append(deg_w[_ops_mod().csr_slot_labels(lookup.deg, i32, b, n, k).reshape(-1).long()])
+        else:
+            cols.append(deg_w[lookup.deg.reshape(-1)[pair].long()])
     return (torch.cat(cols, dim=-1) if len(cols) > 1 else cols[0]).view(b, n, k, lookup.width)
 
 

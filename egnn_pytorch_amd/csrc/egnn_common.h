@@ -270,6 +270,25 @@ __device__ __forceinline__ T egnn_knn_rank(T d, bool mi, bool mj, const uint8_t*
     }
     return d;
 }
+// The same with row i of the adjacency as a sorted column range (CSR: `len` strictly ascending int32 columns at `col`) instead of a byte
+// row.  The caller asks for ascending j between two egnn_csr_rewind calls -- each thread of the selection kernels walks its candidates in
+// ascending order -- so the row is merged, not searched: one cursor per thread, len + (candidates) steps per walk.
+struct egnn_csr_cursor { const int32_t* col; int len, p, next; };
+__device__ __forceinline__ void egnn_csr_rewind(egnn_csr_cursor& c) {
+    c.p = 0;
+    c.next = c.len > 0 ? c.col[0] : 0x7fffffff;
+}
+template <typename T>
+__device__ __forceinline__ T egnn_knn_rank(T d, bool mi, bool mj, egnn_csr_cursor& row, int i, int j) {
+    if (!(mi && mj)) d = (T)1e5;
+    while (row.next < j) {
+        ++row.p;
+        row.next = row.p < row.len ? row.col[row.p] : 0x7fffffff;
+    }
+    if (j == i) d = (T)-1;
+    else if (row.next == j) d = (T)0;
+    return d;
+}
 // order-preserving unsigned images of the ranking values (selection compares keys; ties by ascending index)
 __device__ __forceinline__ uint32_t egnn_rank_key(float f) {
     const uint32_t u = __float_as_uint(f);

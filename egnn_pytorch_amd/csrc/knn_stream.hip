@@ -31,11 +31,19 @@ template <> struct KsKey<double> { typedef uint64_t type; static constexpr int V
 // CDM: 3 = egnn_sqdist (float, C == 3), 8 = egnn_sqdist_n (float, C <= 8), 0 = egnn_sqdist_any (float C > 8, every double C)
 // FL: only the rows with rowflag[b N + i] != 0 are selected and written (the rows the cell-grid selection hands over, knn_grid.hip); a
 // workgroup without such a row returns at once.
-template <typename T, int CDM, bool FL = false>
+// CSR: the adjacency as sorted column ranges (egnn_knn_select_csr_f32 / _f64) -- adj = rowptr, int64 absolute offsets, (N + 1) per graph
+// at a graph stride of adj_bstride entries (0: one graph's rows for all); rowflag's place holds the flat int32 column array (never with
+// FL).  Every row then has an adjacency; its ranking values come from the merging overload of egnn_knn_rank.
+template <bool CSR> struct KsAdj { typedef uint8_t adj_t; typedef uint8_t aux_t; };
+template <> struct KsAdj<true> { typedef int64_t adj_t; typedef int32_t aux_t; };
+
+template <typename T, int CDM, bool FL = false, bool CSR = false>
 __global__ __launch_bounds__(KS_THREADS) void knn_select_stream_kernel(
-    const T* __restrict__ coors, const uint8_t* __restrict__ mask, const uint8_t* __restrict__ adj, int64_t adj_bstride,
-    int N, int K, int C, int R, int IBP, int32_t* __restrict__ idx_out, T* __restrict__ rank_out, const uint8_t* __restrict__ rowflag)
+    const T* __restrict__ coors, const uint8_t* __restrict__ mask, const typename KsAdj<CSR>::adj_t* __restrict__ adj, int64_t adj_bstride,
+    int N, int K, int C, int R, int IBP, int32_t* __restrict__ idx_out, T* __restrict__ rank_out,
+    const typename KsAdj<CSR>::aux_t* __restrict__ rowflag)
 {
+    static_assert(!(FL && CSR), "the flagged rows have no adjacency");
     typedef typename KsKey<T>::type key_t;
     constexpr int KB = 8 * (int)sizeof(key_t);           // key bits
     constexpr int KD = KB / 8;                           // key digits
@@ -71,7 +79,20 @@ __global__ __launch_bounds__(KS_THREADS) void knn_select_stream_kernel(
         if (!any) return;                                                // (the same for every thread of the workgroup)
         fl = i < N && rowflag[(size_t)b * N + i] != 0;
     }
-    const uint8_t* adjrow = (adj && i < N) ? adj + (size_t)b * adj_bstride + (size_t)i * N : nullptr;
+    // (CSR: adjrow only says that the row has an adjacency -- never read; the row itself is the cursor's column range)
+    const uint8_t* adjrow;
+    egnn_csr_cursor csr = {nullptr, 0, 0, 0x7fffffff};
+    if constexpr (CSR) {
+        adjrow = i < N ? reinterpret_cast<const uint8_t*>(adj) : nullptr;
+        if (i < N) {
+            const int64_t* rp = adj + (size_t)b * adj_bstride + i;
+            const int64_t lo = rp[0];
+            csr.col = rowflag + lo;
+            csr.len = (int)(rp[1] - lo);
+        }
+    } else {
+        adjrow = (adj && i < N) ? adj + (size_t)b * adj_bstride + (size_t)i * N : nullptr;
+    }
 
     for (int o = tid; o < R * KS_HSTRIDE; o += KS_THREADS) hist[o] = 0;
     if (s == 0) {
@@ -115,7 +136,8 @@ __global__ __launch_bounds__(KS_THREADS) void knn_select_stream_kernel(
         } else {
             d = egnn_sqdist_any<T, KsKey<T>::V>(qrow, cb + (size_t)j * C, C);
         }
-        return egnn_rank_key(egnn_knn_rank<T>(d, mi, mb ? mb[j] != 0 : true, adjrow, i, j));
+        if constexpr (CSR) return egnn_rank_key(egnn_knn_rank<T>(d, mi, mb ? mb[j] != 0 : true, csr, i, j));
+        else return egnn_rank_key(egnn_knn_rank<T>(d, mi, mb ? mb[j] != 0 : true, adjrow, i, j));
     };
     __syncthreads();
 
@@ -128,6 +150,7 @@ __global__ __launch_bounds__(KS_THREADS) void knn_select_stream_kernel(
         const int kl = L < KD ? L : KD, il = L - kl;                     // resolved key / index digits
         if (mine) {
             int* h = hist + r * KS_HSTRIDE;
+            if constexpr (CSR) egnn_csr_rewind(csr);
             for (int j = s; j < N; j += S) {
                 const key_t kj = key_of(j);
                 if (kl > 0 && (kj >> (KB - 8 * kl)) != P) continue;
@@ -179,6 +202,7 @@ __global__ __launch_bounds__(KS_THREADS) void knn_select_stream_kernel(
         const int kl = L < KD ? L : KD, il = L - kl;                     // (kl >= 1: at least one pass)
         key_t* sk = selk + (size_t)r * K;
         int* sj = selj + (size_t)r * K;
+        if constexpr (CSR) egnn_csr_rewind(csr);
         for (int j = s; j < N; j += S) {
             const key_t kj = key_of(j);
             const key_t kp = kj >> (KB - 8 * kl);
@@ -207,9 +231,9 @@ __global__ __launch_bounds__(KS_THREADS) void knn_select_stream_kernel(
     }
 }
 
-template <typename T>
-int knn_stream_launch(const T* coors, const uint8_t* mask, const uint8_t* adj, int64_t adj_bstride, int B, int N, int K, int C,
-                      int32_t* idx_out, T* rank_out, void* stream, const uint8_t* rowflag = nullptr)
+template <typename T, bool CSR = false>
+int knn_stream_launch(const T* coors, const uint8_t* mask, const typename KsAdj<CSR>::adj_t* adj, int64_t adj_bstride, int B, int N, int K,
+                      int C, int32_t* idx_out, T* rank_out, void* stream, const typename KsAdj<CSR>::aux_t* rowflag = nullptr)
 {
     if (!coors || !idx_out || !rank_out) return EGNN_E_NULLPTR;
     if (B <= 0 || N <= 0 || K <= 0) return EGNN_E_SHAPE;
@@ -226,13 +250,15 @@ int knn_stream_launch(const T* coors, const uint8_t* mask, const uint8_t* adj, i
     const size_t head = KS_RMAX * (sizeof(key_t) + 4 + 4 * 5) + 4 * 4;
     const size_t lds = head + (size_t)((R * KS_HSTRIDE + 1) & ~1) * 4 + (size_t)R * K * sizeof(key_t) +
                        ((size_t)R * K + (((size_t)R * K) & 1)) * 4 + (size_t)R * C * sizeof(T);
-    auto kern = knn_select_stream_kernel<T, 0>;
+    auto kern = knn_select_stream_kernel<T, 0, false, CSR>;
     if constexpr (sizeof(T) == 4) {
-        if (C == 3) kern = knn_select_stream_kernel<T, 3>;
-        else if (C <= 8) kern = knn_select_stream_kernel<T, 8>;
-        if (rowflag) {
-            if (C != 3) return EGNN_E_UNSUPPORTED;
-            kern = knn_select_stream_kernel<T, 3, true>;
+        if (C == 3) kern = knn_select_stream_kernel<T, 3, false, CSR>;
+        else if (C <= 8) kern = knn_select_stream_kernel<T, 8, false, CSR>;
+        if constexpr (!CSR) {
+            if (rowflag) {
+                if (C != 3) return EGNN_E_UNSUPPORTED;
+                kern = knn_select_stream_kernel<T, 3, true>;
+            }
         }
     }
     if (lds > 64 * 1024) {
@@ -264,4 +290,28 @@ extern "C" int egnn_knn_select_stream_f64(const double* coors, const uint8_t* ma
                                           int N, int K, int coor_dim, int32_t* idx_out, double* rank_out, void* stream)
 {
     return knn_stream_launch<double>(coors, mask, adj, adj_batch_stride, B, N, K, coor_dim, idx_out, rank_out, stream);
+}
+
+// The same selection with the adjacency as CSR rows (include/egnn_hip.h): the one kernel at every N.
+template <typename T>
+static int knn_csr(const T* coors, const uint8_t* mask, const int64_t* rowptr, const int32_t* col, int64_t rowptr_graph_stride, int B, int N,
+                   int K, int C, int32_t* idx_out, T* rank_out, void* stream)
+{
+    if (!rowptr) return EGNN_E_NULLPTR;
+    if (N > 0 && rowptr_graph_stride != 0 && rowptr_graph_stride != (int64_t)N + 1) return EGNN_E_SHAPE;
+    return knn_stream_launch<T, true>(coors, mask, rowptr, rowptr_graph_stride, B, N, K, C, idx_out, rank_out, stream, col);
+}
+
+extern "C" int egnn_knn_select_csr_f32(const float* coors, const uint8_t* mask, const int64_t* rowptr, const int32_t* col,
+                                       int64_t rowptr_graph_stride, int B, int N, int K, int coor_dim, int32_t* idx_out, float* rank_out,
+                                       void* stream)
+{
+    return knn_csr<float>(coors, mask, rowptr, col, rowptr_graph_stride, B, N, K, coor_dim, idx_out, rank_out, stream);
+}
+
+extern "C" int egnn_knn_select_csr_f64(const double* coors, const uint8_t* mask, const int64_t* rowptr, const int32_t* col,
+                                       int64_t rowptr_graph_stride, int B, int N, int K, int coor_dim, int32_t* idx_out, double* rank_out,
+                                       void* stream)
+{
+    return knn_csr<double>(coors, mask, rowptr, col, rowptr_graph_stride, B, N, K, coor_dim, idx_out, rank_out, stream);
 }

@@ -61,7 +61,9 @@ extern "C" int egnn_rows_gather_sum_f32(const float* rows, int64_t ld, const int
 // kernel for both).  One thread per (edge, column).
 namespace {
 
-template <typename T>
+// SLOT: `deg` holds the labels of the selected pairs themselves, (B,N,K) bytes read at the slot (egnn_csr_slot_labels_u8 made them from a
+// label CSR), instead of the (B,N,N) map read at [b, i, j] -- the _slot entries; the same kernel otherwise.
+template <typename T, bool SLOT = false>
 __global__ __launch_bounds__(256) void edge_features_gather_kernel(const T* __restrict__ edges, const int64_t* __restrict__ tok,
                                                                    const T* __restrict__ tok_emb, int d1,
                                                                    const uint8_t* __restrict__ deg, const T* __restrict__ deg_emb,
@@ -78,12 +80,12 @@ __global__ __launch_bounds__(256) void edge_features_gather_kernel(const T* __re
         const int64_t pair = node * N + j;
         T v;
         if (col < d1) v = tok ? tok_emb[tok[pair] * d1 + col] : edges[pair * d1 + col];
-        else v = deg_emb[(int64_t)deg[pair] * d2 + (col - d1)];
+        else v = deg_emb[(int64_t)deg[SLOT ? edge : pair] * d2 + (col - d1)];
         out[o] = v;
     }
 }
 
-template <typename T>
+template <typename T, bool SLOT = false>
 int edge_features_gather(const T* edges, const int64_t* edge_tok, const T* edge_tok_emb, int d1, const uint8_t* adj_deg,
                          const T* adj_deg_emb, int d2, const int32_t* idx, int B, int N, int K, T* out, void* stream)
 {
@@ -95,7 +97,7 @@ int edge_features_gather(const T* edges, const int64_t* edge_tok, const T* edge_
     const int64_t total = (int64_t)B * N * K * (d1 + d2);
     int64_t blocks = (total + 255) / 256;
     if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(edge_features_gather_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), edges,
+    hipLaunchKernelGGL((edge_features_gather_kernel<T, SLOT>), dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), edges,
                        edge_tok, edge_tok_emb, d1, adj_deg, adj_deg_emb, d2, idx, N, K, total, out);
     return egnn_launch_status();
 }
@@ -114,6 +116,20 @@ extern "C" int egnn_edge_features_gather_f64(const double* edges, const int64_t*
                                              int B, int N, int K, double* out, void* stream)
 {
     return edge_features_gather<double>(edges, edge_tok, edge_tok_emb, d1, adj_deg, adj_deg_emb, d2, idx, B, N, K, out, stream);
+}
+
+extern "C" int egnn_edge_features_gather_slot_f32(const float* edges, const int64_t* edge_tok, const float* edge_tok_emb, int d1,
+                                                  const uint8_t* slot_deg, const float* adj_deg_emb, int d2, const int32_t* idx,
+                                                  int B, int N, int K, float* out, void* stream)
+{
+    return edge_features_gather<float, true>(edges, edge_tok, edge_tok_emb, d1, slot_deg, adj_deg_emb, d2, idx, B, N, K, out, stream);
+}
+
+extern "C" int egnn_edge_features_gather_slot_f64(const double* edges, const int64_t* edge_tok, const double* edge_tok_emb, int d1,
+                                                  const uint8_t* slot_deg, const double* adj_deg_emb, int d2, const int32_t* idx,
+                                                  int B, int N, int K, double* out, void* stream)
+{
+    return edge_features_gather<double, true>(edges, edge_tok, edge_tok_emb, d1, slot_deg, adj_deg_emb, d2, idx, B, N, K, out, stream);
 }
 
 
@@ -144,7 +160,7 @@ struct FeatGradTable {
 
 __device__ __forceinline__ int fgrad_groups(int D) { return D <= 64 ? 64 / D : 1; }
 
-template <typename T>
+template <typename T, bool SLOT = false>
 __global__ __launch_bounds__(256) void edge_features_grad_part_kernel(const T* __restrict__ g, int64_t ld,
                                                                       const int64_t* __restrict__ tok, const uint8_t* __restrict__ deg,
                                                                       const int32_t* __restrict__ idx, int N, int K, int64_t E,
@@ -178,7 +194,7 @@ __global__ __launch_bounds__(256) void edge_features_grad_part_kernel(const T* _
         const int j = idx ? idx[e] : k;
         if ((unsigned)j >= (unsigned)N) return -1;
         const int64_t pair = node * N + j;
-        const int64_t v = (second ? (int64_t)deg[pair] : tok[pair]) - vb0;
+        const int64_t v = (second ? (int64_t)deg[SLOT ? e : pair] : tok[pair]) - vb0;
         return (v >= 0 && v < vn) ? (int)v : -1;
     };
     if (p < P) {
@@ -263,7 +279,7 @@ FeatGradTable fgrad_table(bool on, int V, int D, int col0, int64_t off, int wave
     return t;
 }
 
-template <typename T>
+template <typename T, bool SLOT = false>
 int edge_features_grad(const T* g, int64_t ld, const int64_t* edge_tok, int V1, int d1, const uint8_t* adj_deg, int V2, int d2,
                        const int32_t* idx, int B, int N, int K, T* g_tok_emb, T* g_deg_emb, T* g_edges, T* work,
                        int64_t* work_floats, void* stream)
@@ -308,7 +324,7 @@ int edge_features_grad(const T* g, int64_t ld, const int64_t* edge_tok, int V1, 
     }
     if (stride == 0) return EGNN_OK;
     const int64_t per = (E + G - 1) / G;
-    hipLaunchKernelGGL(edge_features_grad_part_kernel<T>, dim3((unsigned)G, (unsigned)(t1.nb + t2.nb)), dim3(256), 0, st, g, ld,
+    hipLaunchKernelGGL((edge_features_grad_part_kernel<T, SLOT>), dim3((unsigned)G, (unsigned)(t1.nb + t2.nb)), dim3(256), 0, st, g, ld,
                        edge_tok, adj_deg, idx, N, K, E, per, t1, t2, work, stride);
     int rc = egnn_launch_status();
     if (rc) return rc;
@@ -335,4 +351,22 @@ extern "C" int egnn_edge_features_grad_f64(const double* g, int64_t ld, const in
 {
     return edge_features_grad<double>(g, ld, edge_tok, V1, d1, adj_deg, V2, d2, idx, B, N, K, g_tok_emb, g_deg_emb, g_edges, work,
                                       work_floats, stream);
+}
+
+extern "C" int egnn_edge_features_grad_slot_f32(const float* g, int64_t ld, const int64_t* edge_tok, int V1, int d1,
+                                                const uint8_t* slot_deg, int V2, int d2, const int32_t* idx, int B, int N, int K,
+                                                float* g_tok_emb, float* g_deg_emb, float* g_edges, float* work, int64_t* work_floats,
+                                                void* stream)
+{
+    return edge_features_grad<float, true>(g, ld, edge_tok, V1, d1, slot_deg, V2, d2, idx, B, N, K, g_tok_emb, g_deg_emb, g_edges, work,
+                                           work_floats, stream);
+}
+
+extern "C" int egnn_edge_features_grad_slot_f64(const double* g, int64_t ld, const int64_t* edge_tok, int V1, int d1,
+                                                const uint8_t* slot_deg, int V2, int d2, const int32_t* idx, int B, int N, int K,
+                                                double* g_tok_emb, double* g_deg_emb, double* g_edges, double* work, int64_t* work_floats,
+                                                void* stream)
+{
+    return edge_features_grad<double, true>(g, ld, edge_tok, V1, d1, slot_deg, V2, d2, idx, B, N, K, g_tok_emb, g_deg_emb, g_edges, work,
+                                            work_floats, stream);
 }

@@ -8,13 +8,16 @@ sequence once into a HIP graph (torch.cuda.CUDAGraph; the kernels run on the cap
 
 Restrictions (same as any stream capture): fixed shapes / dtypes / which optional inputs are present; no host
 synchronisation inside forward, i.e. not `only_sparse_neighbors=True` (its K is read back from the device,
-egnn_pytorch.py:249).  The returned outputs are the graph's own buffers: they are overwritten by the next replay --
+egnn_pytorch.py:249), and not `EGNN_Network(num_adj_degrees > 1)` with a `SparseAdjacency` (the CSR expansion reads each degree's entry
+count back to size the next buffers: `graphed` refuses it before any forward runs -- expand outside, or pass the dense map).  A
+`SparseAdjacency` is a non-tensor argument: baked into the graph, and every replay must be called with the same object.  The returned outputs are the graph's own buffers: they are overwritten by the next replay --
 clone them if they have to survive it."""
 from __future__ import annotations
 
 import torch
 
 from . import _ops
+from .sparse_adj import SparseAdjacency
 
 
 def graphed(module, *example_inputs, warmup: int = 2, range_check: str | None = None, **example_kwargs):
@@ -28,6 +31,10 @@ def graphed(module, *example_inputs, warmup: int = 2, range_check: str | None = 
         if callable(getattr(m, "dropout_active", None)) and m.dropout_active():
             raise NotImplementedError("graphed(): a layer has training-mode dropout active; its mask seed would be frozen into the graph "
                                       "(call .eval(), or run the module eagerly)")
+    if any(isinstance(a, SparseAdjacency) for a in list(example_inputs) + list(example_kwargs.values())) and any(
+            (getattr(m, "num_adj_degrees", None) or 0) > 1 for m in module.modules()):
+        raise NotImplementedError("graphed(): num_adj_degrees > 1 with a SparseAdjacency reads each degree's entry count back from the "
+                                  "device (the CSR expansion sizes its buffers from it) and cannot be captured; pass the dense adjacency")
     args = [a.clone() if torch.is_tensor(a) else a for a in example_inputs]
     kwargs = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in example_kwargs.items()}
     dev = next(a for a in list(args) + list(kwargs.values()) if torch.is_tensor(a)).device

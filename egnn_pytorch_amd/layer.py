@@ -24,6 +24,7 @@ from torch import nn
 
 from . import _abi, _dropout, _ops, _weights, autograd as _autograd
 from .attention import GlobalLinearAttention
+from .sparse_adj import SparseAdjacency, SparseLabels
 
 _SPATIAL_ORDER = os.environ.get("EGNN_SPATIAL_ORDER", "1") != "0"     # scheduling knob only; results do not depend on it
 _SLOT_PREP = os.environ.get("EGNN_SLOT_PREP", "1") != "0"             # per-slot records for the edge pass's setup (same results)
@@ -142,7 +143,7 @@ class EdgeLookup:
         out.live = (None if self.live[0] is None else self.live[0][lo:hi],) + tuple(self.live[1:])
         out.edges = None if self.edges is None else self.edges[lo:hi]
         out.tok = None if self.tok is None else self.tok[lo:hi]
-        out.deg = None if self.deg is None else self.deg[lo:hi]
+        out.deg = None if self.deg is None else (self.deg.graphs(lo, hi) if isinstance(self.deg, SparseLabels) else self.deg[lo:hi])
         return out
 
 
@@ -247,7 +248,7 @@ class EGNN(nn.Module):
         if mask is not None and tuple(mask.shape) != (b, n):
             raise ValueError(f"mask shape {tuple(mask.shape)} != {(b, n)}")
         if adj_mat is not None and self._use_nearest():               # (a dense layer does not read the adjacency)
-            want = (b, n, n) if adj_mat.dim() == 3 else (n, n)
+            want = (b, n, n) if adj_mat.dim() == 3 else (n, n)      # (a SparseAdjacency answers with its dense image's shape)
             if tuple(adj_mat.shape) != want:
                 raise ValueError(f"adj_mat shape {tuple(adj_mat.shape)} != {want}")
         # the kernels take raw device pointers: a tensor on another device (or on the host) would be read as garbage, not rejected
@@ -478,6 +479,7 @@ class EGNN(nn.Module):
         dev = feats.device
         if (isinstance(edges, EdgeLookup) or cdim > 8 or self.m_dim > 64 or 2 * self.fourier_features + 1 + self.edge_dim > 16
                 or dev.index != torch.cuda.current_device() or (adj_mat is not None and adj_mat.dtype != torch.bool)
+                or isinstance(adj_mat, SparseAdjacency)             # (the C entry keeps its dense signature)
                 or (not use_nearest and self._dense_pw(b, n, cdim))
                 or (use_nearest and self._use_grid(coors, adj_mat, self.num_nearest_neighbors))):
             return None
@@ -866,7 +868,11 @@ class EGNN_Network(nn.Module):
             if not adj_mat.is_cuda:
                 raise RuntimeError("egnn_pytorch_amd.EGNN_Network runs only on an MI355X (cuda/HIP) device")
             # N-degree expansion (egnn_pytorch.py:414-427) as bit-set algebra on the device instead of float matmuls
-            adj_mat, adj_indices = _ops.adj_expand(adj_mat, b, self.num_adj_degrees)
+            # (a SparseAdjacency: the same expansion on CSR rows, csrc/adj_csr.hip -- the expanded adjacency and the labels stay CSR)
+            if isinstance(adj_mat, SparseAdjacency):
+                adj_mat, adj_indices = _ops.adj_expand_csr(adj_mat, b, self.num_adj_degrees)
+            else:
+                adj_mat, adj_indices = _ops.adj_expand(adj_mat, b, self.num_adj_degrees)
             if self.adj_emb is not None:
                 edges = EdgeLookup(edges=edges, tok=tok, tok_emb=tok_emb, deg=adj_indices, deg_emb=self.adj_emb.weight, dtype=lookup_dtype)
                 tok = None

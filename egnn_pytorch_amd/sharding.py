@@ -12,6 +12,8 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
+from .sparse_adj import SparseAdjacency
+
 
 def shard_bounds(batch: int, rank: int, world: int):
     """Contiguous split of `batch` graphs: the first (batch % world) ranks get one extra graph."""
@@ -26,7 +28,8 @@ def shard_batch(rank: int, world: int, *tensors, shared=()):
     """Slice every per-graph tensor (leading dim B) to this rank's graphs.  `None` entries pass through.  Tensors that
     all graphs share -- a 2-D `(N, N)` adjacency -- are named explicitly in `shared` (compared by identity) and are
     replicated, not split; there is no shape heuristic (a `(B, N)` mask with B == N looks exactly like an adjacency).
-    Every other tensor must have the batch as its leading dimension."""
+    Every other tensor must have the batch as its leading dimension.  A `SparseAdjacency` goes the same way: a batched one is sliced
+    with `graphs(lo, hi)`, one that all graphs share is named in `shared`."""
     shared_ids = {id(t) for t in shared if t is not None}
     per_graph = [t for t in tensors if t is not None and id(t) not in shared_ids]
     if not per_graph:
@@ -43,7 +46,7 @@ def shard_batch(rank: int, world: int, *tensors, shared=()):
             if t.shape[0] != bsz:
                 raise ValueError(f"per-graph tensor with leading dim {t.shape[0]} != batch {bsz} "
                                  f"(pass tensors shared by all graphs via shared=(...))")
-            out.append(t[lo:hi])
+            out.append(t.graphs(lo, hi) if isinstance(t, SparseAdjacency) else t[lo:hi])
     return out
 
 

@@ -98,6 +98,23 @@ int egnn_knn_select_stream_f32(const float* coors, const uint8_t* mask, const ui
                                int B, int N, int K, int coor_dim, int32_t* idx_out, float* rank_out, void* stream);
 int egnn_knn_select_stream_f64(const double* coors, const uint8_t* mask, const uint8_t* adj, int64_t adj_batch_stride,
                                int B, int N, int K, int coor_dim, int32_t* idx_out, double* rank_out, void* stream);
+/* The selection with the adjacency as CSR rows instead of a byte map (csrc/knn_stream.hip: the streaming kernel at every N, reading a
+ * sorted column range where egnn_knn_select_stream_f32 reads a byte row; nothing of size N*N is read or written).
+ *   rowptr  int64, (N + 1) absolute offsets into `col` per graph: rowptr_graph_stride = 0 (one graph's rows, shared by all B) or N + 1
+ *           ((B, N + 1)); row i of graph b is col[rowptr[b stride + i] .. rowptr[b stride + i + 1]).
+ *   col     int32, strictly ascending within a row, every entry in [0, N); may be NULL when every row is empty.  Directed as given; a
+ *           diagonal entry is allowed and ignored, as in the byte map.
+ * Every other argument, the limits and the outputs are those of egnn_knn_select_stream_f32 / _f64 called with the dense image of the
+ * rows, bit for bit.  The entry does not read rowptr / col on the host: offsets and columns out of range are the caller's to exclude
+ * (egnn_pytorch_amd.SparseAdjacency validates them).  Errors: EGNN_E_NULLPTR (coors, rowptr, outputs), EGNN_E_SHAPE (non-positive sizes,
+ * a stride other than 0 or N + 1), EGNN_E_K_GT_N, EGNN_E_UNSUPPORTED (coor_dim outside 1..64, K > 1024, B > 65 535) -- all returned before
+ * any launch. */
+int egnn_knn_select_csr_f32(const float* coors, const uint8_t* mask, const int64_t* rowptr, const int32_t* col,
+                            int64_t rowptr_graph_stride, int B, int N, int K, int coor_dim, int32_t* idx_out, float* rank_out,
+                            void* stream);
+int egnn_knn_select_csr_f64(const double* coors, const uint8_t* mask, const int64_t* rowptr, const int32_t* col,
+                            int64_t rowptr_graph_stride, int B, int N, int K, int coor_dim, int32_t* idx_out, double* rank_out,
+                            void* stream);
 /* The cell-grid selection (csrc/knn_grid.hip): fp32 coordinates, coor_dim == 3, no adjacency, K <= 128, any B <= 65 535 and N.  Outputs
  * bit-identical to egnn_knn_select_stream_f32 for every input with finite coordinates (the same distances and keys, ties to the lowest
  * index), at a cost per row bounded by the row's neighbourhood instead of N: the valid nodes are counting-sorted into a uniform grid of
@@ -115,6 +132,41 @@ int egnn_knn_select_stream_f64(const double* coors, const uint8_t* mask, const u
 size_t egnn_knn_grid_workspace_bytes(int B, int N, int K);
 int egnn_knn_select_grid_f32(const float* coors, const uint8_t* mask, int B, int N, int K, int coor_dim, int32_t* idx_out,
                              float* rank_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Sparse adjacency: the N-degree expansion of EGNN_Network (egnn_pytorch.py:414-427; egnn_adj_expand_u8 is its dense form) on CSR rows
+ * (csrc/adj_csr.hip).  Row pointers are int64 (G, N + 1) ABSOLUTE offsets into a flat int32 column array, columns strictly ascending
+ * within a row; G = 1 (one graph's rows for a whole batch) or G = B.  The labels are a CSR of their own -- row pointers, columns, one
+ * byte per entry -- over every pair that ever received a label (a pair outside it has label 0).
+ * One degree step (degree = 2, 3, ...):  nxt = pattern(cur . cur), labels[nxt XOR cur] = degree (an entry of cur that nxt lacks is
+ * relabelled too: graphs without a diagonal), cur = nxt.  It is two calls, as any CSR product:
+ *   egnn_adj_csr_square_count   the row lengths of nxt and of the new label CSR (old labels u nxt), scanned into nxt_rowptr and
+ *                               new_lab_rowptr ((G, N + 1) each, offsets from 0) and totals[0], totals[1] (device int64): the caller
+ *                               reads the totals back -- the one synchronisation per degree -- and allocates the column arrays;
+ *   egnn_adj_csr_square_fill    nxt_col; new_lab_col, new_lab_val (degree where changed, the old label elsewhere).
+ * The dense images equal egnn_adj_expand_u8's outputs bit for bit.  The library allocates nothing and never synchronises.  A row is
+ * built as a bit set over the column range it touches -- in LDS up to 131 072 columns, beyond that in the workgroup's slice of
+ * `workspace` (slower; no bound on row length or N) -- filled with integer atomics and emitted in ascending order: deterministic.
+ * flags bit 0: every row on the global-memory path (tests).  degree 1 needs no call: cur = A, labels = 1 on A.
+ * workspace: egnn_adj_csr_workspace_bytes(G, N) bytes, 16-byte aligned, shared by the two calls of a step (count leaves nothing in it
+ * that fill reads).  Errors, all before any launch: EGNN_E_NULLPTR; EGNN_E_SHAPE for non-positive sizes, degree < 2, a workspace that is
+ * too small, or a total beyond 2^31 - 1 entries (nxt_nnz / new_lab_nnz: what the caller read from `totals`); EGNN_E_UNSUPPORTED for
+ * degree > 255 or G > 65 535; EGNN_E_ALIGN.  The entries do not read the CSR arrays on the host: offsets out of order or beyond the column
+ * arrays, a column outside [0, N) and rows that are not strictly ascending are the caller's to exclude (a column >= N indexes past the row
+ * pointers and the bit maps); egnn_pytorch_amd.SparseAdjacency validates them. */
+size_t egnn_adj_csr_workspace_bytes(int G, int N);
+int egnn_adj_csr_square_count(const int64_t* cur_rowptr, const int32_t* cur_col, const int64_t* lab_rowptr, const int32_t* lab_col,
+                              int G, int N, int64_t* nxt_rowptr, int64_t* new_lab_rowptr, int64_t* totals, void* workspace,
+                              size_t workspace_bytes, int flags, void* stream);
+int egnn_adj_csr_square_fill(const int64_t* cur_rowptr, const int32_t* cur_col, const int64_t* lab_rowptr, const int32_t* lab_col,
+                             const uint8_t* lab_val, int G, int N, int degree, const int64_t* nxt_rowptr, int32_t* nxt_col,
+                             int64_t nxt_nnz, const int64_t* new_lab_rowptr, int32_t* new_lab_col, uint8_t* new_lab_val,
+                             int64_t new_lab_nnz, void* workspace, size_t workspace_bytes, int flags, void* stream);
+/* The degree labels of the selected pairs: out[b,i,k] = the label of pair (i, j), j = idx[b,i,k] (idx NULL: dense, j = k, K = N), found
+ * by binary search in row i of the label CSR, 0 where the row does not hold j.  rowptr_graph_stride = 0 (G = 1) or N + 1.  out (B,N,K)
+ * bytes: what the _slot entries below read.  rowptr / col are not checked (as above: sorted rows, offsets inside col / val). */
+int egnn_csr_slot_labels_u8(const int64_t* rowptr, const int32_t* col, const uint8_t* val, int64_t rowptr_graph_stride,
+                            const int32_t* idx, int B, int N, int K, uint8_t* out, void* stream);
 
 /* Replaces `int(adj_mat.float().sum(dim=-1).max().item())` (egnn_pytorch.py:249; the diagonal is
  * counted when set).  adj: (rows, N) bytes.  *out_dev (device int32) receives the maximum row sum;
@@ -437,6 +489,23 @@ int egnn_edge_features_grad_f64(const double* g, int64_t ld, const int64_t* edge
                                 const uint8_t* adj_deg, int V2, int d2, const int32_t* idx, int B, int N, int K,
                                 double* g_tok_emb, double* g_deg_emb, double* g_edges, double* work, int64_t* work_floats,
                                 void* stream);
+/* The four entries above with the adjacency-degree labels given per SLOT: slot_deg (B,N,K) bytes, the label of pair (i, idx[b,i,k]) at
+ * [b,i,k] (egnn_csr_slot_labels_u8), instead of the (B,N,N) map read at [b,i,j].  Every other argument as above; the same kernels with
+ * the same G, walk and order of every sum, so the outputs are the bits of the entries above called with the dense map. */
+int egnn_edge_features_gather_slot_f32(const float* edges, const int64_t* edge_tok, const float* edge_tok_emb, int d1,
+                                       const uint8_t* slot_deg, const float* adj_deg_emb, int d2, const int32_t* idx,
+                                       int B, int N, int K, float* out, void* stream);
+int egnn_edge_features_gather_slot_f64(const double* edges, const int64_t* edge_tok, const double* edge_tok_emb, int d1,
+                                       const uint8_t* slot_deg, const double* adj_deg_emb, int d2, const int32_t* idx,
+                                       int B, int N, int K, double* out, void* stream);
+int egnn_edge_features_grad_slot_f32(const float* g, int64_t ld, const int64_t* edge_tok, int V1, int d1,
+                                     const uint8_t* slot_deg, int V2, int d2, const int32_t* idx, int B, int N, int K,
+                                     float* g_tok_emb, float* g_deg_emb, float* g_edges, float* work, int64_t* work_floats,
+                                     void* stream);
+int egnn_edge_features_grad_slot_f64(const double* g, int64_t ld, const int64_t* edge_tok, int V1, int d1,
+                                     const uint8_t* slot_deg, int V2, int d2, const int32_t* idx, int B, int N, int K,
+                                     double* g_tok_emb, double* g_deg_emb, double* g_edges, double* work, int64_t* work_floats,
+                                     void* stream);
 
 /* Backward of the edge pass without anything of size E x H in memory (autograd of egnn_pytorch.py:279-287;
  * csrc/edge_bwd.hip).  One call = one pass over a list of L entries (edges) grouped by a key node: by the source node i
