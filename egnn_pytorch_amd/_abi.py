@@ -41,7 +41,7 @@ SYMBOLS = (
     "egnn_edge_hidden_bwd2_f32", "egnn_edge_hidden_bwd2_f64",
     "egnn_induced_attn_bwd_f32", "egnn_induced_attn_bwd_work_floats", "egnn_token_attn_bwd_chunks", "egnn_token_attn_bwd_f32", "egnn_gelu_bwd_f32",
     "egnn_layer_norm_bwd_parts", "egnn_layer_norm_bwd_f32",
-    "egnn_knn_select_csr_f32", "egnn_knn_select_csr_f64",
+    "egnn_knn_select_csr_f32", "egnn_knn_select_csr_f64", "egnn_knn_select_grid_csr_f32",
     "egnn_adj_csr_workspace_bytes", "egnn_adj_csr_square_count", "egnn_adj_csr_square_fill", "egnn_csr_slot_labels_u8",
     "egnn_edge_features_gather_slot_f32", "egnn_edge_features_gather_slot_f64", "egnn_edge_features_grad_slot_f32",
     "egnn_edge_features_grad_slot_f64",
@@ -434,6 +434,9 @@ def load():
     lib.egnn_knn_grid_workspace_bytes.argtypes = [c_int, c_int, c_int]
     lib.egnn_knn_select_grid_f32.restype = c_int
     lib.egnn_knn_select_grid_f32.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.egnn_knn_select_grid_csr_f32.restype = c_int
+    lib.egnn_knn_select_grid_csr_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                                 c_void_p, c_size_t, c_void_p]
     lib.egnn_linear_f64.restype = c_int
     lib.egnn_linear_f64.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int,
                                     c_int, c_void_p]

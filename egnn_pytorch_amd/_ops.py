@@ -411,7 +411,7 @@ def knn_select_stream(coors, mask, adj_mat, k, out=None):
     return _knn_select(coors, mask, adj_mat, k, out, "egnn_knn_select_stream")
 
 
-KNN_GRID_KMAX = 128           # the K limit of egnn_knn_select_grid_f32 (csrc/knn_grid.hip: KG_KMAX)
+KNN_GRID_KMAX = 128           # the K limit of egnn_knn_select_grid_f32 / _grid_csr_f32 (csrc/knn_grid.hip: KG_KMAX)
 
 
 def knn_grid_workspace(b, n, k, device):
@@ -419,13 +419,21 @@ def knn_grid_workspace(b, n, k, device):
     return empty(_abi.load().egnn_knn_grid_workspace_bytes(b, n, k), dtype=torch.uint8, device=device)
 
 
-def knn_select_grid(coors, mask, k, out=None, ws=None):
-    """knn_select on the cell-grid kernels (egnn_knn_select_grid_f32): fp32 coordinates, coor_dim == 3, no adjacency, K <= 128; the
+def knn_select_grid(coors, mask, k, out=None, ws=None, adj=None):
+    """knn_select on the cell-grid kernels (egnn_knn_select_grid_f32): fp32 coordinates, coor_dim == 3, K <= 128; the
     same outputs bit for bit at a cost per row bounded by its neighbourhood, not by N.  ws: the workspace (`knn_grid_workspace`), allocated
-    here on the current stream when None -- a caller that runs this on a side stream allocates `out` and `ws` on its launch stream."""
+    here on the current stream when None -- a caller that runs this on a side stream allocates `out` and `ws` on its launch stream.
+    adj: None or a SparseAdjacency (egnn_knn_select_grid_csr_f32: the outputs of `knn_select_csr`); a dense map has no grid entry."""
     b, n, cdim = coors.shape
     if coors.dtype != torch.float32:
         raise TypeError(f"knn_select_grid takes float32 coordinates (got {coors.dtype})")
+    if adj is not None:
+        if not isinstance(adj, SparseAdjacency):
+            raise TypeError("knn_select_grid takes the adjacency as a SparseAdjacency (a dense map selects on the all-pairs kernels)")
+        if adj.n != n or (adj.batched and adj.num_graphs != b):
+            raise ValueError(f"adj_mat shape {tuple(adj.shape)} != {(b, n, n)} or {(n, n)}")
+        if adj.device != coors.device:
+            raise RuntimeError(f"Expected all tensors to be on the same device: coors is on {coors.device}, adj_mat on {adj.device}")
     if out is not None:
         idx, rank = out
     else:
@@ -434,6 +442,13 @@ def knn_select_grid(coors, mask, k, out=None, ws=None):
     m8 = _u8(mask)
     if ws is None:
         ws = knn_grid_workspace(b, n, k, coors.device)
+    if adj is not None:
+        with _timed("knn_select_grid"):
+            rc = _abi.load().egnn_knn_select_grid_csr_f32(_ptr(coors), _ptr(m8), _ptr(adj.rowptr), _ptr(adj.col) if adj.col.numel() else None,
+                                                          0 if adj.shared else n + 1, b, n, k, cdim, _ptr(idx), _ptr(rank), _ptr(ws),
+                                                          ws.numel(), _stream())
+        _abi.check(rc, "egnn_knn_select_grid_csr_f32")
+        return idx, rank
     with _timed("knn_select_grid"):
         rc = _abi.load().egnn_knn_select_grid_f32(_ptr(coors), _ptr(m8), b, n, k, cdim, _ptr(idx), _ptr(rank), _ptr(ws), ws.numel(), _stream())
     _abi.check(rc, "egnn_knn_select_grid_f32")

@@ -326,6 +326,11 @@ int egnn_pack_rows_launch(const float* X, int64_t ldx, const float* m_i, const f
 // cell-grid selection (knn_grid.hip) hands over; the other rows of idx_out / rank_out are left as they are
 int egnn_knn_stream_flagged_f32(const float* coors, const uint8_t* mask, int B, int N, int K, const uint8_t* rowflag, int32_t* idx_out,
                                 float* rank_out, void* stream);
+// ... and the same with the adjacency as CSR rows (rowptr / col / stride as in egnn_knn_select_csr_f32): the rows the cell-grid selection
+// with CSR rows hands over, masked rows included
+int egnn_knn_stream_flagged_csr_f32(const float* coors, const uint8_t* mask, const int64_t* rowptr, const int32_t* col,
+                                    int64_t rowptr_graph_stride, int B, int N, int K, const uint8_t* rowflag, int32_t* idx_out,
+                                    float* rank_out, void* stream);
 
 static inline int egnn_launch_status() {
     hipError_t e = hipGetLastError();

@@ -1,4 +1,5 @@
-// Cell-grid k-NN selection (gfx950): fp32 coordinates, coor_dim == 3, no adjacency, optional mask.  Outputs bit-identical to the
+// Cell-grid k-NN selection (gfx950): fp32 coordinates, coor_dim == 3, optional mask, no adjacency or one given as CSR rows (below: "With
+// CSR rows").  Outputs bit-identical to the
 // streaming selection (knn_stream.hip) for every input with finite coordinates, at a cost per row that is bounded by the row's
 // neighbourhood instead of N.  Distances are egnn_sqdist and keys egnn_knn_rank / egnn_rank_key (egnn_common.h), like every
 // other selection kernel: equality is by construction.
@@ -32,6 +33,19 @@
 // -- is off by < 2^-21.  Together < 2^-9; the kernel uses (r h)^2 (1 - 2^-8).  A row stops once its K-th best d^2 is STRICTLY below
 // that: every unvisited node then has a computed d^2 above the K-th key, so none can equal it and the lowest-index tie policy is
 // decided among visited nodes only.  A row that never stops has visited every cell.
+//
+// With CSR rows (kg_search_kernel<true>, egnn_knn_select_grid_csr_f32).  The ranking value of (i, j) is overwritten AFTER the mask: -1 for
+// j == i, 0 for j in row i of the adjacency -- an adjacent masked node ranks 0, a masked row keeps itself and its bonds.  The build passes
+// do not change (only valid nodes go into the grid).  A valid row seeds its buffer with (key(-1), i) and (key(0), j) for the first
+// min(len, K) columns j != i of its row (ascending on one key: the first are the best; <= K + 1 entries, the buffer holds max(2 K, K + 64))
+// and marks it dirty; in the cells it drops i and every member of the row -- a binary search of the sorted columns, only for a candidate
+// that already passed comp < tau -- so composites stay unique.  The stop rule is untouched: a K-th key of -1 or 0 is below
+// (r h)^2 (1 - 2^-8) after ring 1, so a saturated row stops there, but it DOES visit ring 1: a node outside the row that coincides with i
+// (d^2 = +0) has the key of an adjacent node and enters by its lower index.  Adjacent nodes the search has not visited are seeds already,
+// so the rule's argument about unvisited nodes is about non-adjacent ones, as before.  A masked row of a graph the grid answers is written
+// directly: i at -1, the columns != i at 0, then the lowest indices outside both at 1e5, cut at K -- one thread per entry, a binary search
+// in the first K + 1 columns, whatever the degree.  Flagged rows (masked rows of a flagged graph too) go to the streaming kernel's flagged
+// CSR instantiation.  The instantiation without an adjacency is the code it was: its three CSR arguments are appended and never read.
 #include "egnn_common.h"
 
 namespace {
@@ -295,10 +309,27 @@ __device__ __forceinline__ void kg_compact(uint64_t* buf, uint64_t* tmp, int& cn
     if (n == K) tau = buf[K - 1];
 }
 
+// j among the `len` strictly ascending columns at `col`
+__device__ __forceinline__ bool kg_csr_member(const int32_t* __restrict__ col, int len, int j)
+{
+    int lo = 0, hi = len;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (col[mid] < j) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < len && col[lo] == j;
+}
+
+// CSR: every row has an adjacency, row i of graph b = the columns col[rowptr[b rp_stride + i] .. rowptr[b rp_stride + i + 1]); without
+// it the three last arguments are not read.
+template <bool CSR>
 __global__ __launch_bounds__(KG_THREADS) void kg_search_kernel(const uint8_t* __restrict__ mask, const KgHdr* __restrict__ hdr,
                                                                const int* __restrict__ cell_of, const int* __restrict__ start,
                                                                const float4* __restrict__ sorted, uint8_t* __restrict__ rowflag, int N, int K,
-                                                               int32_t* __restrict__ idx_out, float* __restrict__ rank_out)
+                                                               int32_t* __restrict__ idx_out, float* __restrict__ rank_out,
+                                                               const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                               int64_t rp_stride)
 {
     __shared__ uint64_t sbuf[KG_THREADS / 64][KG_CAP];
     __shared__ uint64_t stmp[KG_THREADS / 64][KG_KMAX];
@@ -317,8 +348,50 @@ __global__ __launch_bounds__(KG_THREADS) void kg_search_kernel(const uint8_t* __
             const int rr = o / K, k = o - rr * K, i = base + rr;
             if (i < N && !mb[i]) {
                 const size_t ob = ((size_t)b * N + i) * K;
-                idx_out[ob + k] = k;
-                rank_out[ob + k] = 1e5f;
+                if constexpr (CSR) {
+                    // ... behind i itself at -1 and the row's columns != i at 0: entry k of the merge of 0, 1, 2, ... against the sorted
+                    // row.  Only the first K + 1 columns can matter; indices at 1e5 appear only when the whole row lies among them.
+                    const int64_t* rp = rowptr + (size_t)b * rp_stride + i;
+                    const int64_t lo = rp[0];
+                    const int64_t len = rp[1] - lo;
+                    const int32_t* cr = col + lo;                          // (not read when len == 0: col may be NULL)
+                    const int lim = (int)(len < (int64_t)K + 1 ? len : (int64_t)K + 1);
+                    int ip = 0;                                           // columns below i among the first lim
+                    for (int hi = lim; ip < hi;) {
+                        const int mid = (ip + hi) >> 1;
+                        if (cr[mid] < i) ip = mid + 1;
+                        else hi = mid;
+                    }
+                    const bool diag = ip < lim && cr[ip] == i;
+                    const int nadj = lim - (diag ? 1 : 0);
+                    int j;
+                    float rk;
+                    if (k == 0) {
+                        j = i;
+                        rk = -1.f;
+                    } else if (k - 1 < nadj) {
+                        const int t = k - 1;
+                        j = cr[(diag && t >= ip) ? t + 1 : t];
+                        rk = 0.f;
+                    } else {
+                        // the m-th index outside S = {i} u row (sorted, L entries): m + t for the first t with S[t] - t > m
+                        const int m = k - 1 - nadj, L = lim + (diag ? 0 : 1);
+                        auto S = [&](int t) -> int { return diag ? cr[t] : (t < ip ? cr[t] : (t == ip ? i : cr[t - 1])); };
+                        int t = 0;
+                        for (int hi = L; t < hi;) {
+                            const int mid = (t + hi) >> 1;
+                            if (S(mid) - mid > m) hi = mid;
+                            else t = mid + 1;
+                        }
+                        j = m + t;
+                        rk = 1e5f;
+                    }
+                    idx_out[ob + k] = j;
+                    rank_out[ob + k] = rk;
+                } else {
+                    idx_out[ob + k] = k;
+                    rank_out[ob + k] = 1e5f;
+                }
                 if (k == 0) fb[i] = 0;
             }
         }
@@ -338,6 +411,32 @@ __global__ __launch_bounds__(KG_THREADS) void kg_search_kernel(const uint8_t* __
         int cnt = 0;
         bool dirty = false;
         uint64_t tau = ~0ull;
+        const int32_t* cr = nullptr;
+        int clen = 0;
+        if constexpr (CSR) {
+            // the seeds: i itself at -1, then the first K columns != i at 0 -- ascending and on one key, so the first are the best; the
+            // grid's candidates never repeat them (below).  At most K + 1 entries, sorted by the first compaction.
+            const int64_t* rp = rowptr + (size_t)b * rp_stride + i;
+            const int64_t lo = rp[0];
+            clen = (int)(rp[1] - lo);
+            cr = col + lo;                                                // (not read when clen == 0: col may be NULL)
+            if (lane == 0) buf[0] = ((uint64_t)egnn_rank_key(-1.f) << 32) | (uint32_t)i;
+            cnt = 1;
+            const int lim = min(clen, K + 1);
+            for (int t0 = 0; t0 < lim; t0 += 64) {
+                const int t = t0 + lane;
+                const int j = t < lim ? cr[t] : i;
+                const bool pass = j != i;
+                const uint64_t bal = __ballot(pass);
+                if (pass) {
+                    const int below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
+                    buf[cnt + below] = ((uint64_t)egnn_rank_key(0.f) << 32) | (uint32_t)j;
+                }
+                cnt += __builtin_popcountll(bal);
+            }
+            cnt = min(cnt, K + 1);                                        // (the K + 1-th column, kept when the diagonal was not among them)
+            dirty = true;
+        }
         for (int r = 1;; ++r) {
             const int nrow = 2 * r + 1;
             const int nouter = nrow * nrow;
@@ -385,6 +484,8 @@ __global__ __launch_bounds__(KG_THREADS) void kg_search_kernel(const uint8_t* __
                             const uint32_t key = egnn_rank_key(egnn_knn_rank<float>(d, true, true, nullptr, i, j));
                             comp = ((uint64_t)key << 32) | (uint32_t)j;
                             pass = comp < tau;
+                            // (CSR: i and its row are seeded; the row is searched only for a candidate that would be kept)
+                            if constexpr (CSR) pass = pass && j != i && !kg_csr_member(cr, clen, j);
                         }
                         const uint64_t bal = __ballot(pass);
                         if (pass) {
@@ -405,7 +506,8 @@ __global__ __launch_bounds__(KG_THREADS) void kg_search_kernel(const uint8_t* __
             }
             if (r >= rmax) break;
         }
-        // (every cell visited or the rule above met; nvalid >= K, so K entries, sorted)
+        // (every cell visited or the rule above met; nvalid >= K, so K entries, sorted -- CSR: the seeds and the valid nodes outside
+        // them are distinct and no fewer)
         kg_wave_sync();
         const float d2k = egnn_rank_from_key((uint32_t)(tau >> 32));
         const bool hand_over = cnt < K || (d2k >= 1e5f && H.nvalid < N);
@@ -431,11 +533,13 @@ extern "C" size_t egnn_knn_grid_workspace_bytes(int B, int N, int K)
     return kg_layout(B, N).total;
 }
 
-extern "C" int egnn_knn_select_grid_f32(const float* coors, const uint8_t* mask, int B, int N, int K, int coor_dim, int32_t* idx_out,
-                                        float* rank_out, void* workspace, size_t workspace_bytes, void* stream)
+// both entries: rowptr == NULL selects without an adjacency
+static int kg_select(const float* coors, const uint8_t* mask, const int64_t* rowptr, const int32_t* col, int64_t rp_stride, int B, int N,
+                     int K, int coor_dim, int32_t* idx_out, float* rank_out, void* workspace, size_t workspace_bytes, void* stream)
 {
     if (!coors || !idx_out || !rank_out || !workspace) return EGNN_E_NULLPTR;
     if (B <= 0 || N <= 0 || K <= 0 || K > N) return EGNN_E_SHAPE;
+    if (rowptr && rp_stride != 0 && rp_stride != (int64_t)N + 1) return EGNN_E_SHAPE;
     if (coor_dim != 3 || K > KG_KMAX || B > 65535) return EGNN_E_UNSUPPORTED;
     const KgLayout L = kg_layout(B, N);
     if (workspace_bytes < L.total) return EGNN_E_SHAPE;
@@ -456,9 +560,29 @@ extern "C" int egnn_knn_select_grid_f32(const float* coors, const uint8_t* mask,
     hipLaunchKernelGGL(kg_count_kernel, nodes, dim3(KG_THREADS), 0, st, coors, mask, N, hdr, cell_of, cnt);
     hipLaunchKernelGGL(kg_scan_kernel, dim3((unsigned)B), dim3(1024), 0, st, N, hdr, cnt, start);
     hipLaunchKernelGGL(kg_place_kernel, nodes, dim3(KG_THREADS), 0, st, coors, N, hdr, cell_of, cnt, start, sorted);
-    hipLaunchKernelGGL(kg_search_kernel, dim3((unsigned)((N + KG_SLOTS - 1) / KG_SLOTS), (unsigned)B), dim3(KG_THREADS), 0, st, mask, hdr,
-                       cell_of, start, sorted, rowflag, N, K, idx_out, rank_out);
+    const dim3 slots((unsigned)((N + KG_SLOTS - 1) / KG_SLOTS), (unsigned)B);
+    if (rowptr)
+        hipLaunchKernelGGL(kg_search_kernel<true>, slots, dim3(KG_THREADS), 0, st, mask, hdr, cell_of, start, sorted, rowflag, N, K, idx_out,
+                           rank_out, rowptr, col, rp_stride);
+    else
+        hipLaunchKernelGGL(kg_search_kernel<false>, slots, dim3(KG_THREADS), 0, st, mask, hdr, cell_of, start, sorted, rowflag, N, K, idx_out,
+                           rank_out, (const int64_t*)nullptr, (const int32_t*)nullptr, (int64_t)0);
     int rc = egnn_launch_status();
     if (rc != EGNN_OK) return rc;
+    if (rowptr) return egnn_knn_stream_flagged_csr_f32(coors, mask, rowptr, col, rp_stride, B, N, K, rowflag, idx_out, rank_out, stream);
     return egnn_knn_stream_flagged_f32(coors, mask, B, N, K, rowflag, idx_out, rank_out, stream);
+}
+
+extern "C" int egnn_knn_select_grid_f32(const float* coors, const uint8_t* mask, int B, int N, int K, int coor_dim, int32_t* idx_out,
+                                        float* rank_out, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return kg_select(coors, mask, nullptr, nullptr, 0, B, N, K, coor_dim, idx_out, rank_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int egnn_knn_select_grid_csr_f32(const float* coors, const uint8_t* mask, const int64_t* rowptr, const int32_t* col,
+                                            int64_t rowptr_graph_stride, int B, int N, int K, int coor_dim, int32_t* idx_out, float* rank_out,
+                                            void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!rowptr) return EGNN_E_NULLPTR;
+    return kg_select(coors, mask, rowptr, col, rowptr_graph_stride, B, N, K, coor_dim, idx_out, rank_out, workspace, workspace_bytes, stream);
 }

@@ -16,6 +16,8 @@
 // R query rows per workgroup share every pass (R histograms in LDS; lane l works for row l % R on the candidates j = l / R + S t,
 // S = 256 / R), so the coordinate stream is read once for R rows.  Deterministic: only integer counters are atomic, and the output
 // order is the (key, index) order.
+// Instantiations: the adjacency as a byte row or as CSR rows (CSR), every row or only the rows a flag byte names (FL: the rows the cell-grid
+// selection hands over, knn_grid.hip) -- all four combinations; `rowflag` and `col` are separate arguments.
 #include "egnn_common.h"
 
 namespace {
@@ -32,18 +34,19 @@ template <> struct KsKey<double> { typedef uint64_t type; static constexpr int V
 // FL: only the rows with rowflag[b N + i] != 0 are selected and written (the rows the cell-grid selection hands over, knn_grid.hip); a
 // workgroup without such a row returns at once.
 // CSR: the adjacency as sorted column ranges (egnn_knn_select_csr_f32 / _f64) -- adj = rowptr, int64 absolute offsets, (N + 1) per graph
-// at a graph stride of adj_bstride entries (0: one graph's rows for all); rowflag's place holds the flat int32 column array (never with
-// FL).  Every row then has an adjacency; its ranking values come from the merging overload of egnn_knn_rank.
-template <bool CSR> struct KsAdj { typedef uint8_t adj_t; typedef uint8_t aux_t; };
-template <> struct KsAdj<true> { typedef int64_t adj_t; typedef int32_t aux_t; };
+// at a graph stride of adj_bstride entries (0: one graph's rows for all); col = the flat int32 column array (NULL without CSR).  Every
+// row then has an adjacency; its ranking values come from the merging overload of egnn_knn_rank.
+// FL and CSR together: the rows the cell-grid selection with CSR rows hands over (egnn_knn_select_grid_csr_f32) -- masked rows
+// included, which have an adjacency like every other row.
+template <bool CSR> struct KsAdj { typedef uint8_t adj_t; };
+template <> struct KsAdj<true> { typedef int64_t adj_t; };
 
 template <typename T, int CDM, bool FL = false, bool CSR = false>
 __global__ __launch_bounds__(KS_THREADS) void knn_select_stream_kernel(
     const T* __restrict__ coors, const uint8_t* __restrict__ mask, const typename KsAdj<CSR>::adj_t* __restrict__ adj, int64_t adj_bstride,
     int N, int K, int C, int R, int IBP, int32_t* __restrict__ idx_out, T* __restrict__ rank_out,
-    const typename KsAdj<CSR>::aux_t* __restrict__ rowflag)
+    const uint8_t* __restrict__ rowflag, const int32_t* __restrict__ col)
 {
-    static_assert(!(FL && CSR), "the flagged rows have no adjacency");
     typedef typename KsKey<T>::type key_t;
     constexpr int KB = 8 * (int)sizeof(key_t);           // key bits
     constexpr int KD = KB / 8;                           // key digits
@@ -87,7 +90,7 @@ __global__ __launch_bounds__(KS_THREADS) void knn_select_stream_kernel(
         if (i < N) {
             const int64_t* rp = adj + (size_t)b * adj_bstride + i;
             const int64_t lo = rp[0];
-            csr.col = rowflag + lo;
+            csr.col = col + lo;
             csr.len = (int)(rp[1] - lo);
         }
     } else {
@@ -233,7 +236,7 @@ __global__ __launch_bounds__(KS_THREADS) void knn_select_stream_kernel(
 
 template <typename T, bool CSR = false>
 int knn_stream_launch(const T* coors, const uint8_t* mask, const typename KsAdj<CSR>::adj_t* adj, int64_t adj_bstride, int B, int N, int K,
-                      int C, int32_t* idx_out, T* rank_out, void* stream, const typename KsAdj<CSR>::aux_t* rowflag = nullptr)
+                      int C, int32_t* idx_out, T* rank_out, void* stream, const uint8_t* rowflag = nullptr, const int32_t* col = nullptr)
 {
     if (!coors || !idx_out || !rank_out) return EGNN_E_NULLPTR;
     if (B <= 0 || N <= 0 || K <= 0) return EGNN_E_SHAPE;
@@ -254,11 +257,9 @@ int knn_stream_launch(const T* coors, const uint8_t* mask, const typename KsAdj<
     if constexpr (sizeof(T) == 4) {
         if (C == 3) kern = knn_select_stream_kernel<T, 3, false, CSR>;
         else if (C <= 8) kern = knn_select_stream_kernel<T, 8, false, CSR>;
-        if constexpr (!CSR) {
-            if (rowflag) {
-                if (C != 3) return EGNN_E_UNSUPPORTED;
-                kern = knn_select_stream_kernel<T, 3, true>;
-            }
+        if (rowflag) {
+            if (C != 3) return EGNN_E_UNSUPPORTED;
+            kern = knn_select_stream_kernel<T, 3, true, CSR>;
         }
     }
     if (lds > 64 * 1024) {
@@ -267,7 +268,7 @@ int knn_stream_launch(const T* coors, const uint8_t* mask, const typename KsAdj<
     }
     const dim3 grid((unsigned)((N + R - 1) / R), (unsigned)B);
     hipLaunchKernelGGL(kern, grid, dim3(KS_THREADS), lds, static_cast<hipStream_t>(stream), coors, mask, adj, adj_bstride, N, K, C, R,
-                       IBP, idx_out, rank_out, rowflag);
+                       IBP, idx_out, rank_out, rowflag, col);
     return egnn_launch_status();
 }
 
@@ -278,6 +279,14 @@ int egnn_knn_stream_flagged_f32(const float* coors, const uint8_t* mask, int B, 
 {
     if (!rowflag) return EGNN_E_NULLPTR;
     return knn_stream_launch<float>(coors, mask, nullptr, 0, B, N, K, 3, idx_out, rank_out, stream, rowflag);
+}
+
+int egnn_knn_stream_flagged_csr_f32(const float* coors, const uint8_t* mask, const int64_t* rowptr, const int32_t* col,
+                                    int64_t rowptr_graph_stride, int B, int N, int K, const uint8_t* rowflag, int32_t* idx_out,
+                                    float* rank_out, void* stream)
+{
+    if (!rowflag || !rowptr) return EGNN_E_NULLPTR;
+    return knn_stream_launch<float, true>(coors, mask, rowptr, rowptr_graph_stride, B, N, K, 3, idx_out, rank_out, stream, rowflag, col);
 }
 
 extern "C" int egnn_knn_select_stream_f32(const float* coors, const uint8_t* mask, const uint8_t* adj, int64_t adj_batch_stride, int B,
@@ -299,7 +308,7 @@ static int knn_csr(const T* coors, const uint8_t* mask, const int64_t* rowptr, c
 {
     if (!rowptr) return EGNN_E_NULLPTR;
     if (N > 0 && rowptr_graph_stride != 0 && rowptr_graph_stride != (int64_t)N + 1) return EGNN_E_SHAPE;
-    return knn_stream_launch<T, true>(coors, mask, rowptr, rowptr_graph_stride, B, N, K, C, idx_out, rank_out, stream, col);
+    return knn_stream_launch<T, true>(coors, mask, rowptr, rowptr_graph_stride, B, N, K, C, idx_out, rank_out, stream, nullptr, col);
 }
 
 extern "C" int egnn_knn_select_csr_f32(const float* coors, const uint8_t* mask, const int64_t* rowptr, const int32_t* col,

@@ -115,7 +115,7 @@ int egnn_knn_select_csr_f32(const float* coors, const uint8_t* mask, const int64
 int egnn_knn_select_csr_f64(const double* coors, const uint8_t* mask, const int64_t* rowptr, const int32_t* col,
                             int64_t rowptr_graph_stride, int B, int N, int K, int coor_dim, int32_t* idx_out, double* rank_out,
                             void* stream);
-/* The cell-grid selection (csrc/knn_grid.hip): fp32 coordinates, coor_dim == 3, no adjacency, K <= 128, any B <= 65 535 and N.  Outputs
+/* The cell-grid selection (csrc/knn_grid.hip): fp32 coordinates, coor_dim == 3, no adjacency (with CSR rows: the entry below), K <= 128, any B <= 65 535 and N.  Outputs
  * bit-identical to egnn_knn_select_stream_f32 for every input with finite coordinates (the same distances and keys, ties to the lowest
  * index), at a cost per row bounded by the row's neighbourhood instead of N: the valid nodes are counting-sorted into a uniform grid of
  * cells (16 nodes per cell on average, outliers clamped into the border cells of a mean +- 4 sd box) and each row visits the cells at
@@ -132,6 +132,25 @@ int egnn_knn_select_csr_f64(const double* coors, const uint8_t* mask, const int6
 size_t egnn_knn_grid_workspace_bytes(int B, int N, int K);
 int egnn_knn_select_grid_f32(const float* coors, const uint8_t* mask, int B, int N, int K, int coor_dim, int32_t* idx_out,
                              float* rank_out, void* workspace, size_t workspace_bytes, void* stream);
+/* The cell-grid selection for a call with an adjacency given as CSR rows: rowptr, col and rowptr_graph_stride exactly as in
+ * egnn_knn_select_csr_f32 (int64 absolute offsets, stride 0 or N + 1; columns strictly ascending, every entry in [0, N); col may be NULL
+ * when every row is empty; a diagonal entry is allowed and ignored; neither array is read on the host), every other argument as in
+ * egnn_knn_select_grid_f32.  Outputs bit-identical to egnn_knn_select_csr_f32 for every input with finite coordinates: i itself ranks
+ * -1, the nodes of row i rank 0 -- masked ones included, and in masked rows too -- and a node outside the row that coincides with i
+ * (d^2 = +0) ties with them by index.  The grid holds the valid nodes, as without an adjacency.  A valid row seeds its candidate list
+ * with itself and the first min(len, K) columns of its row other than i (ascending on one key: the first are the best) and drops i and
+ * every member of its row from the cells it visits (a binary search of the row, only for candidates that would enter the list); the stop
+ * rule is unchanged, so a row whose seeds fill K stops after ring 1, which it still visits for the coincident nodes.  A masked row of a
+ * graph the grid answers is written directly: i, the row's columns other than i at 0, then the lowest indices outside both at 1e5, cut
+ * at K (a merge of 0, 1, 2, ... against the sorted row: work per row independent of its degree).  Flags and hand-over as in
+ * egnn_knn_select_grid_f32, per graph and per row; the flagged rows are finished by the streaming kernel on the CSR rows.  The CSR is read
+ * in place: workspace = egnn_knn_grid_workspace_bytes(B, N, K), unchanged.  No host read-back, seven launches, deterministic.
+ * Errors, all returned before any launch: EGNN_E_NULLPTR (coors, rowptr, outputs, workspace), EGNN_E_SHAPE (non-positive sizes, K > N,
+ * a workspace that is too small, a stride other than 0 or N + 1), EGNN_E_UNSUPPORTED (coor_dim != 3, K > 128, B > 65 535), EGNN_E_ALIGN
+ * (a workspace that is not 16-byte aligned). */
+int egnn_knn_select_grid_csr_f32(const float* coors, const uint8_t* mask, const int64_t* rowptr, const int32_t* col,
+                                 int64_t rowptr_graph_stride, int B, int N, int K, int coor_dim, int32_t* idx_out, float* rank_out,
+                                 void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Sparse adjacency: the N-degree expansion of EGNN_Network (egnn_pytorch.py:414-427; egnn_adj_expand_u8 is its dense form) on CSR rows
