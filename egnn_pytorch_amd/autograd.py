@@ -780,6 +780,12 @@ class EGNNFunction(torch.autograd.Function):
         f64 = layer.float64_kernels()
         exact_path = f64 or _exact_active() or s_in > 16 or coors.shape[-1] > 8 or layer.m_dim > 64
         exact_native = bool(_NATIVE_EXACT and exact_path and s_in <= (40 if f64 else 80) and feats.is_cuda)
+        if native and feats.is_cuda:
+            # a single graph beyond the backward kernels' 2^31-byte tables: said here, before the first launch (where only the
+            # adjacency decides K, with K = 1: the projection table's bound holds for every K, `_backward_native` re-checks with the K it finds)
+            use_nn = layer.num_nearest_neighbors > 0 or layer.only_sparse_neighbors
+            k_known = feats.shape[1] if not use_nn else (1 if (adj_mat is not None and layer.only_sparse_neighbors) else layer.num_nearest_neighbors)
+            check_fused_training_shape(layer, feats.shape[0], feats.shape[1], min(k_known, feats.shape[1]))
         with torch.no_grad():
             node_out, coors_out, order, idx, rank, valid_radius, u_pre, proj = layer._forward_hip_checked(
                 feats, coors, edges if lookup is None else lookup, mask, adj_mat, order_hint, want_u=native or exact_native,
@@ -1381,6 +1387,71 @@ def _node_mlp_backward(layer, w, f, m_i, g_out, grads_by_id, drop=None, row0=0, 
     return (tg[0] if tg[0] is not None else torch.zeros_like(g_out)) + g_out, g_mi
 
 
+_I31 = 1 << 31
+
+
+def _fused_entry_capacity(g, n, k):
+    """the longest entry list one egnn_edge_bwd_pass_f32 call over g graphs is handed: egnn_dest_lists_capacity (csrc/entry_lists.hip)
+    restated -- every destination wastes less than one 16-entry tile, the list is whole rounds of 128 entries; the by-source list
+    (`entry_list`: ceil(K / 16) tiles per node) is never longer"""
+    tiles = g * (n * k // 16 + n) + 8
+    return (tiles * 16 + 127) // 128 * 128
+
+
+def _fused_chunk_fits(g, n, k, hp):
+    """what egnn_edge_bwd_pass_f32 (csrc/edge_bwd.hip) checks of a chunk of g graphs: E and L below 2^31, the (g N, 2 Hp) fp32
+    projection table below 2^31 bytes, the (L / 16, Hp) fp32 partial rows below 2^31 bytes"""
+    l = _fused_entry_capacity(g, n, k)
+    return g * n * k < _I31 and l < _I31 and g * n * 2 * hp * 4 < _I31 and (l >> 4) * hp * 4 < _I31
+
+
+def _fused_graphs_per_chunk(b, n, k, hp):
+    """How many of the b graphs (N nodes, K neighbours, padded hidden width Hp) one chunk of `_backward_native` takes: the largest
+    count, at most b, that `_fused_chunk_fits`; 0 when a single graph does not fit."""
+    if b <= 0 or not _fused_chunk_fits(1, n, k, hp):
+        return 0
+    # (each bound is linear in the count up to the rounding of the entry list: start from the closed form, then settle exactly)
+    g = min(b, (_I31 - 1) // (n * 2 * hp * 4), (_I31 - 1) // (n * k), (_I31 - 1) // ((n * k // 16 + n + 16) * hp * 4))
+    g = max(1, g)
+    while g > 1 and not _fused_chunk_fits(g, n, k, hp):
+        g -= 1
+    while g < b and _fused_chunk_fits(g + 1, n, k, hp):
+        g += 1
+    return g
+
+
+class FusedBackwardLimit(NotImplementedError):
+    """one graph is larger than the training kernels address"""
+
+
+def _fused_largest_graph(k, hp):
+    """the largest N for which one graph of K neighbours fits a chunk (`_fused_chunk_fits` is monotone in N: bisection)"""
+    lo, hi = 0, _I31 // (2 * hp * 4) + 1                                    # (the P table's bound alone admits no more)
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        if mid >= k and _fused_chunk_fits(1, mid, k, hp):
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo
+
+
+def _fused_limit_message(b, n, k, hp):
+    most = _fused_largest_graph(k, hp)
+    return (f"egnn_pytorch_amd: training a graph of {n} nodes (B = {b}, K = {k}, padded hidden width Hp = {hp}) is beyond the fused "
+            f"backward kernels: one graph's projection table (N x 2 Hp fp32 = {n * 2 * hp * 4} bytes) and partial rows "
+            f"({(n * k // 16 + n) * hp * 4} bytes) must each stay below 2^31 bytes (signed 32-bit offsets in egnn_edge_bwd_pass_f32), "
+            f"at most {most} nodes per graph at this K and width.  Split the graph, or run it under torch.no_grad(): inference has no such limit.")
+
+
+def check_fused_training_shape(layer, b, n, k):
+    """Raise FusedBackwardLimit -- before anything is launched -- when a single graph of this shape does not fit the native backward."""
+    from . import _abi
+    hp = _abi.load().egnn_padded_hidden(2 * (2 * layer.fourier_features + 2 * layer.dim + layer.edge_dim + 1))
+    if k > 0 and n > 0 and b > 0 and _fused_graphs_per_chunk(b, n, k, hp) == 0:
+        raise FusedBackwardLimit(_fused_limit_message(b, n, k, hp))
+
+
 def _backward_native(ctx, g_node, g_coors):
     """The backward on the HIP kernels (module docstring), per chunk of graphs:
        1. behind u = ctx.u_pre (edge_mlp's second Linear, written by the forward kernel): the pooled messages (egnn_edge_pool_f32), node_mlp
@@ -1391,7 +1462,7 @@ def _backward_native(ctx, g_node, g_coors):
           ->  d/d P_i, d/d P_j per node, d/d W_s, d/d scalars, d/d W_2;
        3. node-level products: d/d feats, d/d W_i, W_j, b_1 from the per-node sums and feats; d/d scalars -> coordinates (closed
           form when the distance is the only scalar, the scalars' own small graph otherwise) and edge features.
-    Every sum over edges has a fixed order.  Chunks: the kernels' tables stay below 2 GB (signed 32-bit offsets)."""
+    Every sum over edges has a fixed order.  Chunks: the kernels' tables stay below 2 GB (signed 32-bit offsets): `_fused_graphs_per_chunk`."""
     from . import _abi, _ops, _weights
     w = ctx.layer.packed_weights()
     orig_params = list(ctx.layer.parameters())
@@ -1439,13 +1510,13 @@ def _backward_native(ctx, g_node, g_coors):
     if len(ctx.saved_tensors) > 7 and ctx.saved_tensors[7].numel() and fused:
         proj_all = ctx.saved_tensors[7]                                   # (B N, 2 Hp): what the forward's edge pass read (P_i still as
                                                                           # (hi, lo) words when ctx.proj_words: decoded in `early` below)
-    if True:
-        # nothing of size E x H: graphs are only chunked to keep the P table below 4 GB (32-bit buffer offsets) and E below 2^31
-        # (the kernel addresses both with signed 32-bit scalar offsets)
-        step = max(1, min(b, int(((1 << 31) - 1) // (n * 2 * hp * 4)), int(((1 << 31) - 1) // (n * k)),
-                          int(((1 << 31) - 1) // ((n * k // 16 + n + 16) * hp * 4))))         # (... and the partial rows)
-        if _FUSED_MAX_GRAPHS > 0:
-            step = min(step, _FUSED_MAX_GRAPHS)
+    # nothing of size E x H: graphs are only chunked to keep the P table and the partial rows below 2 GB and E below 2^31
+    # (egnn_edge_bwd_pass_f32 addresses them with signed 32-bit scalar offsets): `_fused_graphs_per_chunk`
+    step = _fused_graphs_per_chunk(b, n, k, hp)
+    if step == 0:
+        raise FusedBackwardLimit(_fused_limit_message(b, n, k, hp))
+    if _FUSED_MAX_GRAPHS > 0:
+        step = min(step, _FUSED_MAX_GRAPHS)
     # the first Linear's blocks, zero padded to the kernel's hidden width Hp: everything below works on the contiguous
     # (E, Hp) buffers the kernel wrote (slicing [:, :H] first would copy 17 GB per use at the north-star shape)
     # (padded copies of parameters are kept with the packed weights: `w` is rebuilt whenever a parameter changes, so once per

@@ -1195,6 +1195,17 @@ extern "C" int egnn_padded_hidden(int H) { return (H + 31) / 32 * 32; }
 
 extern "C" int egnn_edge_mfmas(int S) { return S <= 1 ? 1 : (S <= 4 ? 3 : (S <= 5 ? 4 : (S <= 8 ? 6 : 12))); }
 
+// 1 when the kernels behind egnn_edge_fused_f32 can address one graph's rows of the projection table: they gather through a buffer
+// resource over the graph's N rows with 32-bit per-lane byte offsets (edge_body), so N * ldp * 4 has to fit 32 bits -- and, where a
+// tile carries the P_i rows of several nodes (6 <= K, K % 32 != 0), stay below the offset 0x80000000 that stands for "no such row,
+// read zeros".  Beyond it the plain-fp32 kernels (egnn_edge_exact_f32: 64-bit addresses) run the layer.
+extern "C" int egnn_edge_fused_covers(int N, int K, int64_t ldp)
+{
+    if (N <= 0 || K <= 0 || ldp <= 0) return 0;
+    const uint64_t bytes = (uint64_t)N * (uint64_t)ldp * 4u;
+    return bytes <= ((K >= 6 && K % 32 != 0) ? 0x80000000ull : 0xffffffffull) ? 1 : 0;
+}
+
 #endif
 
 // internal: the two compilations of this file (coordinate dimension 3 / generic), and the persistent wave-per-node kernel of the
@@ -1246,6 +1257,9 @@ int EGNN_EDGE_ENTRY(const egnn_edge_args* args, void* stream)
     hipStream_t s = static_cast<hipStream_t>(stream);
     // NM = ceil(3 S / 4) first-layer MFMAs, rounded up to an instantiated value; Wst must be laid out for that NM
     if (a.wst_terms != 4 * egnn_edge_mfmas(a.S)) return EGNN_E_SHAPE;
+    // one graph's table rows behind a 32-bit buffer resource (edge_body; the wave-per-node kernel holds the same limit): a larger graph
+    // is an error here, never a wrapped offset
+    if (!egnn_edge_fused_covers(a.N, a.K, a.ldp)) return EGNN_E_UNSUPPORTED;
 #if !defined(EGNN_EDGE_GENERIC_C) && !defined(EGNN_EDGE_DROP_TU) && EGNN_EDGE_PW
     if (a.algo == 0) {
         const int rc = egnn_edge_pw_launch(args, stream);

@@ -333,6 +333,8 @@ extern "C" int egnn_layer_forward_opts_f32(const egnn_layer_desc* desc, const eg
     const bool nearest = desc->num_nearest_neighbors > 0 || desc->only_sparse_neighbors;
     if (!nearest && K != N) return EGNN_E_SHAPE;                               // dense all-pairs path
     if (K > N) return EGNN_E_K_GT_N;                                           // torch.topk's error upstream (:258)
+    // a graph whose rows of the projection table the edge kernels' 32-bit offsets do not reach: said before anything is enqueued
+    if (K > 0 && !egnn_edge_fused_covers(N, K, 2 * (int64_t)x.Hp)) return EGNN_E_UNSUPPORTED;
     const Workspace w = carve(desc, x, B, N, K);
     if (workspace_bytes < w.bytes) return EGNN_E_SHAPE;
     if (reinterpret_cast<uintptr_t>(workspace) & 255) return EGNN_E_ALIGN;

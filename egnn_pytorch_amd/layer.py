@@ -392,6 +392,15 @@ class EGNN(nn.Module):
         return (_SLOT_PREP and _DENSE_PW and b * n >= 8192 and n % 32 == 0 and 32 <= n <= 4096 and cdim == 3 and self.m_dim <= 16
                 and self.edge_dim == 0 and self.fourier_features == 0 and not self.dropout_active() and b * n * n * 16 <= (1 << 28))
 
+    def _fused_covers(self, n, k):
+        """One graph's rows of the (N, 2 Hp) fp32 projection table fit the 32-bit byte offsets of the fused edge kernels
+        (egnn_edge_fused_covers: 4 GB per graph -- 258 111 nodes at dim 512; 2 GB where 6 <= K and K % 32 != 0).  A larger graph runs on the
+        plain-fp32 kernels, which address with 64 bits: the same layer several times slower, never a wrapped offset."""
+        h = 2 * (2 * self.fourier_features + 2 * self.dim + self.edge_dim + 1)
+        if k <= 0 or n * (h + 32) * 8 <= 0x80000000:                      # (every ordinary shape: no call into the library)
+            return True
+        return _abi.load().egnn_edge_fused_covers(n, k, 2 * _abi.load().egnn_padded_hidden(h)) == 1
+
     def _use_grid(self, coors, adj_mat, k):
         """the neighbour selection of this call on the cell grid (egnn_knn_select_grid_f32; with a SparseAdjacency
         egnn_knn_select_grid_csr_f32) rather than the all-pairs kernels.  A dense adjacency stays there: its byte map is N^2 already."""
@@ -490,7 +499,7 @@ class EGNN(nn.Module):
             return None
         desc, info, blob_dev, img = st
         kr = k, valid_radius = self._neighbour_count(n, adj_mat)
-        if k == 0:                                                  # (no messages: not covered by the C entry)
+        if k == 0 or not self._fused_covers(n, k):                  # (no messages / a graph beyond the fused kernels' offsets: not the C entry's)
             return self._forward_hip(feats, coors, edges, mask, adj_mat, order_hint, kr=kr)
         feats, coors = _ops.aligned(feats), _ops.aligned(coors)     # (any layout of the caller's: `_ops.aligned`)
         if edges is not None:
@@ -543,7 +552,9 @@ class EGNN(nn.Module):
         # more per-edge scalars than the split-fp16 edge kernels carry (2 fourier + 1 + edge_dim > 16, up to 160): the plain-fp32 kernels
         # ... and more than 8 coordinates (the fused kernels keep x_i - x_j in registers up to 8)
         # ... and heads wider than 64 message channels (the fused kernels hold up to four 16-channel accumulator tiles per edge tile)
-        wide_shape = 2 * self.fourier_features + 1 + self.edge_dim > 16 or coors.shape[-1] > 8 or self.m_dim > 64
+        # ... and a single graph whose rows of the projection table the fused kernels' 32-bit byte offsets do not reach (`_fused_covers`)
+        wide_shape = (2 * self.fourier_features + 1 + self.edge_dim > 16 or coors.shape[-1] > 8 or self.m_dim > 64
+                      or not self._fused_covers(feats.shape[1], kr[0]))
         if exact_active() or wide_shape:
             return self._forward_exact(feats, coors, edges, mask, adj_mat, kr, want_u=want_u, drop=drop)
         b, n, dim = feats.shape
@@ -692,7 +703,10 @@ class EGNN(nn.Module):
         k, valid_radius = kr
         idx = rank = None
         if self._use_nearest() and k > 0:
-            idx, rank = _ops.knn_select(coors, mask, adj_mat, k)
+            if self._use_grid(coors, adj_mat, k):                        # (the same list bit for bit, sub-quadratic: `_KNN_GRID_MIN_N`)
+                idx, rank = _ops.knn_select_grid(coors, mask, k, adj=adj_mat)
+            else:
+                idx, rank = _ops.knn_select(coors, mask, adj_mat, k)
         f32 = lambda t: t.detach().to(dtype).contiguous()                # noqa: E731  (the module's tensors in the compute dtype)
         node_out, coors_out, m_i = feats, coors, None
         u_pre = proj_keep = None                                         # want_u (forward under autograd): u (E, m_dim) and the projection table

@@ -300,6 +300,10 @@ int egnn_linear_hl_lda_f32(const void* A_hi, const void* A_lo, int Kp_a, const v
  * one case in which a caller may hand the projection a row mask -- the general kernel's tiles mix the P_i rows of several nodes in one
  * MFMA operand, where an unwritten row would reach its tile neighbours' edges.) */
 int egnn_edge_pw_covers(int B, int N, int K, int S, int fourier, int edge_dim, int m_dim, int coor_dim, int64_t ldp);
+/* 1 when egnn_edge_fused_f32 (either of its kernels) can address one graph's N rows of a projection table with row stride ldp floats:
+ * N * ldp * 4 <= 0xffffffff bytes (<= 0x80000000 for 6 <= K, K % 32 != 0).  Beyond it egnn_edge_fused_f32 and egnn_layer_forward_*_f32
+ * return EGNN_E_UNSUPPORTED before any launch; egnn_edge_exact_f32 (64-bit addresses) has no such limit. */
+int egnn_edge_fused_covers(int N, int K, int64_t ldp);
 int egnn_linear_hl_lda_rows_f32(const void* A_hi, const void* A_lo, int Kp_a, const void* W_hi, const void* W_lo,
                                 float w_inv_scale, const float* bias, const float* residual, int64_t ldr,
                                 float* C, int64_t ldc, void* C_hi, void* C_lo, int Kp_out, int64_t M, int N, int Kp,

@@ -430,3 +430,124 @@ def test_blob_assembled_from_the_torch_packer_equals_the_c_host_packer(kw):
     for name, _ in _abi.PackedInfo._fields_:
         assert getattr(info_c, name) == getattr(info_t, name), name
     assert blob_c.numel() == blob_t.numel() and torch.equal(blob_c, blob_t)
+
+
+# ------------------------------------------------------------------ size limits decided on the host (tests/test_gpu_offset_limits.py crosses them)
+def _bwd_pass_accepts(lib, g, n, k, hp):
+    """the three size conditions egnn_edge_bwd_pass_f32 (csrc/edge_bwd.hip) checks of a call over g graphs, with the longest entry list
+    such a call is handed (egnn_dest_lists_capacity; the by-source list is never longer): E and L below 2^31, the P table and the
+    partial rows below 2^31 bytes"""
+    e, l = g * n * k, lib.egnn_dest_lists_capacity(g, n, k)
+    assert l >= (g * n * ((k + 15) // 16) * 16 + 127) // 128 * 128          # (autograd.entry_list by source)
+    return e < 2 ** 31 and l < 2 ** 31, g * n * (2 * hp) * 4 < 2 ** 31, (l >> 4) * hp * 4 < 2 ** 31
+
+
+def test_fused_backward_chunk_size_meets_the_kernel_limits_tightly():
+    """autograd._fused_graphs_per_chunk: for (N, K, Hp) on either side of each of its three bounds every returned step satisfies what
+    the kernel checks, step + 1 violates some of it, and 0 means that one graph alone does not fit."""
+    from egnn_pytorch_amd import _abi, autograd as A
+    lib = _abi.load()
+    shapes = set()
+    for hp in (64, 288, 544, 2080):
+        table_n = (2 ** 31 - 1) // (2 * hp * 4)                              # the P table's bound for one graph
+        for k in (1, 8, 16, 17, 32, 64, 100):
+            rows_n = (2 ** 31) // ((k // 16 + 1) * hp * 4)                   # about the partial rows' bound for one graph
+            for n in (64, 1000, 1024, 4096, 40000, table_n - 1, table_n, table_n + 1, table_n // 2, table_n // 2 + 1,
+                      rows_n - 16, rows_n - 1, rows_n, rows_n + 1, rows_n // 2, rows_n // 3 + 1):
+                if n >= max(k, 1):
+                    shapes.add((n, k, hp))
+    for k in (16, 32, 2048):                                                # E = g N K around 2^31 (narrow layers)
+        for n in (2 ** 31 // k // 7, 2 ** 31 // k // 7 + 1, 2 ** 20):
+            shapes.add((n, k, 32))
+    binding = set()
+    for n, k, hp in sorted(shapes):
+        for b in (1, 3, 10 ** 6):
+            step = A._fused_graphs_per_chunk(b, n, k, hp)
+            one = all(_bwd_pass_accepts(lib, 1, n, k, hp))
+            assert (step == 0) == (not one), (b, n, k, hp, step)
+            if step == 0:
+                continue
+            assert 1 <= step <= b
+            assert all(_bwd_pass_accepts(lib, step, n, k, hp)), (b, n, k, hp, step)
+            if step < b:
+                ok = _bwd_pass_accepts(lib, step + 1, n, k, hp)
+                assert not all(ok), (b, n, k, hp, step)
+                binding.update(i for i, v in enumerate(ok) if not v)
+    # (the partial rows take L Hp / 4 bytes with Hp >= 32: E, L < 2^31 alone never decides)
+    assert binding == {1, 2}                                                # the P table and the partial rows each decided somewhere
+    assert A._fused_entry_capacity(3, 1000, 17) == lib.egnn_dest_lists_capacity(3, 1000, 17)
+    assert A._fused_graphs_per_chunk(160, 1024, 32, 2080) < 126             # K = 32: the partial rows bind before the P table
+    # one graph at dim 512 (Hp = 2080): beyond the P table's 2^31 bytes no chunk exists -- the limit the Python layer names
+    assert A._fused_graphs_per_chunk(1, 129056, 8, 2080) == 0 and A._fused_graphs_per_chunk(1, 129055, 8, 2080) == 1
+    with pytest.raises(A.FusedBackwardLimit, match=r"2\^31"):
+        raise A.FusedBackwardLimit(A._fused_limit_message(1, 139264, 32, 2080))
+    # the number the message names IS the largest graph admitted, for K that are no multiple of 16 as well (the partial rows take
+    # N K / 16 + N tiles: the bound moves with every K)
+    for k, hp in ((24, 288), (17, 288), (31, 2080), (47, 288), (8, 544), (32, 2080), (100, 64)):
+        most = A._fused_largest_graph(k, hp)
+        assert A._fused_graphs_per_chunk(1, most, k, hp) == 1 and A._fused_graphs_per_chunk(1, most + 1, k, hp) == 0, (k, hp, most)
+        assert all(_bwd_pass_accepts(lib, 1, most, k, hp)) and not all(_bwd_pass_accepts(lib, 1, most + 1, k, hp))
+        msg = A._fused_limit_message(1, most + 1, k, hp)
+        assert f"at most {most} nodes per graph" in msg and f"{most + 1} nodes" in msg, msg
+    assert A._fused_largest_graph(24, 288) == 745648 and A._fused_largest_graph(32, 2080) == 86032
+
+
+def test_edge_kernels_cover_predicates_at_their_limits():
+    """egnn_edge_pw_covers and egnn_edge_fused_covers (host functions) at N ldp 4 = 2^32 - 4 / 2^32 and B N K 16 = 2^32 - 16 / 2^32, and
+    egnn_edge_fused_f32 itself: beyond what its kernels address it returns EGNN_E_UNSUPPORTED -- before it touches the device."""
+    from egnn_pytorch_amd import _abi
+    lib = _abi.load()
+    pw = lambda b, n, k, ldp: lib.egnn_edge_pw_covers(b, n, k, 1, 0, 0, 16, 3, ldp)      # noqa: E731
+    fused = lib.egnn_edge_fused_covers
+    # one graph's table rows, N ldp 4 bytes: 2^32 - 4 / 2^32 (one node, so that the records stay small)
+    assert pw(1, 1, 32, 2 ** 30 - 1) == 1 and pw(1, 1, 32, 2 ** 30) == 0
+    assert fused(1, 32, 2 ** 30 - 1) == 1 and fused(1, 32, 2 ** 30) == 0
+    assert fused(2 ** 30 - 1, 32, 1) == 1 and fused(2 ** 30, 32, 1) == 0
+    ldp_hi = 2 ** 32 // (4096 * 4)                                          # ... and with 4096 nodes: 2^32 - 16 384 / 2^32
+    assert pw(1, 4096, 32, ldp_hi - 1) == 1 and pw(1, 4096, 32, ldp_hi) == 0
+    assert fused(4096, 32, ldp_hi - 1) == 1 and fused(4096, 32, ldp_hi) == 0
+    # the slot records, B N K 16 bytes: the kernel's K is a multiple of 32, so 2^32 - 16 is no shape -- the nearest one below, 2^32 - 512,
+    # and 2^32
+    assert pw(1, 2 ** 23 - 1, 32, 4) == 1 and pw(1, 2 ** 23, 32, 4) == 0
+    assert pw(2 ** 13 - 1, 1024, 32, 128) == 1 and pw(2 ** 13, 1024, 32, 128) == 0 and (2 ** 13) * 1024 * 32 * 16 == 2 ** 32
+    # tiles that carry several nodes' P_i rows (6 <= K, K % 32 != 0) keep offset 0x80000000 free: "no such row, read zeros"
+    assert fused(2 ** 29, 16, 1) == 1 and fused(2 ** 29 + 1, 16, 1) == 0
+    assert fused(2 ** 29 + 1, 3, 1) == 1 and fused(2 ** 29 + 1, 64, 1) == 1
+    # dim 512: ldp = 4160 floats, 258 111 nodes
+    ldp = 2 * lib.egnn_padded_hidden(2050)
+    assert lib.egnn_edge_fused_covers(258111, 32, ldp) == 1 and lib.egnn_edge_fused_covers(258112, 32, ldp) == 0
+    # egnn_edge_fused_f32: every argument check passes, then the size guard answers.  The pointers are made up, so this call is made
+    # only where no device is present: there a guard that failed could launch nothing, on a device it would launch on garbage
+    if torch.cuda.is_available():
+        return
+    a = _abi.EdgeArgs()
+    fake = 1 << 20
+    a.B, a.N, a.K, a.dim, a.m_dim, a.H, a.Hp = 1, 258112, 32, 512, 16, 2050, 2080
+    a.S, a.pi_split, a.ldp, a.coor_dim, a.wst_terms = 1, 1, ldp, 3, 4
+    a.Pi = a.Pj = a.Wst = a.W2h = a.b2 = a.coors = a.idx = a.m_i = fake
+    a.ws_inv_scale = a.w2_inv_scale = 1.0
+    a.algo = 1
+    assert lib.egnn_edge_fused_f32(ctypes.byref(a), None) == -3            # EGNN_E_UNSUPPORTED
+    a.algo = 0
+    assert lib.egnn_edge_fused_f32(ctypes.byref(a), None) == -3
+    a.coor_dim = 2                                                         # (the generic-dimension compilation holds the same guard)
+    assert lib.egnn_edge_fused_f32(ctypes.byref(a), None) == -3
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="calls the entry with made-up pointers: only where no device could be launched on")
+def test_c_layer_forward_refuses_a_graph_beyond_the_edge_kernels_offsets():
+    """egnn_layer_forward_f32 holds egnn_edge_fused_covers' limit itself, in front of its workspace check and of every launch: one node
+    beyond 4 GB of table rows per graph (dim 512: 258 112 nodes) it returns EGNN_E_UNSUPPORTED whatever the workspace; at the limit the
+    next check answers (EGNN_E_SHAPE for a workspace of 0 bytes).  The pointers are never read: both calls return before the device
+    is touched -- and the test runs only where there is none."""
+    from ctypes import byref
+    from egnn_pytorch_amd import EGNN, _abi, _ops
+    desc, info, _ = _ops.pack_weights_c(EGNN(dim=512, num_nearest_neighbors=32))
+    lib = _abi.load()
+    fake = 1 << 20
+
+    def call(n, ws_bytes):
+        return lib.egnn_layer_forward_f32(byref(desc), byref(info), fake, fake, fake, None, None, None, 0, 1, n, 32, 3, fake, fake, fake,
+                                          ws_bytes, None, None)
+    assert call(258112, 1 << 50) == -3 and call(258112, 0) == -3          # EGNN_E_UNSUPPORTED
+    assert call(258111, 0) == -2                                          # EGNN_E_SHAPE: the workspace check, behind the guard
