@@ -12,40 +12,13 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
 import torch  # noqa: F401  (must precede CDLL, see module docstring)
 
 ABI_VERSION = 44
 _LIB_NAME = "libegnn_hip.so"
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
-
-# every symbol include/egnn_hip.h declares
-SYMBOLS = (
-    "egnn_abi_version", "egnn_error_string", "egnn_padded_hidden", "egnn_knn_select_f32",
-    "egnn_adj_max_degree_u8",
-    "egnn_edge_fused_f32", "egnn_spatial_order_f32", "egnn_linear_hl_f32", "egnn_split_f16", "egnn_node_prep_hl",
-    "egnn_packed_halves", "egnn_adj_expand_u8", "egnn_adj_expand_wide_u8", "egnn_adj_expand_workspace_bytes", "egnn_edge_mfmas",
-    "egnn_packed_weights_bytes", "egnn_packed_layout", "egnn_pack_weights_host", "egnn_workspace_bytes", "egnn_layer_forward_f32", "egnn_layer_forward_opts_f32",
-    "egnn_edge_bwd_pass_f32", "egnn_edge_bwd_chunk_steps", "egnn_edge_bwd_work_bytes", "egnn_edge_tail_bwd_f32", "egnn_edge_tail_part_floats", "egnn_edge_pool_f32", "egnn_rows_gather_sum_f32", "egnn_edge_features_gather_f32", "egnn_edge_features_grad_f32",
-    "egnn_edge_features_gather_f64", "egnn_edge_features_grad_f64",
-    "egnn_induced_attn_f32", "egnn_token_attn_f32", "egnn_slot_prep_f32", "egnn_spatial_order_masked_f32", "egnn_struct_bytes",
-    "egnn_dest_lists_capacity", "egnn_dest_lists_i32", "egnn_split_scaled_f16", "egnn_linear_hl_splitk_f32", "egnn_sum_parts_f32", "egnn_absmax_f32", "egnn_unsplit_words_f32", "egnn_split_scaled_both_f16", "egnn_split_scaled_colsum_rows", "egnn_drop_silu_f32", "egnn_drop_silu_f64", "egnn_silu_bwd_f32", "egnn_silu_bwd_drop_f32",
-    "egnn_linear_hl_drop_f32", "egnn_linear_hl_lda_f32", "egnn_linear_hl_lda_rows_f32", "egnn_edge_pw_covers", "egnn_edge_fused_covers",
-    "egnn_linear_f32", "egnn_node_prep_f32", "egnn_edge_exact_f32", "egnn_edge_exact_workspace_bytes",
-    "egnn_knn_select_f64", "egnn_knn_select_stream_f32", "egnn_knn_select_stream_f64", "egnn_knn_grid_workspace_bytes", "egnn_knn_select_grid_f32", "egnn_linear_f64", "egnn_node_prep_f64", "egnn_edge_exact_f64",
-    "egnn_edge_exact_bwd_f32", "egnn_edge_exact_bwd_f64", "egnn_edge_exact_node_sums_f32", "egnn_edge_exact_node_sums_f64",
-    "egnn_edge_tail_exact_bwd_f32", "egnn_edge_tail_exact_bwd_f64", "egnn_status_publish",
-    "egnn_node_mlp_fused_halves", "egnn_node_mlp_fused_pack_f16", "egnn_node_mlp_fused_f32",
-    "egnn_edge_hidden_fwd_f32", "egnn_edge_hidden_fwd_f64", "egnn_edge_hidden_bwd_f32", "egnn_edge_hidden_bwd_f64",
-    "egnn_edge_hidden_bwd2_f32", "egnn_edge_hidden_bwd2_f64",
-    "egnn_induced_attn_bwd_f32", "egnn_induced_attn_bwd_work_floats", "egnn_token_attn_bwd_chunks", "egnn_token_attn_bwd_f32", "egnn_gelu_bwd_f32",
-    "egnn_layer_norm_bwd_parts", "egnn_layer_norm_bwd_f32",
-    "egnn_knn_select_csr_f32", "egnn_knn_select_csr_f64", "egnn_knn_select_grid_csr_f32",
-    "egnn_adj_csr_workspace_bytes", "egnn_adj_csr_square_count", "egnn_adj_csr_square_fill", "egnn_csr_slot_labels_u8",
-    "egnn_edge_features_gather_slot_f32", "egnn_edge_features_gather_slot_f64", "egnn_edge_features_grad_slot_f32",
-    "egnn_edge_features_grad_slot_f64",
-)
 
 
 class EdgeArgs(Structure):
@@ -68,7 +41,7 @@ class EdgeArgs(Structure):
         ("U_out", c_void_p),
         ("edges_by_k", c_int32),
         ("slots", c_void_p),
-        ("drop_thr", ctypes.c_uint32), ("drop_seed", ctypes.c_uint32), ("drop_inv_keep", c_float),
+        ("drop_thr", c_uint32), ("drop_seed", c_uint32), ("drop_inv_keep", c_float),
         ("algo", c_int32),
     ]
 
@@ -183,7 +156,7 @@ class PackedInfo(Structure):
                 ("wcat_rows", c_int32), ("w5_rows", c_int32), ("w6_rows", c_int32),
                 ("wcat_inv_scale", c_float), ("ws_inv_scale", c_float), ("w2_inv_scale", c_float), ("w3_inv_scale", c_float),
                 ("w5_inv_scale", c_float), ("w6_inv_scale", c_float)] + \
-               [(f, ctypes.c_uint64) for f in INFO_OFFSETS] + [("bytes", ctypes.c_uint64)]
+               [(f, c_uint64) for f in INFO_OFFSETS] + [("bytes", c_uint64)]
 
 
 class ForwardOpts(Structure):
@@ -191,6 +164,142 @@ class ForwardOpts(Structure):
     _fields_ = [("side_stream", c_void_p), ("ev_fork", c_void_p), ("ev_join", c_void_p), ("order", c_void_p), ("nmf_img", c_void_p),
                 ("order_is_hint", c_int32), ("status_words", c_int32), ("status_pub", c_void_p), ("status_seq", c_int32),
                 ("reserved", c_int32)]
+
+
+# (header struct name, mirror), in the order of egnn_struct_bytes(which): load() compares the sizes.  (LayerParams mirrors
+# egnn_layer_params, which egnn_struct_bytes does not cover.)
+STRUCTS = (
+    ("egnn_edge_args", EdgeArgs), ("egnn_edge_bwd_args", EdgeBwdArgs), ("egnn_edge_tail_args", EdgeTailArgs),
+    ("egnn_layer_desc", LayerDesc), ("egnn_packed_info", PackedInfo), ("egnn_edge_exact_args", EdgeExactArgs),
+    ("egnn_edge_exact_bwd_args", EdgeExactBwdArgs), ("egnn_edge_tail_exact_args", EdgeTailExactArgs),
+    ("egnn_forward_opts", ForwardOpts), ("egnn_edge_hidden_args", EdgeHiddenArgs),
+)
+
+_LAYER_FORWARD = (POINTER(LayerDesc), POINTER(PackedInfo), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                  c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p)
+
+# Every prototype of include/egnn_hip.h, once: (names that share the signature, restype, argtypes).  This table is the whole
+# binding -- load() applies it in one loop -- and tests/test_abi_agreement.py checks it against the header type by type.
+SIGNATURES = {name: (restype, argtypes) for names, restype, argtypes in (
+    ("egnn_abi_version egnn_edge_tail_part_floats egnn_edge_bwd_chunk_steps", c_int, ()),
+    ("egnn_struct_bytes", c_int64, (c_int,)),
+    ("egnn_status_publish", c_int, (c_void_p, c_void_p, c_int, c_int32, c_void_p)),
+    ("egnn_error_string", c_char_p, (c_int,)),
+    ("egnn_padded_hidden egnn_edge_mfmas egnn_token_attn_bwd_chunks", c_int, (c_int,)),
+    # neighbour selection
+    ("egnn_knn_select_f32 egnn_knn_select_f64 egnn_knn_select_stream_f32 egnn_knn_select_stream_f64", c_int,
+     (c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p)),
+    ("egnn_knn_select_csr_f32 egnn_knn_select_csr_f64", c_int,
+     (c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p)),
+    ("egnn_knn_grid_workspace_bytes egnn_dest_lists_capacity", c_size_t, (c_int, c_int, c_int)),
+    ("egnn_knn_select_grid_f32", c_int,
+     (c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p)),
+    ("egnn_knn_select_grid_csr_f32", c_int,
+     (c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p)),
+    # adjacency: CSR expansion, degrees, dense expansion
+    ("egnn_adj_csr_workspace_bytes egnn_adj_expand_workspace_bytes", c_size_t, (c_int, c_int)),
+    ("egnn_adj_csr_square_count", c_int,
+     (c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p)),
+    ("egnn_adj_csr_square_fill", c_int,
+     (c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+      c_int64, c_void_p, c_size_t, c_int, c_void_p)),
+    ("egnn_csr_slot_labels_u8", c_int, (c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p)),
+    ("egnn_adj_max_degree_u8", c_int, (c_void_p, c_int64, c_int, c_void_p, c_void_p)),
+    ("egnn_adj_expand_u8 egnn_adj_expand_wide_u8", c_int,
+     (c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p)),
+    # scheduling aids and the backward's transposed neighbour list
+    ("egnn_spatial_order_f32", c_int, (c_void_p, c_int, c_int, c_void_p, c_void_p)),
+    ("egnn_spatial_order_masked_f32", c_int, (c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p)),
+    ("egnn_dest_lists_i32", c_int,
+     (c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p)),
+    ("egnn_slot_prep_f32", c_int, (c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p, c_void_p)),
+    # split-f16 GEMMs and their operand passes
+    ("egnn_packed_halves egnn_split_scaled_colsum_rows", c_int64, (c_int64, c_int)),
+    ("egnn_linear_hl_f32", c_int,
+     (c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int64,
+      c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p)),
+    ("egnn_linear_hl_lda_f32", c_int,
+     (c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int,
+      c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p)),
+    ("egnn_linear_hl_lda_rows_f32", c_int,
+     (c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int,
+      c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p)),
+    ("egnn_linear_hl_drop_f32", c_int,
+     (c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int64,
+      c_int, c_int, c_int, c_int, c_int, c_uint32, c_uint32, c_float, c_void_p, c_void_p)),
+    ("egnn_edge_pw_covers", c_int, (c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64)),
+    ("egnn_edge_fused_covers", c_int, (c_int, c_int, c_int64)),
+    ("egnn_split_scaled_f16", c_int,
+     (c_void_p, c_int64, c_int64, c_int, c_float, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p)),
+    ("egnn_split_scaled_both_f16", c_int,
+     (c_void_p, c_int64, c_int64, c_int, c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64,
+      c_void_p)),
+    ("egnn_silu_bwd_f32 egnn_gelu_bwd_f32", c_int, (c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p)),
+    ("egnn_silu_bwd_drop_f32", c_int,
+     (c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_uint32, c_uint32, c_float, c_int64, c_int, c_void_p)),
+    ("egnn_linear_hl_splitk_f32", c_int,
+     (c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p)),
+    ("egnn_sum_parts_f32", c_int, (c_void_p, c_int, c_int64, c_float, c_void_p, c_void_p)),
+    ("egnn_absmax_f32", c_int, (c_void_p, c_int64, c_void_p, c_void_p)),
+    ("egnn_unsplit_words_f32", c_int, (c_void_p, c_int64, c_int64, c_int, c_void_p)),
+    ("egnn_node_mlp_fused_halves", c_int64, (c_int, c_int)),
+    ("egnn_node_mlp_fused_pack_f16", c_int, (c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p)),
+    ("egnn_node_mlp_fused_f32", c_int,
+     (c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p)),
+    ("egnn_split_f16", c_int, (c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p)),
+    ("egnn_node_prep_hl", c_int,
+     (c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int64, c_int, c_int,
+      c_void_p, c_void_p)),
+    # the fused edge pass, its look-up tables and its backward
+    ("egnn_edge_fused_f32", c_int, (POINTER(EdgeArgs), c_void_p)),
+    ("egnn_edge_features_gather_f32 egnn_edge_features_gather_f64 egnn_edge_features_gather_slot_f32 egnn_edge_features_gather_slot_f64",
+     c_int, (c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p)),
+    ("egnn_edge_features_grad_f32 egnn_edge_features_grad_f64 egnn_edge_features_grad_slot_f32 egnn_edge_features_grad_slot_f64", c_int,
+     (c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+      c_void_p, POINTER(c_int64), c_void_p)),
+    ("egnn_edge_bwd_pass_f32", c_int, (POINTER(EdgeBwdArgs), c_void_p)),
+    ("egnn_edge_bwd_work_bytes", c_size_t, (c_int64, c_int, c_int, c_int)),
+    ("egnn_edge_tail_bwd_f32", c_int, (POINTER(EdgeTailArgs), c_void_p)),
+    ("egnn_edge_pool_f32", c_int, (c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p)),
+    ("egnn_rows_gather_sum_f32", c_int, (c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p)),
+    # whole layers
+    ("egnn_packed_weights_bytes", c_size_t, (POINTER(LayerDesc),)),
+    ("egnn_packed_layout", c_int, (POINTER(LayerDesc), POINTER(PackedInfo))),
+    ("egnn_pack_weights_host", c_int, (POINTER(LayerDesc), POINTER(LayerParams), c_void_p, POINTER(PackedInfo))),
+    ("egnn_workspace_bytes", c_size_t, (POINTER(LayerDesc), c_int, c_int, c_int)),
+    ("egnn_layer_forward_f32", c_int, _LAYER_FORWARD),
+    ("egnn_layer_forward_opts_f32", c_int, _LAYER_FORWARD + (POINTER(ForwardOpts),)),
+    # global attention blocks
+    ("egnn_induced_attn_f32", c_int,
+     (c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p)),
+    ("egnn_token_attn_f32", c_int,
+     (c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int64, c_void_p)),
+    ("egnn_induced_attn_bwd_f32", c_int,
+     (c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
+      c_void_p)),
+    ("egnn_induced_attn_bwd_work_floats", c_int64, (c_int, c_int, c_int, c_int, c_int)),
+    ("egnn_token_attn_bwd_f32", c_int,
+     (c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p)),
+    ("egnn_layer_norm_bwd_parts", c_int, (c_int64,)),
+    ("egnn_layer_norm_bwd_f32", c_int,
+     (c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p)),
+    # plain fp32 / float64 kernels
+    ("egnn_linear_f32 egnn_linear_f64", c_int,
+     (c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p)),
+    ("egnn_node_prep_f32", c_int, (c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int, c_int, c_void_p)),
+    ("egnn_node_prep_f64", c_int, (c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_int64, c_int, c_int, c_void_p)),
+    ("egnn_drop_silu_f32 egnn_drop_silu_f64", c_int,
+     (c_void_p, c_int64, c_int64, c_int, c_uint32, c_uint32, c_float, c_int64, c_void_p)),
+    ("egnn_edge_exact_workspace_bytes", c_size_t, (c_int, c_int, c_int, c_int, c_int)),
+    ("egnn_edge_exact_f32 egnn_edge_exact_f64", c_int, (POINTER(EdgeExactArgs), c_void_p)),
+    ("egnn_edge_exact_bwd_f32 egnn_edge_exact_bwd_f64", c_int, (POINTER(EdgeExactBwdArgs), c_void_p)),
+    ("egnn_edge_exact_node_sums_f32 egnn_edge_exact_node_sums_f64", c_int,
+     (c_void_p, c_int64, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p)),
+    ("egnn_edge_tail_exact_bwd_f32 egnn_edge_tail_exact_bwd_f64", c_int, (POINTER(EdgeTailExactArgs), c_void_p)),
+    ("egnn_edge_hidden_fwd_f32 egnn_edge_hidden_fwd_f64 egnn_edge_hidden_bwd_f32 egnn_edge_hidden_bwd_f64 "
+     "egnn_edge_hidden_bwd2_f32 egnn_edge_hidden_bwd2_f64", c_int, (POINTER(EdgeHiddenArgs), c_void_p)),
+) for name in names.split()}
+SYMBOLS = tuple(SIGNATURES)
 
 
 def layer_desc(layer) -> "LayerDesc":
@@ -257,216 +366,12 @@ def load():
     missing = [s for s in SYMBOLS if not hasattr(lib, s)]
     if missing:
         raise EGNNHipError(f"{path} does not export {missing}; rebuild it")
-
-    lib.egnn_abi_version.restype = c_int
-    lib.egnn_abi_version.argtypes = []
-    lib.egnn_error_string.restype = c_char_p
-    lib.egnn_error_string.argtypes = [c_int]
-    lib.egnn_padded_hidden.restype = c_int
-    lib.egnn_padded_hidden.argtypes = [c_int]
-    lib.egnn_knn_select_f32.restype = c_int
-    lib.egnn_knn_select_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
-                                        c_void_p, c_void_p, c_void_p]
-    lib.egnn_adj_max_degree_u8.restype = c_int
-    lib.egnn_adj_max_degree_u8.argtypes = [c_void_p, c_int64, c_int, c_void_p, c_void_p]
-    lib.egnn_adj_expand_workspace_bytes.restype = c_size_t
-    lib.egnn_adj_expand_workspace_bytes.argtypes = [c_int, c_int]
-    for name in ("egnn_adj_expand_u8", "egnn_adj_expand_wide_u8"):
-        getattr(lib, name).restype = c_int
-        getattr(lib, name).argtypes = [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.egnn_packed_halves.restype = c_int64
-    lib.egnn_packed_halves.argtypes = [c_int64, c_int]
-    lib.egnn_linear_hl_f32.restype = c_int
-    lib.egnn_linear_hl_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p,
-                                       c_int64, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
-    lib.egnn_linear_hl_lda_f32.restype = c_int
-    lib.egnn_linear_hl_lda_f32.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p,
-                                           c_int64, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
-    lib.egnn_edge_pw_covers.restype = c_int
-    lib.egnn_edge_pw_covers.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64]
-    lib.egnn_edge_fused_covers.restype = c_int
-    lib.egnn_edge_fused_covers.argtypes = [c_int, c_int, c_int64]
-    lib.egnn_linear_hl_lda_rows_f32.restype = c_int
-    lib.egnn_linear_hl_lda_rows_f32.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p,
-                                                c_int64, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                                                c_void_p]
-    lib.egnn_linear_hl_drop_f32.restype = c_int
-    lib.egnn_linear_hl_drop_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p,
-                                            c_int64, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_int,
-                                            ctypes.c_uint32, ctypes.c_uint32, c_float, c_void_p, c_void_p]
-    lib.egnn_node_mlp_fused_halves.restype = c_int64
-    lib.egnn_node_mlp_fused_halves.argtypes = [c_int, c_int]
-    lib.egnn_node_mlp_fused_pack_f16.restype = c_int
-    lib.egnn_node_mlp_fused_pack_f16.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]
-    lib.egnn_node_mlp_fused_f32.restype = c_int
-    lib.egnn_node_mlp_fused_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int64,
-                                            c_int, c_int, c_void_p, c_void_p]
-    lib.egnn_split_f16.restype = c_int
-    lib.egnn_split_f16.argtypes = [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
-    lib.egnn_node_prep_hl.restype = c_int
-    lib.egnn_node_prep_hl.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int,
-                                      c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p]
-    lib.egnn_spatial_order_f32.restype = c_int
-    lib.egnn_spatial_order_f32.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p]
-    lib.egnn_spatial_order_masked_f32.restype = c_int
-    lib.egnn_spatial_order_masked_f32.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]
-    lib.egnn_slot_prep_f32.restype = c_int
-    lib.egnn_slot_prep_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p, c_void_p]
-    lib.egnn_dest_lists_capacity.restype = c_size_t
-    lib.egnn_dest_lists_capacity.argtypes = [c_int, c_int, c_int]
-    lib.egnn_dest_lists_i32.restype = c_int
-    lib.egnn_dest_lists_i32.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.egnn_split_scaled_f16.restype = c_int
-    lib.egnn_split_scaled_f16.argtypes = [c_void_p, c_int64, c_int64, c_int, c_float, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
-    lib.egnn_linear_hl_splitk_f32.restype = c_int
-    lib.egnn_linear_hl_splitk_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int64, c_int, c_int, c_int,
-                                              c_int, c_void_p]
-    lib.egnn_sum_parts_f32.restype = c_int
-    lib.egnn_sum_parts_f32.argtypes = [c_void_p, c_int, c_int64, c_float, c_void_p, c_void_p]
-    lib.egnn_absmax_f32.restype = c_int
-    lib.egnn_absmax_f32.argtypes = [c_void_p, c_int64, c_void_p, c_void_p]
-    lib.egnn_split_scaled_both_f16.restype = c_int
-    lib.egnn_split_scaled_both_f16.argtypes = [c_void_p, c_int64, c_int64, c_int, c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
-                                               c_void_p, c_void_p, c_int64, c_void_p]
-    for fn in (lib.egnn_drop_silu_f32, lib.egnn_drop_silu_f64):
-        fn.restype = c_int
-        fn.argtypes = [c_void_p, c_int64, c_int64, c_int, c_uint32, c_uint32, c_float, c_int64, c_void_p]
-    lib.egnn_split_scaled_colsum_rows.restype = c_int64
-    lib.egnn_split_scaled_colsum_rows.argtypes = [c_int64, c_int]
-    lib.egnn_silu_bwd_f32.restype = c_int
-    lib.egnn_silu_bwd_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
-    lib.egnn_silu_bwd_drop_f32.restype = c_int
-    lib.egnn_silu_bwd_drop_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_uint32, c_uint32, c_float, c_int64, c_int, c_void_p]
-    lib.egnn_unsplit_words_f32.restype = c_int
-    lib.egnn_unsplit_words_f32.argtypes = [c_void_p, c_int64, c_int64, c_int, c_void_p]
-    lib.egnn_edge_mfmas.restype = c_int
-    lib.egnn_edge_mfmas.argtypes = [c_int]
-    lib.egnn_edge_fused_f32.restype = c_int
-    lib.egnn_edge_fused_f32.argtypes = [POINTER(EdgeArgs), c_void_p]
-    lib.egnn_edge_bwd_pass_f32.restype = c_int
-    lib.egnn_edge_bwd_pass_f32.argtypes = [POINTER(EdgeBwdArgs), c_void_p]
-    lib.egnn_edge_tail_bwd_f32.restype = c_int
-    lib.egnn_edge_tail_bwd_f32.argtypes = [POINTER(EdgeTailArgs), c_void_p]
-    lib.egnn_edge_tail_part_floats.restype = c_int
-    lib.egnn_edge_tail_part_floats.argtypes = []
-    lib.egnn_edge_pool_f32.restype = c_int
-    lib.egnn_edge_pool_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
-    lib.egnn_edge_bwd_chunk_steps.restype = c_int
-    lib.egnn_edge_bwd_chunk_steps.argtypes = []
-    lib.egnn_edge_bwd_work_bytes.restype = c_size_t
-    lib.egnn_edge_bwd_work_bytes.argtypes = [c_int64, c_int, c_int, c_int]
-    lib.egnn_induced_attn_f32.restype = c_int
-    lib.egnn_induced_attn_f32.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
-                                          c_void_p]
-    lib.egnn_token_attn_f32.restype = c_int
-    lib.egnn_token_attn_f32.argtypes = [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int64,
-                                        c_void_p]
-    lib.egnn_induced_attn_bwd_f32.restype = c_int
-    lib.egnn_induced_attn_bwd_f32.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                              c_float, c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.egnn_induced_attn_bwd_work_floats.restype = c_int64
-    lib.egnn_induced_attn_bwd_work_floats.argtypes = [c_int, c_int, c_int, c_int, c_int]
-    lib.egnn_token_attn_bwd_chunks.restype = c_int
-    lib.egnn_token_attn_bwd_chunks.argtypes = [c_int]
-    lib.egnn_token_attn_bwd_f32.restype = c_int
-    lib.egnn_token_attn_bwd_f32.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_float,
-                                            c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.egnn_gelu_bwd_f32.restype = c_int
-    lib.egnn_gelu_bwd_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
-    lib.egnn_layer_norm_bwd_parts.restype = c_int
-    lib.egnn_layer_norm_bwd_parts.argtypes = [c_int64]
-    lib.egnn_layer_norm_bwd_f32.restype = c_int
-    lib.egnn_layer_norm_bwd_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
-                                            c_void_p]
-    for gather, grad in ((lib.egnn_edge_features_gather_f32, lib.egnn_edge_features_grad_f32),
-                         (lib.egnn_edge_features_gather_f64, lib.egnn_edge_features_grad_f64),      # (pointers only: one signature)
-                         (lib.egnn_edge_features_gather_slot_f32, lib.egnn_edge_features_grad_slot_f32),
-                         (lib.egnn_edge_features_gather_slot_f64, lib.egnn_edge_features_grad_slot_f64)):
-        gather.restype = c_int
-        gather.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
-        grad.restype = c_int
-        grad.argtypes = [c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
-                         c_int, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_void_p]
-    lib.egnn_rows_gather_sum_f32.restype = c_int
-    lib.egnn_rows_gather_sum_f32.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p]
-
-    lib.egnn_packed_weights_bytes.restype = c_size_t
-    lib.egnn_packed_weights_bytes.argtypes = [POINTER(LayerDesc)]
-    lib.egnn_packed_layout.restype = c_int
-    lib.egnn_packed_layout.argtypes = [POINTER(LayerDesc), POINTER(PackedInfo)]
-    lib.egnn_pack_weights_host.restype = c_int
-    lib.egnn_pack_weights_host.argtypes = [POINTER(LayerDesc), POINTER(LayerParams), c_void_p, POINTER(PackedInfo)]
-    lib.egnn_workspace_bytes.restype = c_size_t
-    lib.egnn_workspace_bytes.argtypes = [POINTER(LayerDesc), c_int, c_int, c_int]
-    lib.egnn_layer_forward_f32.restype = c_int
-    lib.egnn_layer_forward_f32.argtypes = [POINTER(LayerDesc), POINTER(PackedInfo), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                           c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
-                                           c_void_p, c_void_p]
-    lib.egnn_layer_forward_opts_f32.restype = c_int
-    lib.egnn_layer_forward_opts_f32.argtypes = lib.egnn_layer_forward_f32.argtypes + [POINTER(ForwardOpts)]
-
-    lib.egnn_linear_f32.restype = c_int
-    lib.egnn_linear_f32.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
-                                    c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p]
-    lib.egnn_node_prep_f32.restype = c_int
-    lib.egnn_node_prep_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int, c_int, c_void_p]
-    lib.egnn_edge_exact_f32.restype = c_int
-    lib.egnn_edge_exact_f32.argtypes = [POINTER(EdgeExactArgs), c_void_p]
-    lib.egnn_edge_exact_f64.restype = c_int
-    lib.egnn_edge_exact_f64.argtypes = [POINTER(EdgeExactArgs), c_void_p]
-    lib.egnn_knn_select_f64.restype = c_int
-    lib.egnn_knn_select_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
-    for name in ("egnn_knn_select_stream_f32", "egnn_knn_select_stream_f64"):
-        getattr(lib, name).restype = c_int
-        getattr(lib, name).argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
-    for name in ("egnn_knn_select_csr_f32", "egnn_knn_select_csr_f64"):
-        getattr(lib, name).restype = c_int
-        getattr(lib, name).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
-    lib.egnn_adj_csr_workspace_bytes.restype = c_size_t
-    lib.egnn_adj_csr_workspace_bytes.argtypes = [c_int, c_int]
-    lib.egnn_adj_csr_square_count.restype = c_int
-    lib.egnn_adj_csr_square_count.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                              c_size_t, c_int, c_void_p]
-    lib.egnn_adj_csr_square_fill.restype = c_int
-    lib.egnn_adj_csr_square_fill.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
-                                             c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_void_p]
-    lib.egnn_csr_slot_labels_u8.restype = c_int
-    lib.egnn_csr_slot_labels_u8.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
-    lib.egnn_knn_grid_workspace_bytes.restype = c_size_t
-    lib.egnn_knn_grid_workspace_bytes.argtypes = [c_int, c_int, c_int]
-    lib.egnn_knn_select_grid_f32.restype = c_int
-    lib.egnn_knn_select_grid_f32.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-    lib.egnn_knn_select_grid_csr_f32.restype = c_int
-    lib.egnn_knn_select_grid_csr_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                                                 c_void_p, c_size_t, c_void_p]
-    lib.egnn_linear_f64.restype = c_int
-    lib.egnn_linear_f64.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int,
-                                    c_int, c_void_p]
-    lib.egnn_node_prep_f64.restype = c_int
-    lib.egnn_node_prep_f64.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_int64, c_int, c_int, c_void_p]
-    for fn in (lib.egnn_edge_exact_bwd_f32, lib.egnn_edge_exact_bwd_f64):
-        fn.restype = c_int
-        fn.argtypes = [POINTER(EdgeExactBwdArgs), c_void_p]
-    for fn in (lib.egnn_edge_tail_exact_bwd_f32, lib.egnn_edge_tail_exact_bwd_f64):
-        fn.restype = c_int
-        fn.argtypes = [POINTER(EdgeTailExactArgs), c_void_p]
-    for name in ("egnn_edge_hidden_fwd_f32", "egnn_edge_hidden_fwd_f64", "egnn_edge_hidden_bwd_f32", "egnn_edge_hidden_bwd_f64",
-                 "egnn_edge_hidden_bwd2_f32", "egnn_edge_hidden_bwd2_f64"):
-        getattr(lib, name).restype = c_int
-        getattr(lib, name).argtypes = [POINTER(EdgeHiddenArgs), c_void_p]
-    for fn in (lib.egnn_edge_exact_node_sums_f32, lib.egnn_edge_exact_node_sums_f64):
-        fn.restype = c_int
-        fn.argtypes = [c_void_p, c_int64, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.egnn_status_publish.restype = c_int
-    lib.egnn_status_publish.argtypes = [c_void_p, c_void_p, c_int, c_int32, c_void_p]
-    lib.egnn_edge_exact_workspace_bytes.restype = c_size_t
-    lib.egnn_edge_exact_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if lib.egnn_abi_version() != ABI_VERSION:
         raise EGNNHipError(f"{path}: ABI version {lib.egnn_abi_version()} != {ABI_VERSION}; rebuild it")
-    lib.egnn_struct_bytes.restype = c_int64
-    lib.egnn_struct_bytes.argtypes = [c_int]
-    for which, mirror in enumerate((EdgeArgs, EdgeBwdArgs, EdgeTailArgs, LayerDesc, PackedInfo, EdgeExactArgs, EdgeExactBwdArgs, EdgeTailExactArgs,
-                                    ForwardOpts, EdgeHiddenArgs)):
+    for which, (_, mirror) in enumerate(STRUCTS):
         if lib.egnn_struct_bytes(which) != ctypes.sizeof(mirror):
             raise EGNNHipError(f"{path}: sizeof({mirror.__name__}) = {ctypes.sizeof(mirror)} here, {lib.egnn_struct_bytes(which)} in the "
                                f"library: the ctypes mirror in _abi.py and include/egnn_hip.h disagree")

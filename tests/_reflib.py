@@ -14,15 +14,20 @@ from egnn_pytorch_amd._ops import _ptr, _stream, _timed, empty
 _PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libegnn_hip_ref.so")
 _lib = None
 
+# every prototype of include/egnn_hip_ref.h: name -> (restype, argtypes), the form of _abi.SIGNATURES (tests/test_abi_agreement.py)
+SIGNATURES = {
+    "egnn_linear_split_f32": (c_int, (c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_int64, c_void_p,
+                                      c_int64, c_int64, c_int, c_int, c_int, c_void_p)),
+}
+
 
 def load():
     global _lib
     if _lib is None:
         _abi.load()                                        # the HIP runtime torch initialised, then ours
         lib = ctypes.CDLL(_PATH)
-        lib.egnn_linear_split_f32.restype = c_int
-        lib.egnn_linear_split_f32.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p,
-                                              c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p]
+        for name, (restype, argtypes) in SIGNATURES.items():
+            getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
         _lib = lib
     return _lib
 

@@ -1,10 +1,8 @@
-"""CPU-side checks of the shipped host code: the C-ABI library loads and exports every symbol the header
-declares, the drop-in modules keep the reference's constructor / state_dict contract, the weight re-layout
+"""CPU-side checks of the shipped host code: the C-ABI library loads and exports every symbol the binding
+names (the binding against the header: tests/test_abi_agreement.py), the drop-in modules keep the reference's constructor / state_dict contract, the weight re-layout
 is algebraically exact, and the product path refuses to run without a GPU (no fallback)."""
 import ctypes
 import os
-import re
-import sys
 
 import numpy as np
 import pytest
@@ -17,12 +15,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_abi_library_loads_and_exports_header_symbols():
+    """(The header against the binding, symbol by symbol and type by type: tests/test_abi_agreement.py.)"""
     from egnn_pytorch_amd import _abi
     lib = _abi.load()                                   # no compute call: loading needs no GPU
-    header = open(os.path.join(ROOT, "include", "egnn_hip.h")).read()
-    declared = set(re.findall(r"\b(egnn_[a-z0-9_]+)\s*\(", header))
-    assert declared == set(_abi.SYMBOLS), declared ^ set(_abi.SYMBOLS)
-    for sym in declared:
+    for sym in _abi.SYMBOLS:
         assert hasattr(lib, sym), sym
     assert lib.egnn_abi_version() == _abi.ABI_VERSION
     assert lib.egnn_padded_hidden(2050) == 2080 and lib.egnn_padded_hidden(64) == 64
@@ -30,22 +26,6 @@ def test_abi_library_loads_and_exports_header_symbols():
     for s_ in range(1, 17):                             # host mirror of the kernel's instantiation table
         assert lib.egnn_edge_mfmas(s_) == _weights.edge_mfmas(s_) and 4 * _weights.edge_mfmas(s_) >= 3 * s_
     assert b"out of range" in lib.egnn_error_string(-5)
-
-
-def test_edge_args_struct_matches_header():
-    """Field order / count of the ctypes mirror against `struct egnn_edge_args` in the header."""
-    from egnn_pytorch_amd import _abi
-    header = open(os.path.join(ROOT, "include", "egnn_hip.h")).read()
-    body = header[header.index("typedef struct egnn_edge_args {"):header.index("} egnn_edge_args;")]
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split("{", 1)[1].split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        for part in decl.split(","):
-            names.append(re.findall(r"[A-Za-z_][A-Za-z0-9_]*", part)[-1])
-    assert names == [f[0] for f in _abi.EdgeArgs._fields_]
 
 
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):

@@ -1,17 +1,11 @@
 """Second-order autograd (create_graph=True) without a GPU: the closed forms of the E x H block (autograd.py::EdgeHidden /
 EdgeHiddenGrad, the specification of csrc/edge_hidden.hip) against torch's own double backward of the literal expression, the whole
-layer through autograd.EGNNFunction on the CPU stand-in against the reference's float64 second-order results, and the argument
-struct of the new C entries against the header."""
-import os
-import re
-
-import numpy as np
+layer through autograd.EGNNFunction on the CPU stand-in against the reference's float64 second-order results.  (The argument
+struct of the C entries against the header: tests/test_abi_agreement.py.)"""
 import pytest
 import torch
 
 from tests._reference import check_state, pack_grads, reference_result, state_digest, unpack_grads
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _block_inputs(b, n, k, h, m, s_dim, dense, seed=0):
@@ -267,23 +261,3 @@ def test_create_graph_with_no_neighbours(cpu_layer_stub):
         assert (g is None) == (w is None)
         if g is not None:
             assert torch.allclose(g, w, rtol=1e-12, atol=1e-14)
-
-
-def test_edge_hidden_args_struct_matches_header():
-    """Field order / count of the ctypes mirror against `struct egnn_edge_hidden_args` in the header."""
-    from egnn_pytorch_amd import _abi
-    header = open(os.path.join(ROOT, "include", "egnn_hip.h")).read()
-    body = header[header.index("typedef struct egnn_edge_hidden_args {"):header.index("} egnn_edge_hidden_args;")]
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split("{", 1)[1].split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        for part in decl.split(","):
-            names.append(re.findall(r"[A-Za-z_][A-Za-z0-9_]*", part)[-1])
-    assert names == [f[0] for f in _abi.EdgeHiddenArgs._fields_]
-    lib = _abi.load()
-    import ctypes
-    assert lib.egnn_struct_bytes(9) == ctypes.sizeof(_abi.EdgeHiddenArgs)
-    assert np.all([hasattr(lib, f"egnn_edge_hidden_{w}_{d}") for w in ("fwd", "bwd", "bwd2") for d in ("f32", "f64")])

@@ -1,21 +1,13 @@
 """`SparseAdjacency` on the host (egnn_pytorch_amd/sparse_adj.py): constructors and `to_dense()` round trips, `graphs`, `max_degree`
-against the oracle, validation errors, sharding; the agreement of header, binding and library on the new entries (CSR selection,
-csrc/knn_stream.hip; CSR expansion and slot labels, csrc/adj_csr.hip; gather / gradient by slot, csrc/segment_sum.hip), whose
-argument checks return before anything is launched; and the expansion's rule restated on CSR rows in plain Python against the oracle,
-which pins the XOR relabelling independently of the kernel."""
-import os
-import re
-
+against the oracle, validation errors, sharding; the argument checks of its entries (CSR selection, csrc/knn_stream.hip; CSR
+expansion and slot labels, csrc/adj_csr.hip; gather / gradient by slot, csrc/segment_sum.hip), which return before anything is
+launched (header, binding and library on those entries: tests/test_abi_agreement.py); and the expansion's rule restated on CSR rows
+in plain Python against the oracle, which pins the XOR relabelling independently of the kernel."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import egnn_oracle as O
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("egnn_knn_select_csr_f32", "egnn_knn_select_csr_f64", "egnn_adj_csr_workspace_bytes", "egnn_adj_csr_square_count",
-       "egnn_adj_csr_square_fill", "egnn_csr_slot_labels_u8", "egnn_edge_features_gather_slot_f32", "egnn_edge_features_gather_slot_f64",
-       "egnn_edge_features_grad_slot_f32", "egnn_edge_features_grad_slot_f64")
 
 
 def _SA():
@@ -192,19 +184,7 @@ def test_graphed_refuses_the_csr_expansion_before_any_forward():
         graphed(net, torch.randn(1, 9, 8), torch.randn(1, 9, 3), adj_mat=sa)
 
 
-def test_csr_entries_in_header_binding_and_library():
-    from egnn_pytorch_amd import _abi
-    header = open(os.path.join(ROOT, "include", "egnn_hip.h")).read()
-    lib = _abi.load()
-    for sym in NEW:
-        assert re.search(r"\b" + sym + r"\s*\(", header), sym
-        assert sym in _abi.SYMBOLS, sym
-        assert hasattr(lib, sym), sym
-    assert "#define EGNN_ABI_VERSION 44" in header
-    assert _abi.ABI_VERSION == 44 and lib.egnn_abi_version() == 44
-
-
-@pytest.mark.parametrize("sym", NEW[:2])
+@pytest.mark.parametrize("sym", ["egnn_knn_select_csr_f32", "egnn_knn_select_csr_f64"])
 def test_csr_argument_checks_need_no_device(sym):
     """Every argument check returns before anything is launched: they run without a GPU."""
     from egnn_pytorch_amd import _abi
