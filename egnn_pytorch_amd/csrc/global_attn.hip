@@ -35,11 +35,15 @@ __global__ __launch_bounds__(256) void induced_attn_kernel(const float* __restri
             const int d = lane + 64 * u;
             qr[t][u] = (t < T && d < dh) ? q[((size_t)b * T + t) * inner + h * dh + d] * scale : 0.f;
         }
-    float m[TMAX], l[TMAX], o[TMAX][DPL];
+    // A wave adds up N / 4 terms one after the other: plain fp32 running sums drift by ~sqrt(N / 4) roundings (2.3e-6 of the output at
+    // N = 4099, beyond the 2e-6 the backward cores keep -- tests/test_gpu_attention_forward.py), so l and o carry a Kahan compensation
+    // (lc, oc: what the last additions rounded away; the sums are l - lc, o - oc).  The rescaling by corr is exact while the
+    // maximum stands (corr = 1).
+    float m[TMAX], l[TMAX], lc[TMAX], o[TMAX][DPL], oc[TMAX][DPL];
     for (int t = 0; t < TMAX; ++t) {
-        m[t] = -FLT_MAX; l[t] = 0.f;
+        m[t] = -FLT_MAX; l[t] = 0.f; lc[t] = 0.f;
 #pragma unroll
-        for (int u = 0; u < DPL; ++u) o[t][u] = 0.f;
+        for (int u = 0; u < DPL; ++u) { o[t][u] = 0.f; oc[t][u] = 0.f; }
     }
     for (int n = wave; n < N; n += 4) {
         const float* row = kv + ((size_t)b * N + n) * ldkv + h * dh;
@@ -59,16 +63,24 @@ __global__ __launch_bounds__(256) void induced_attn_kernel(const float* __restri
             if (!keep) s = -FLT_MAX;                                   // masked_fill_(~mask, -finfo.max), :102-105
             const float mn = fmaxf(m[t], s);
             const float corr = __expf(m[t] - mn), p = __expf(s - mn);
-            l[t] = l[t] * corr + p;
+            {
+                const float base = l[t] * corr, y = p - lc[t] * corr, sum = base + y;
+                lc[t] = (sum - base) - y;
+                l[t] = sum;
+            }
 #pragma unroll
-            for (int u = 0; u < DPL; ++u) o[t][u] = o[t][u] * corr + p * vr[u];
+            for (int u = 0; u < DPL; ++u) {
+                const float base = o[t][u] * corr, y = p * vr[u] - oc[t][u] * corr, sum = base + y;
+                oc[t][u] = (sum - base) - y;
+                o[t][u] = sum;
+            }
             m[t] = mn;
         }
     }
     for (int t = 0; t < T; ++t) {
-        if (lane == 0) { sm[wave][t][0] = m[t]; sm[wave][t][1] = l[t]; }
+        if (lane == 0) { sm[wave][t][0] = m[t]; sm[wave][t][1] = l[t] - lc[t]; }
 #pragma unroll
-        for (int u = 0; u < DPL; ++u) so[wave][t][lane + 64 * u] = o[t][u];
+        for (int u = 0; u < DPL; ++u) so[wave][t][lane + 64 * u] = o[t][u] - oc[t][u];
     }
     __syncthreads();
     // merge the four partial softmaxes (fixed order) and normalise
