@@ -9,9 +9,10 @@ from .layer import EGNN, EGNN_Network, CoorsNorm, exact_arithmetic
 from ._ops import phase_timer, check_range
 from ._abi import EGNNHipError, EGNNRangeError
 from .sparse_adj import SparseAdjacency
+from .sparse_edges import SparseEdges
 from . import sharding
 from .graph import graphed
 
 __all__ = ["EGNN", "EGNN_Network", "CoorsNorm", "phase_timer", "sharding", "graphed", "check_range", "EGNNHipError",
-           "EGNNRangeError", "exact_arithmetic", "SparseAdjacency"]
+           "EGNNRangeError", "exact_arithmetic", "SparseAdjacency", "SparseEdges"]
 __version__ = "0.1.0"

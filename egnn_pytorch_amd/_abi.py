@@ -257,6 +257,12 @@ SIGNATURES = {name: (restype, argtypes) for names, restype, argtypes in (
     ("egnn_edge_features_grad_f32 egnn_edge_features_grad_f64 egnn_edge_features_grad_slot_f32 egnn_edge_features_grad_slot_f64", c_int,
      (c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
       c_void_p, POINTER(c_int64), c_void_p)),
+    ("egnn_edge_features_gather_csr_f32 egnn_edge_features_gather_csr_f64", c_int,
+     (c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+      c_void_p)),
+    ("egnn_edge_features_grad_csr_f32 egnn_edge_features_grad_csr_f64", c_int,
+     (c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+      c_void_p, c_void_p, POINTER(c_int64), c_void_p)),
     ("egnn_edge_bwd_pass_f32", c_int, (POINTER(EdgeBwdArgs), c_void_p)),
     ("egnn_edge_bwd_work_bytes", c_size_t, (c_int64, c_int, c_int, c_int)),
     ("egnn_edge_tail_bwd_f32", c_int, (POINTER(EdgeTailArgs), c_void_p)),

@@ -924,11 +924,62 @@ def _deg_labels(deg, idx, b, n, k):
     return deg, ""
 
 
-def edge_features_gather(lookup, idx, b, n, k):
+def _slot_deg_labels(deg, idx, b, n, k):
+    """(B,N,K) label bytes of the selected pairs, what the _csr entries read: from a SparseLabels (egnn_csr_slot_labels_u8) or from the
+    (B,N,N) map a dense adjacency was expanded to (a byte gather; the dense layer's slots are the map itself)"""
+    if deg is None:
+        return None
+    if isinstance(deg, SparseLabels):
+        return csr_slot_labels(deg, idx, b, n, k)
+    return deg if idx is None else deg.reshape(b * n, n).gather(1, idx.reshape(b * n, k).long()).view(b, n, k)
+
+
+def _csr_checked(lookup, what, idx, b, n, k):
+    csr = lookup.csr
+    if csr.num_graphs != b or csr.n != n:
+        raise ValueError(f"{what}: SparseEdges for {csr.num_graphs} graphs of {csr.n} nodes, call on {b} graphs of {n} "
+                         "(a SparseEdges is per graph: its graph count must equal the batch size)")
+    if idx is not None and (idx.dtype != torch.int32 or not idx.is_contiguous() or tuple(idx.shape) != (b, n, k)):
+        raise ValueError(f"{what}: idx must be a contiguous ({b}, {n}, {k}) int32 tensor")
+    if idx is None and k != n:
+        raise ValueError(f"{what}: the dense layer has K = N (got K = {k}, N = {n})")
+    return csr
+
+
+def _csr_first_table(lookup):
+    """(values, tokens) of a CSR first table as the entries take them: one of the two, never an empty tensor (whose pointer is NULL) --
+    a SparseEdges without entries gets one row that no position refers to"""
+    vals, tok = lookup.edges, lookup.tok
+    if vals is not None and vals.shape[0] == 0:
+        vals = vals.new_zeros(1, lookup.d1)
+    if tok is not None and tok.shape[0] == 0:
+        tok = tok.new_zeros(1)
+    return vals, tok
+
+
+def edge_features_gather(lookup, idx, b, n, k, with_pos=False):
     """(B,N,K,edge_dim) features of the selected pairs from EGNN_Network's look-up tables, in the tables' dtype --
-    egnn_edge_features_gather_f32 / _f64."""
-    dev = (lookup.deg if lookup.deg is not None else (lookup.tok if lookup.tok is not None else lookup.edges)).device
+    egnn_edge_features_gather_f32 / _f64.  A look-up whose first table is a SparseEdges (`lookup.csr`): egnn_edge_features_gather_csr_f32 /
+    _f64, which also finds `pos` (B,N,K) int32, every selected pair's offset into the CSR or -1 -- returned too when `with_pos` (the
+    gradient entry and the second-order path read it)."""
     dtype = _lookup_dtype(lookup, "edge_features_gather")
+    if getattr(lookup, "csr", None) is not None:
+        csr = _csr_checked(lookup, "edge_features_gather", idx, b, n, k)
+        dev = csr.device
+        name = "egnn_edge_features_gather_csr" + ("_f64" if dtype == torch.float64 else "_f32")
+        deg = _slot_deg_labels(lookup.deg, idx, b, n, k)
+        out = empty(b, n, k, lookup.width, dtype=dtype, device=dev)
+        pos = empty(b, n, k, dtype=torch.int32, device=dev)
+        vals, tok = _csr_first_table(lookup)
+        with _timed("edge_features"):
+            rc = getattr(_abi.load(), name)(_ptr(csr.rowptr), _ptr(csr.col), _ptr(vals), _ptr(tok), _ptr(lookup.tok_emb),
+                                            lookup.d1, _ptr(deg), _ptr(lookup.deg_emb), lookup.d2, _ptr(idx), b, n, k, _ptr(pos),
+                                            _ptr(out), _stream())
+        _abi.check(rc, name)
+        return (out, pos) if with_pos else out
+    if with_pos:
+        raise ValueError("edge_features_gather: positions exist for a SparseEdges first table only")
+    dev = (lookup.deg if lookup.deg is not None else (lookup.tok if lookup.tok is not None else lookup.edges)).device
     deg, slot = _deg_labels(lookup.deg, idx, b, n, k)
     name = "egnn_edge_features_gather" + slot + ("_f64" if dtype == torch.float64 else "_f32")
     out = empty(b, n, k, lookup.width, dtype=dtype, device=dev)
@@ -940,12 +991,44 @@ def edge_features_gather(lookup, idx, b, n, k):
     return out
 
 
-def edge_features_grad(lookup, idx, b, n, k, g, want_tok=True, want_deg=True, g_edges=None):
+def _edge_features_grad_csr(lookup, idx, b, n, k, g, dtype, on1, on2, g_values, pos):
+    """`edge_features_grad` for a SparseEdges first table: egnn_edge_features_grad_csr_f32 / _f64"""
+    dev = g.device
+    csr = _csr_checked(lookup, "edge_features_grad", idx, b, n, k)
+    if pos is None:
+        pos = edge_features_gather(lookup, idx, b, n, k, with_pos=True)[1]
+    if pos.dtype != torch.int32 or not pos.is_contiguous() or tuple(pos.shape) != (b, n, k):
+        raise ValueError(f"edge_features_grad: pos must be a contiguous ({b}, {n}, {k}) int32 tensor")
+    if g_values is not None and (lookup.tok is not None or g_values.dtype != dtype or not g_values.is_contiguous()
+                                 or tuple(g_values.shape) != (csr.col.numel(), lookup.d1)):
+        raise ValueError(f"edge_features_grad: g_values must be a contiguous (nnz, d1) {dtype} tensor for float SparseEdges values")
+    name = "egnn_edge_features_grad_csr" + ("_f64" if dtype == torch.float64 else "_f32")
+    deg = _slot_deg_labels(lookup.deg, idx, b, n, k) if on2 else None
+    v1 = lookup.tok_emb.shape[0] if on1 else 0
+    v2 = lookup.deg_emb.shape[0] if on2 else 0
+    g_tok = empty(v1, lookup.d1, dtype=dtype, device=dev) if on1 else None
+    g_deg = empty(v2, lookup.d2, dtype=dtype, device=dev) if on2 else None
+    entry = getattr(_abi.load(), name)
+    args = (_ptr(g), g.stride(0), _ptr(pos), _ptr(_csr_first_table(lookup)[1]) if on1 else None, v1, lookup.d1, _ptr(deg), v2,
+            lookup.d2, _ptr(idx), b, n, k, _ptr(g_tok), _ptr(g_deg), _ptr(g_values))
+    nw = c_int64(0)
+    _abi.check(entry(*args, None, byref(nw), _stream()), name)
+    work = empty(max(1, nw.value), dtype=dtype, device=dev)
+    nw = c_int64(work.numel())
+    with _timed("edge_features_grad"):
+        rc = entry(*args, _ptr(work), byref(nw), _stream())
+    _abi.check(rc, name)
+    return g_tok, g_deg
+
+
+def edge_features_grad(lookup, idx, b, n, k, g, want_tok=True, want_deg=True, g_edges=None, pos=None):
     """The transpose of `edge_features_gather` -- egnn_edge_features_grad_f32 / _f64: g (B N K, >= edge_dim) rows in the tables' dtype
     whose first lookup.width columns are d loss / d the gathered features (row stride g.stride(0)) -> (g_tok_emb (V1, d1) or None,
     g_deg_emb (V2, d2) or None) in that dtype, sums in a fixed order.  g_edges: a zeroed (B,N,N,d1) tensor of that dtype for dense
     float edges, which receives its rows in place.  lookup's label tensors are read for graphs [0, b): pass a lookup sliced to the
-    graphs of g."""
+    graphs of g.  A SparseEdges first table (`lookup.csr`): g_edges is the zeroed (nnz, d1) gradient of its float values -- the whole
+    one, whichever graphs the call covers: the offsets are absolute -- and pos (B,N,K) the positions `edge_features_gather` returned
+    for these graphs (None: looked up again)."""
     dev = g.device
     if g.dim() != 2 or g.stride(1) != 1 or g.shape[0] != b * n * k or g.shape[1] < lookup.width:
         raise ValueError(f"edge_features_grad: g {tuple(g.shape)} / strides {g.stride()} for {b * n * k} edges of width {lookup.width}")
@@ -954,6 +1037,8 @@ def edge_features_grad(lookup, idx, b, n, k, g, want_tok=True, want_deg=True, g_
         raise TypeError(f"edge_features_grad: g must be float32 or float64, matching the tables (g is {g.dtype}, the tables {dtype})")
     on1 = want_tok and lookup.tok is not None
     on2 = want_deg and lookup.deg is not None
+    if getattr(lookup, "csr", None) is not None:
+        return _edge_features_grad_csr(lookup, idx, b, n, k, g, dtype, on1, on2, g_edges, pos)
     deg, slot = _deg_labels(lookup.deg, idx, b, n, k) if on2 else (None, "_slot" if isinstance(lookup.deg, SparseLabels) else "")
     name = "egnn_edge_features_grad" + slot + ("_f64" if dtype == torch.float64 else "_f32")
     v1 = lookup.tok_emb.shape[0] if on1 else 0

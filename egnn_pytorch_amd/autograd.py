@@ -722,7 +722,11 @@ class _LookupGrads:
         self.dtypes = ctx.table_dtypes
         need = ctx.needs_input_grad                         # (EGNNFunction's own layout: the tables are inputs 6, 8, 9)
         self.want = (bool(need[6]) and self.lookup.edges is not None, bool(need[8]), bool(need[9]))
-        self.g_edges = torch.zeros(b, n, n, self.lookup.d1, dtype=self.dtype, device=device) if self.want[0] else None
+        # (a SparseEdges first table: the gradient of its float values, (nnz, d1) -- every chunk stores into the one tensor, the
+        # positions are absolute offsets)
+        self.csr = self.lookup.csr is not None
+        shape = tuple(self.lookup.edges.shape) if (self.csr and self.want[0]) else (b, n, n, self.lookup.d1)
+        self.g_edges = torch.zeros(shape, dtype=self.dtype, device=device) if self.want[0] else None
         self.tok = self.deg = None
 
     @property
@@ -734,9 +738,10 @@ class _LookupGrads:
         d loss / d the gathered features."""
         if not self.active or k == 0:
             return
-        ge = None if self.g_edges is None else self.g_edges[lo:hi]
+        ge = None if self.g_edges is None else (self.g_edges if self.csr else self.g_edges[lo:hi])
+        pos = self.ctx.csr_pos[lo:hi] if self.csr else None     # (the positions the forward's look-up found)
         t, d = _ops_mod().edge_features_grad(self.lookup.graphs(lo, hi), i32, hi - lo, n, k, g_rows, want_tok=self.want[1],
-                                             want_deg=self.want[2], g_edges=ge)
+                                             want_deg=self.want[2], g_edges=ge, pos=pos)
         if t is not None:
             self.tok = t if self.tok is None else self.tok + t
         if d is not None:
@@ -808,8 +813,12 @@ class EGNNFunction(torch.autograd.Function):
             b, n = feats.shape[:2]
             k = n if idx is None else idx.shape[-1]
             with torch.no_grad():
-                edges = (_ops_mod().edge_features_gather(lookup, idx, b, n, k) if k > 0 else
+                edges = (_ops_mod().edge_features_gather(lookup, idx, b, n, k, with_pos=lookup.csr is not None) if k > 0 else
                          torch.empty(b, n, 0, lookup.width, dtype=lookup.dtype, device=feats.device))
+            # (a SparseEdges first table: the position of every selected pair in its rows, kept for the gradient entry and `_lookup_rows`)
+            ctx.csr_pos = None
+            if lookup.csr is not None:
+                edges, ctx.csr_pos = edges if k > 0 else (edges, torch.empty(b, n, 0, dtype=torch.int32, device=feats.device))
             ctx.table_dtypes = tuple(None if t is None else t.dtype for t in lookup.live)
         ctx.layer = layer
         ctx.has_u = u_pre is not None                    # (E, 16 ceil(m_dim / 16)) fp32: E x m, not E x H
@@ -1843,15 +1852,26 @@ def _backward_native(ctx, g_node, g_coors):
             lk.outputs() if lk is not None else (g_edges.to(in_dtypes[2]) if want_ge else None), *out_params)
 
 
-def _lookup_rows(lookup, idx, b, n, k):
+def _lookup_rows(lookup, idx, b, n, k, pos=None):
     """The (B,N,K,edge_dim) features of the selected pairs, gathered from the caller's tensors behind an EdgeLookup (`live`: the dense
-    float edges, the embedding weights) by differentiable indexing: E x D, what egnn_edge_features_gather_f32 reads, under autograd."""
+    float edges, the embedding weights) by differentiable indexing: E x D, what egnn_edge_features_gather_f32 reads, under autograd.
+    pos: a SparseEdges first table's positions of the selected pairs (B,N,K), -1 where its rows do not hold one -- `values` / the
+    token rows are indexed through them, a missing pair reading zeros / token 0 as in the dense image."""
     edges, tok_w, deg_w = lookup.live
     dev = (lookup.tok if lookup.tok is not None else (lookup.deg if lookup.deg is not None else edges)).device
     j = torch.arange(n, device=dev)[None, None, :].expand(b, n, k) if idx is None else idx.long()
     pair = (torch.arange(b * n, device=dev).view(b, n, 1) * n + j).reshape(-1)          # (b N + i) N + j
     cols = []
-    if lookup.d1:
+    if lookup.d1 and lookup.csr is not None:
+        held = pos.reshape(-1) >= 0
+        at = pos.reshape(-1).long().clamp(min=0)
+        if lookup.tok is not None:
+            tok = lookup.tok[at] if lookup.tok.numel() else at   # (no entries: every pair is missing)
+            cols.append(tok_w[torch.where(held, tok, torch.zeros_like(tok))])
+        else:
+            rows = edges[at] if edges.shape[0] else edges.new_zeros(at.numel(), lookup.d1)
+            cols.append(torch.where(held[:, None], rows, torch.zeros_like(rows)))
+    elif lookup.d1:
         cols.append(tok_w[lookup.tok.reshape(-1)[pair]] if lookup.tok is not None else edges.reshape(-1, lookup.d1)[pair])
     if lookup.d2:
         if isinstance(lookup.deg, SparseLabels):                # (label CSR: the labels of the selected pairs, per slot)
@@ -1882,7 +1902,8 @@ def _backward_twice(ctx, g_node, g_coors):
     idx = None if idx32 is None else idx32.long()
     by_k = getattr(ctx, "edges_by_k", False)
     lookup = ctx.lookup
-    e_in = _lookup_rows(lookup, idx, b, n, k).to(pd) if by_k else (None if edges is None else edges.to(pd))
+    e_in = (_lookup_rows(lookup, idx, b, n, k, pos=getattr(ctx, "csr_pos", None)).to(pd) if by_k else
+            (None if edges is None else edges.to(pd)))
     out_n, out_c = layer_given_neighbors(layer, feats.to(pd), coors.to(pd), e_in, mask, idx, None if rank is None else rank.to(pd),
                                          ctx.valid_radius, drop=getattr(ctx, "drop", None), edges_by_k=by_k, edge_hidden=True)
     unused = _unused_params(layer, ctx)

@@ -160,10 +160,14 @@ struct FeatGradTable {
 
 __device__ __forceinline__ int fgrad_groups(int D) { return D <= 64 ? 64 / D : 1; }
 
-template <typename T, bool SLOT = false>
+// CSR: the first table's labels are the values of a CSR (egnn_pytorch_amd.SparseEdges), `tok` (nnz) read at pos[e] -- the position
+// egnn_edge_features_gather_csr_f32 / _f64 found for slot e; a slot whose row does not hold its pair (pos < 0) carries token 0, as the
+// dense image does.  The same walk and the same sums otherwise: the _csr entries.
+template <typename T, bool SLOT = false, bool CSR = false>
 __global__ __launch_bounds__(256) void edge_features_grad_part_kernel(const T* __restrict__ g, int64_t ld,
                                                                       const int64_t* __restrict__ tok, const uint8_t* __restrict__ deg,
-                                                                      const int32_t* __restrict__ idx, int N, int K, int64_t E,
+                                                                      const int32_t* __restrict__ idx, const int32_t* __restrict__ pos,
+                                                                      int N, int K, int64_t E,
                                                                       int64_t per, FeatGradTable t1, FeatGradTable t2,
                                                                       T* __restrict__ part, int64_t stride)
 {
@@ -194,7 +198,11 @@ __global__ __launch_bounds__(256) void edge_features_grad_part_kernel(const T* _
         const int j = idx ? idx[e] : k;
         if ((unsigned)j >= (unsigned)N) return -1;
         const int64_t pair = node * N + j;
-        const int64_t v = (second ? (int64_t)deg[SLOT ? e : pair] : tok[pair]) - vb0;
+        int64_t v;
+        if (second) v = (int64_t)deg[SLOT ? e : pair];
+        else if (CSR) { const int32_t ps = pos[e]; v = ps >= 0 ? tok[ps] : (int64_t)0; }
+        else v = tok[pair];
+        v -= vb0;
         return (v >= 0 && v < vn) ? (int)v : -1;
     };
     if (p < P) {
@@ -265,6 +273,22 @@ __global__ __launch_bounds__(256) void edge_features_grad_dense_kernel(const T* 
     }
 }
 
+// ... and of float CSR values: g_values[pos[e], :] = g[e, :d1] where the row holds the pair -- a plain store as well (the K pairs of a row
+// are distinct and rows are per graph, so no two slots share a position)
+template <typename T>
+__global__ __launch_bounds__(256) void edge_features_grad_values_kernel(const T* __restrict__ g, int64_t ld,
+                                                                        const int32_t* __restrict__ pos, int d1, int64_t total,
+                                                                        T* __restrict__ g_values)
+{
+    for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (int64_t)gridDim.x * 256) {
+        const int64_t e = o / d1;
+        const int c = (int)(o - e * d1);
+        const int32_t ps = pos[e];
+        if (ps < 0) continue;
+        g_values[(int64_t)ps * d1 + c] = g[e * ld + c];
+    }
+}
+
 FeatGradTable fgrad_table(bool on, int V, int D, int col0, int64_t off, int wave_elems)
 {
     FeatGradTable t{};
@@ -279,10 +303,11 @@ FeatGradTable fgrad_table(bool on, int V, int D, int col0, int64_t off, int wave
     return t;
 }
 
-template <typename T, bool SLOT = false>
+// CSR (with SLOT): edge_tok holds the tokens of a CSR's entries and g_edges is g_values (nnz, d1), both reached through pos (B,N,K)
+template <typename T, bool SLOT = false, bool CSR = false>
 int edge_features_grad(const T* g, int64_t ld, const int64_t* edge_tok, int V1, int d1, const uint8_t* adj_deg, int V2, int d2,
                        const int32_t* idx, int B, int N, int K, T* g_tok_emb, T* g_deg_emb, T* g_edges, T* work,
-                       int64_t* work_floats, void* stream)
+                       int64_t* work_floats, void* stream, const int32_t* pos = nullptr)
 {
     constexpr int WAVE_ELEMS = FGRAD_LDS_WAVE_ELEMS<T>;
     if (!work_floats) return EGNN_E_NULLPTR;
@@ -311,21 +336,25 @@ int edge_features_grad(const T* g, int64_t ld, const int64_t* edge_tok, int V1, 
         return EGNN_OK;
     }
     if (*work_floats < G * stride) return EGNN_E_SHAPE;
-    if (!g) return EGNN_E_NULLPTR;
+    if (!g || (CSR && !pos)) return EGNN_E_NULLPTR;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (g_edges) {
         const int64_t total = E * d1;
         int64_t blocks = (total + 255) / 256;
         if (blocks > 65536) blocks = 65536;
-        hipLaunchKernelGGL(edge_features_grad_dense_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, g, ld, idx, N, K, d1, total,
-                           g_edges);
+        if (CSR)
+            hipLaunchKernelGGL(edge_features_grad_values_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, g, ld, pos, d1, total,
+                               g_edges);
+        else
+            hipLaunchKernelGGL(edge_features_grad_dense_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, g, ld, idx, N, K, d1, total,
+                               g_edges);
         const int rc = egnn_launch_status();
         if (rc) return rc;
     }
     if (stride == 0) return EGNN_OK;
     const int64_t per = (E + G - 1) / G;
-    hipLaunchKernelGGL((edge_features_grad_part_kernel<T, SLOT>), dim3((unsigned)G, (unsigned)(t1.nb + t2.nb)), dim3(256), 0, st, g, ld,
-                       edge_tok, adj_deg, idx, N, K, E, per, t1, t2, work, stride);
+    hipLaunchKernelGGL((edge_features_grad_part_kernel<T, SLOT, CSR>), dim3((unsigned)G, (unsigned)(t1.nb + t2.nb)), dim3(256), 0, st, g,
+                       ld, edge_tok, adj_deg, idx, pos, N, K, E, per, t1, t2, work, stride);
     int rc = egnn_launch_status();
     if (rc) return rc;
     hipLaunchKernelGGL(edge_features_grad_sum_kernel<T>, dim3((unsigned)((stride + 255) / 256)), dim3(256), 0, st, work, stride, (int)G,
@@ -369,4 +398,26 @@ extern "C" int egnn_edge_features_grad_slot_f64(const double* g, int64_t ld, con
 {
     return edge_features_grad<double, true>(g, ld, edge_tok, V1, d1, slot_deg, V2, d2, idx, B, N, K, g_tok_emb, g_deg_emb, g_edges, work,
                                             work_floats, stream);
+}
+
+// The CSR first table (egnn_pytorch_amd.SparseEdges): tokens (nnz) / g_values (nnz, d1) reached through pos (B,N,K), the positions
+// egnn_edge_features_gather_csr_f32 / _f64 wrote; the degree labels per slot.
+extern "C" int egnn_edge_features_grad_csr_f32(const float* g, int64_t ld, const int32_t* pos, const int64_t* tokens, int V1, int d1,
+                                               const uint8_t* slot_deg, int V2, int d2, const int32_t* idx, int B, int N, int K,
+                                               float* g_tok_emb, float* g_deg_emb, float* g_values, float* work, int64_t* work_floats,
+                                               void* stream)
+{
+    if (!pos) return EGNN_E_NULLPTR;
+    return edge_features_grad<float, true, true>(g, ld, tokens, V1, d1, slot_deg, V2, d2, idx, B, N, K, g_tok_emb, g_deg_emb, g_values,
+                                                 work, work_floats, stream, pos);
+}
+
+extern "C" int egnn_edge_features_grad_csr_f64(const double* g, int64_t ld, const int32_t* pos, const int64_t* tokens, int V1, int d1,
+                                               const uint8_t* slot_deg, int V2, int d2, const int32_t* idx, int B, int N, int K,
+                                               double* g_tok_emb, double* g_deg_emb, double* g_values, double* work,
+                                               int64_t* work_floats, void* stream)
+{
+    if (!pos) return EGNN_E_NULLPTR;
+    return edge_features_grad<double, true, true>(g, ld, tokens, V1, d1, slot_deg, V2, d2, idx, B, N, K, g_tok_emb, g_deg_emb, g_values,
+                                                  work, work_floats, stream, pos);
 }

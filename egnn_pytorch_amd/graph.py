@@ -18,6 +18,7 @@ import torch
 
 from . import _ops
 from .sparse_adj import SparseAdjacency
+from .sparse_edges import SparseEdges
 
 
 def graphed(module, *example_inputs, warmup: int = 2, range_check: str | None = None, **example_kwargs):
@@ -35,6 +36,9 @@ def graphed(module, *example_inputs, warmup: int = 2, range_check: str | None = 
             (getattr(m, "num_adj_degrees", None) or 0) > 1 for m in module.modules()):
         raise NotImplementedError("graphed(): num_adj_degrees > 1 with a SparseAdjacency reads each degree's entry count back from the "
                                   "device (the CSR expansion sizes its buffers from it) and cannot be captured; pass the dense adjacency")
+    if any(isinstance(a, SparseEdges) for a in list(example_inputs) + list(example_kwargs.values())):
+        raise NotImplementedError("graphed(): a SparseEdges is not supported -- its values would be baked into the graph and could not be "
+                                  "replaced between replays; run the module eagerly, or pass dense edges")
     args = [a.clone() if torch.is_tensor(a) else a for a in example_inputs]
     kwargs = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in example_kwargs.items()}
     dev = next(a for a in list(args) + list(kwargs.values()) if torch.is_tensor(a)).device

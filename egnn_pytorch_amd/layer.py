@@ -25,6 +25,7 @@ from torch import nn
 from . import _abi, _dropout, _ops, _weights, autograd as _autograd
 from .attention import GlobalLinearAttention
 from .sparse_adj import SparseAdjacency, SparseLabels
+from .sparse_edges import SparseEdges
 
 _SPATIAL_ORDER = os.environ.get("EGNN_SPATIAL_ORDER", "1") != "0"     # scheduling knob only; results do not depend on it
 _SLOT_PREP = os.environ.get("EGNN_SLOT_PREP", "1") != "0"             # per-slot records for the edge pass's setup (same results)
@@ -101,9 +102,15 @@ class EdgeLookup:
     `deg_emb` (`live`) are the caller's tensors -- the dense float edges and the embedding weights -- and the kernels read detached
     copies of them in `dtype`, the compute dtype of the layers that consume them: float32, or float64 for float64 modules
     (egnn_edge_features_gather_f64).  Under autograd the layer hands the live ones to autograd.EGNNFunction as differentiable inputs:
-    their gradients come from egnn_edge_features_grad_f32 / _f64, a reduction over the selected pairs only."""
+    their gradients come from egnn_edge_features_grad_f32 / _f64, a reduction over the selected pairs only.
+    `csr`: the first table as a SparseEdges -- its float values (nnz, d) take the place of `edges` (live[0], differentiable, with the
+    detached copy in `dtype`) or its tokens (nnz,) that of `tok`, both read through the positions the kernel finds in `csr`'s rows
+    (egnn_edge_features_gather_csr_f32 / _f64); nothing of size N^2 then stands behind the first table."""
 
-    def __init__(self, edges=None, tok=None, tok_emb=None, deg=None, deg_emb=None, dtype=torch.float32):
+    def __init__(self, edges=None, tok=None, tok_emb=None, deg=None, deg_emb=None, dtype=torch.float32, csr=None):
+        self.csr = csr
+        if csr is not None:
+            edges, tok = (None, csr.values) if csr.is_tokens else (csr.values, None)
         self.live = (edges, tok_emb if tok is not None else None, deg_emb if deg is not None else None)
         self.tok = None if tok is None else tok.contiguous().long()
         self.deg = None if deg is None else deg.contiguous()
@@ -141,9 +148,12 @@ class EdgeLookup:
         """The same tables for graphs [lo, hi) of the batch (the labels and dense edges sliced, the embedding tables shared)."""
         out = copy.copy(self)
         out._casts = {}
-        out.live = (None if self.live[0] is None else self.live[0][lo:hi],) + tuple(self.live[1:])
-        out.edges = None if self.edges is None else self.edges[lo:hi]
-        out.tok = None if self.tok is None else self.tok[lo:hi]
+        if self.csr is not None:                                # (a slice of rowptr: values / tokens are shared, offsets absolute)
+            out.csr = self.csr.graphs(lo, hi)
+        else:
+            out.live = (None if self.live[0] is None else self.live[0][lo:hi],) + tuple(self.live[1:])
+            out.edges = None if self.edges is None else self.edges[lo:hi]
+            out.tok = None if self.tok is None else self.tok[lo:hi]
         out.deg = None if self.deg is None else (self.deg.graphs(lo, hi) if isinstance(self.deg, SparseLabels) else self.deg[lo:hi])
         return out
 
@@ -241,9 +251,16 @@ class EGNN(nn.Module):
         if (edges is not None) != (self.edge_dim > 0):
             raise ValueError("`edges` must be passed if and only if edge_dim > 0")
         b, n = feats.shape[:2]
-        if isinstance(edges, EdgeLookup):
+        if isinstance(edges, EdgeLookup):                           # (a SparseEdges arrives as one: `forward` wraps it)
             if edges.width != self.edge_dim:
                 raise ValueError(f"edge look-up tables give {edges.width} features per pair, edge_dim is {self.edge_dim}")
+            if edges.csr is not None:
+                if tuple(edges.csr.shape[:3]) != (b, n, n):
+                    raise ValueError(f"SparseEdges shape {tuple(edges.csr.shape)} != {(b, n, n)} + features: it is per graph, its graph "
+                                     "count must equal the batch size")
+                if edges.csr.device != feats.device:
+                    raise RuntimeError(f"Expected all tensors to be on the same device: feats is on {feats.device}, edges on "
+                                       f"{edges.csr.device}")
         elif edges is not None and tuple(edges.shape) != (b, n, n, self.edge_dim):
             raise ValueError(f"edges shape {tuple(edges.shape)} != {(b, n, n, self.edge_dim)}")
         if mask is not None and tuple(mask.shape) != (b, n):
@@ -257,8 +274,19 @@ class EGNN(nn.Module):
             if t is not None and t.device != feats.device:
                 raise RuntimeError(f"Expected all tensors to be on the same device: feats is on {feats.device}, {name} on {t.device}")
 
+    def _sparse_edges_lookup(self, edges):
+        """A SparseEdges of float values as the look-up table the kernels read (EdgeLookup with a CSR first table): the layer then takes
+        `_forward_hip` / `_forward_exact`, as for every EdgeLookup."""
+        if edges.is_tokens:
+            raise TypeError("EGNN takes a SparseEdges of float values (nnz, edge_dim); bond tokens are EGNN_Network(num_edge_tokens=...)'s")
+        if edges.values.dtype not in _FLOAT_DTYPES:
+            raise NotImplementedError(f"the gfx950 path takes floating-point edges (got {edges.values.dtype})")
+        return EdgeLookup(csr=edges, dtype=self.compute_dtype())
+
     def forward(self, feats, coors, edges=None, mask=None, adj_mat=None):
         out = None
+        if isinstance(edges, SparseEdges):
+            edges = self._sparse_edges_lookup(edges)
         try:
             with _ops.early_publish():                              # (the one-call C forward may publish the status words itself)
                 out = self._call(feats, coors, edges, mask, adj_mat, None)[:2]
@@ -846,7 +874,7 @@ class EGNN_Network(nn.Module):
         # otherwise nothing is recorded
         grad = torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters()) or
                                             any(torch.is_tensor(t) and t.is_floating_point() and t.requires_grad
-                                                for t in (feats, coors, edges)))
+                                                for t in (feats, coors, edges.values if isinstance(edges, SparseEdges) else edges)))
         try:
             with _ops.early_publish(last=False) as early:           # (`_forward` sets `last` in front of the last layer)
                 with torch.enable_grad() if grad else torch.no_grad():
@@ -875,8 +903,18 @@ class EGNN_Network(nn.Module):
         # the same pairs (egnn_edge_features_grad_f32 / _f64).  The tables' kernel-side copies take the layers' compute dtype, made once
         # here for all of them: float64 for a float64 network, which runs on the tables like any other.
         lookup_dtype = self.layers[0][1].compute_dtype() if len(self.layers) else torch.float32
-        tok = tok_emb = None
-        if edges is not None and self.edge_emb is not None:
+        tok = tok_emb = csr = None
+        if isinstance(edges, SparseEdges):
+            # bond tokens / bond features on CSR rows: the first table of the look-up, read through the positions the kernel finds in
+            # the rows (csrc/edge_csr.hip) -- no (B,N,N) token map, no (B,N,N,edge_dim) tensor and no gradient of that size
+            if edges.is_tokens != (self.edge_emb is not None):
+                raise TypeError("a SparseEdges holds int64 tokens for a network with num_edge_tokens, float values otherwise "
+                                f"(got {edges.values.dtype})")
+            if not edges.is_tokens and edges.values.dtype not in _FLOAT_DTYPES:
+                raise NotImplementedError(f"the gfx950 path takes floating-point edges (got {edges.values.dtype})")
+            csr, edges = edges, None
+            tok_emb = self.edge_emb.weight if csr.is_tokens else None
+        elif edges is not None and self.edge_emb is not None:
             tok, tok_emb, edges = edges, self.edge_emb.weight, None
 
         if self.num_adj_degrees is not None:
@@ -890,10 +928,11 @@ class EGNN_Network(nn.Module):
             else:
                 adj_mat, adj_indices = _ops.adj_expand(adj_mat, b, self.num_adj_degrees)
             if self.adj_emb is not None:
-                edges = EdgeLookup(edges=edges, tok=tok, tok_emb=tok_emb, deg=adj_indices, deg_emb=self.adj_emb.weight, dtype=lookup_dtype)
-                tok = None
-        if tok is not None:                                         # edge tokens without adjacency degrees
-            edges = EdgeLookup(tok=tok, tok_emb=tok_emb, dtype=lookup_dtype)
+                edges = EdgeLookup(edges=edges, tok=tok, tok_emb=tok_emb, deg=adj_indices, deg_emb=self.adj_emb.weight, dtype=lookup_dtype,
+                                   csr=csr)
+                tok = csr = None
+        if tok is not None or csr is not None:                      # edge tokens / a SparseEdges without adjacency degrees
+            edges = EdgeLookup(tok=tok, tok_emb=tok_emb, dtype=lookup_dtype, csr=csr)
 
         global_tokens = None
         if self.global_tokens is not None:

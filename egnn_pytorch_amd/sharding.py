@@ -13,6 +13,7 @@ import torch
 import torch.distributed as dist
 
 from .sparse_adj import SparseAdjacency
+from .sparse_edges import SparseEdges
 
 
 def shard_bounds(batch: int, rank: int, world: int):
@@ -29,7 +30,7 @@ def shard_batch(rank: int, world: int, *tensors, shared=()):
     all graphs share -- a 2-D `(N, N)` adjacency -- are named explicitly in `shared` (compared by identity) and are
     replicated, not split; there is no shape heuristic (a `(B, N)` mask with B == N looks exactly like an adjacency).
     Every other tensor must have the batch as its leading dimension.  A `SparseAdjacency` goes the same way: a batched one is sliced
-    with `graphs(lo, hi)`, one that all graphs share is named in `shared`."""
+    with `graphs(lo, hi)`, one that all graphs share is named in `shared`; a `SparseEdges` is always per graph and is sliced likewise."""
     shared_ids = {id(t) for t in shared if t is not None}
     per_graph = [t for t in tensors if t is not None and id(t) not in shared_ids]
     if not per_graph:
@@ -46,7 +47,7 @@ def shard_batch(rank: int, world: int, *tensors, shared=()):
             if t.shape[0] != bsz:
                 raise ValueError(f"per-graph tensor with leading dim {t.shape[0]} != batch {bsz} "
                                  f"(pass tensors shared by all graphs via shared=(...))")
-            out.append(t.graphs(lo, hi) if isinstance(t, SparseAdjacency) else t[lo:hi])
+            out.append(t.graphs(lo, hi) if isinstance(t, (SparseAdjacency, SparseEdges)) else t[lo:hi])
     return out
 
 

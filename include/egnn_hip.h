@@ -529,6 +529,43 @@ int egnn_edge_features_grad_slot_f64(const double* g, int64_t ld, const int64_t*
                                      const uint8_t* slot_deg, int V2, int d2, const int32_t* idx, int B, int N, int K,
                                      double* g_tok_emb, double* g_deg_emb, double* g_edges, double* work, int64_t* work_floats,
                                      void* stream);
+/* The first table given as the VALUES OF A CSR (egnn_pytorch_amd.SparseEdges) instead of a (B,N,N,..) tensor: rowptr (B, N + 1) int64,
+ * absolute offsets into col (nnz) int32, every row strictly ascending (always per graph: no shared form), with either values (nnz, d1)
+ * -- bond features -- or tokens (nnz) int64 and edge_tok_emb (T, d1) -- bond tokens; exactly one of the two is not NULL.  The pattern is
+ * the CSR's own: it need not be the adjacency's.  The position look-up is fused with the gather (csrc/edge_csr.hip): for j = idx[b,i,k]
+ * (idx NULL: dense, j = k, K = N)
+ *   pos[b,i,k]   = the offset of j in row i of graph b, or -1 where the row does not hold j or (unsigned)j >= N      (B,N,K) int32
+ *   out[b,i,k,:] = [ values[pos] | edge_tok_emb[tokens[pos]]   (pos < 0: zeros | edge_tok_emb[0])   |   adj_deg_emb[slot_deg[b,i,k]] ]
+ * i.e. what egnn_edge_features_gather_slot_f32 returns for the dense image (zeros / token 0 at the pairs the rows do not hold), bit for
+ * bit: a copy.  slot_deg / adj_deg_emb (d2 > 0) as in the _slot entries.  pos is an output the caller keeps: the _grad_csr entries
+ * read it.  A wave owns a node; every slot's position is a binary search in the node's sorted row.  Errors, all before the launch:
+ * EGNN_E_NULLPTR (rowptr, pos, out, a table that d1 / d2 needs); EGNN_E_SHAPE for non-positive B, N, K or d1, d2 < 0, both or neither of
+ * values / tokens, idx NULL with K != N.  The CSR arrays are not read on the host and not checked on the device: offsets outside col, rows
+ * out of order and nnz > 2^31 - 1 are the caller's to exclude (SparseEdges validates them). */
+int egnn_edge_features_gather_csr_f32(const int64_t* rowptr, const int32_t* col, const float* values, const int64_t* tokens,
+                                      const float* edge_tok_emb, int d1, const uint8_t* slot_deg, const float* adj_deg_emb, int d2,
+                                      const int32_t* idx, int B, int N, int K, int32_t* pos, float* out, void* stream);
+int egnn_edge_features_gather_csr_f64(const int64_t* rowptr, const int32_t* col, const double* values, const int64_t* tokens,
+                                      const double* edge_tok_emb, int d1, const uint8_t* slot_deg, const double* adj_deg_emb, int d2,
+                                      const int32_t* idx, int B, int N, int K, int32_t* pos, double* out, void* stream);
+/* Its transpose, egnn_edge_features_grad_slot_f32 / _f64 with the first table reached through pos (B,N,K), as the entry above wrote it:
+ *   g_values[pos[e], :] = g[e, :d1]   where pos[e] >= 0: float values (tokens NULL) -- a plain store, the K pairs of a row are distinct
+ *                                     and rows are per graph; the caller zeroes g_values (nnz, d1), entries no edge selected keep their 0
+ *   g_tok_emb[v, :] = sum of g[e, :d1] over the edges whose slot token is v: tokens[pos[e]], or 0 where pos[e] < 0   (V1 x d1)
+ *   g_deg_emb as in the _slot entries.
+ * The same kernels as the dense entries with one more template switch -- the same G, walk and order of every sum -- so the bits are those
+ * of egnn_edge_features_grad_slot_f32 / _f64 called with the dense image; no float atomics, two runs give the same bits.  work NULL =
+ * size query (*work_floats receives the size, nothing is launched), otherwise *work_floats is the size of `work`.  Errors before any
+ * launch as above, and EGNN_E_NULLPTR for pos NULL, EGNN_E_SHAPE for g_values together with tokens.  pos is not checked on the device:
+ * it must hold offsets inside tokens / g_values or negative numbers. */
+int egnn_edge_features_grad_csr_f32(const float* g, int64_t ld, const int32_t* pos, const int64_t* tokens, int V1, int d1,
+                                    const uint8_t* slot_deg, int V2, int d2, const int32_t* idx, int B, int N, int K,
+                                    float* g_tok_emb, float* g_deg_emb, float* g_values, float* work, int64_t* work_floats,
+                                    void* stream);
+int egnn_edge_features_grad_csr_f64(const double* g, int64_t ld, const int32_t* pos, const int64_t* tokens, int V1, int d1,
+                                    const uint8_t* slot_deg, int V2, int d2, const int32_t* idx, int B, int N, int K,
+                                    double* g_tok_emb, double* g_deg_emb, double* g_values, double* work, int64_t* work_floats,
+                                    void* stream);
 
 /* Backward of the edge pass without anything of size E x H in memory (autograd of egnn_pytorch.py:279-287;
  * csrc/edge_bwd.hip).  One call = one pass over a list of L entries (edges) grouped by a key node: by the source node i
