@@ -191,10 +191,11 @@ SIGNATURES = {name: (restype, argtypes) for names, restype, argtypes in (
      (c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p)),
     ("egnn_knn_select_csr_f32 egnn_knn_select_csr_f64", c_int,
      (c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p)),
-    ("egnn_knn_grid_workspace_bytes egnn_dest_lists_capacity", c_size_t, (c_int, c_int, c_int)),
-    ("egnn_knn_select_grid_f32", c_int,
+    ("egnn_knn_grid_workspace_bytes egnn_knn_grid_workspace_bytes_f64 egnn_dest_lists_capacity", c_size_t, (c_int, c_int, c_int)),
+    ("egnn_knn_grid_rowflag_offset_f64", c_size_t, (c_int, c_int)),
+    ("egnn_knn_select_grid_f32 egnn_knn_select_grid_f64", c_int,
      (c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p)),
-    ("egnn_knn_select_grid_csr_f32", c_int,
+    ("egnn_knn_select_grid_csr_f32 egnn_knn_select_grid_csr_f64", c_int,
      (c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p)),
     # adjacency: CSR expansion, degrees, dense expansion
     ("egnn_adj_csr_workspace_bytes egnn_adj_expand_workspace_bytes", c_size_t, (c_int, c_int)),

@@ -411,22 +411,33 @@ def knn_select_stream(coors, mask, adj_mat, k, out=None):
     return _knn_select(coors, mask, adj_mat, k, out, "egnn_knn_select_stream")
 
 
-KNN_GRID_KMAX = 128           # the K limit of egnn_knn_select_grid_f32 / _grid_csr_f32 (csrc/knn_grid.hip: KG_KMAX)
+KNN_GRID_KMAX = 128           # the K limit of egnn_knn_select_grid_f32 / _f64 and _grid_csr_f32 / _f64 (csrc/knn_grid.hip: KG_KMAX)
 
 
-def knn_grid_workspace(b, n, k, device):
-    """the workspace of `knn_select_grid` for (B, N, K): egnn_knn_grid_workspace_bytes bytes, allocated on the current stream"""
-    return empty(_abi.load().egnn_knn_grid_workspace_bytes(b, n, k), dtype=torch.uint8, device=device)
+def _grid_suffix(dtype):
+    """the entry suffix of the cell-grid selection for coordinates of `dtype`: float32, or float64 (a float64 module)"""
+    if dtype == torch.float32:
+        return "_f32"
+    if dtype == torch.float64:
+        return "_f64"
+    raise TypeError(f"knn_select_grid takes float32 or float64 coordinates (got {dtype})")
+
+
+def knn_grid_workspace(b, n, k, device, dtype=torch.float32):
+    """the workspace of `knn_select_grid` for (B, N, K) and coordinates of `dtype`: egnn_knn_grid_workspace_bytes bytes (float64:
+    egnn_knn_grid_workspace_bytes_f64 -- its sorted records are twice as wide), allocated on the current stream"""
+    query = "egnn_knn_grid_workspace_bytes" + ("_f64" if _grid_suffix(dtype) == "_f64" else "")
+    return empty(getattr(_abi.load(), query)(b, n, k), dtype=torch.uint8, device=device)
 
 
 def knn_select_grid(coors, mask, k, out=None, ws=None, adj=None):
-    """knn_select on the cell-grid kernels (egnn_knn_select_grid_f32): fp32 coordinates, coor_dim == 3, K <= 128; the
-    same outputs bit for bit at a cost per row bounded by its neighbourhood, not by N.  ws: the workspace (`knn_grid_workspace`), allocated
-    here on the current stream when None -- a caller that runs this on a side stream allocates `out` and `ws` on its launch stream.
-    adj: None or a SparseAdjacency (egnn_knn_select_grid_csr_f32: the outputs of `knn_select_csr`); a dense map has no grid entry."""
+    """knn_select on the cell-grid kernels (egnn_knn_select_grid_f32; float64 coordinates: egnn_knn_select_grid_f64, rank in float64):
+    coor_dim == 3, K <= 128; the same outputs bit for bit at a cost per row bounded by its neighbourhood, not by N.  Any other dtype:
+    TypeError.  ws: the workspace (`knn_grid_workspace` for the coordinates' dtype), allocated here on the current stream when None
+    -- a caller that runs this on a side stream allocates `out` and `ws` on its launch stream.
+    adj: None or a SparseAdjacency (egnn_knn_select_grid_csr_f32 / _f64: the outputs of `knn_select_csr`); a dense map has no grid entry."""
     b, n, cdim = coors.shape
-    if coors.dtype != torch.float32:
-        raise TypeError(f"knn_select_grid takes float32 coordinates (got {coors.dtype})")
+    sfx = _grid_suffix(coors.dtype)
     if adj is not None:
         if not isinstance(adj, SparseAdjacency):
             raise TypeError("knn_select_grid takes the adjacency as a SparseAdjacency (a dense map selects on the all-pairs kernels)")
@@ -438,20 +449,22 @@ def knn_select_grid(coors, mask, k, out=None, ws=None, adj=None):
         idx, rank = out
     else:
         idx = empty(b, n, k, dtype=torch.int32, device=coors.device)
-        rank = empty(b, n, k, dtype=torch.float32, device=coors.device)
+        rank = empty(b, n, k, dtype=coors.dtype, device=coors.device)
     m8 = _u8(mask)
     if ws is None:
-        ws = knn_grid_workspace(b, n, k, coors.device)
+        ws = knn_grid_workspace(b, n, k, coors.device, coors.dtype)
     if adj is not None:
+        name = "egnn_knn_select_grid_csr" + sfx
         with _timed("knn_select_grid"):
-            rc = _abi.load().egnn_knn_select_grid_csr_f32(_ptr(coors), _ptr(m8), _ptr(adj.rowptr), _ptr(adj.col) if adj.col.numel() else None,
-                                                          0 if adj.shared else n + 1, b, n, k, cdim, _ptr(idx), _ptr(rank), _ptr(ws),
-                                                          ws.numel(), _stream())
-        _abi.check(rc, "egnn_knn_select_grid_csr_f32")
+            rc = getattr(_abi.load(), name)(_ptr(coors), _ptr(m8), _ptr(adj.rowptr), _ptr(adj.col) if adj.col.numel() else None,
+                                            0 if adj.shared else n + 1, b, n, k, cdim, _ptr(idx), _ptr(rank), _ptr(ws), ws.numel(),
+                                            _stream())
+        _abi.check(rc, name)
         return idx, rank
+    name = "egnn_knn_select_grid" + sfx
     with _timed("knn_select_grid"):
-        rc = _abi.load().egnn_knn_select_grid_f32(_ptr(coors), _ptr(m8), b, n, k, cdim, _ptr(idx), _ptr(rank), _ptr(ws), ws.numel(), _stream())
-    _abi.check(rc, "egnn_knn_select_grid_f32")
+        rc = getattr(_abi.load(), name)(_ptr(coors), _ptr(m8), b, n, k, cdim, _ptr(idx), _ptr(rank), _ptr(ws), ws.numel(), _stream())
+    _abi.check(rc, name)
     return idx, rank
 
 

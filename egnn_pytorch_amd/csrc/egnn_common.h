@@ -331,6 +331,12 @@ int egnn_knn_stream_flagged_f32(const float* coors, const uint8_t* mask, int B, 
 int egnn_knn_stream_flagged_csr_f32(const float* coors, const uint8_t* mask, const int64_t* rowptr, const int32_t* col,
                                     int64_t rowptr_graph_stride, int B, int N, int K, const uint8_t* rowflag, int32_t* idx_out,
                                     float* rank_out, void* stream);
+// ... and both for double coordinates (the float64 cell grid: egnn_knn_select_grid_f64 / _grid_csr_f64)
+int egnn_knn_stream_flagged_f64(const double* coors, const uint8_t* mask, int B, int N, int K, const uint8_t* rowflag, int32_t* idx_out,
+                                double* rank_out, void* stream);
+int egnn_knn_stream_flagged_csr_f64(const double* coors, const uint8_t* mask, const int64_t* rowptr, const int32_t* col,
+                                    int64_t rowptr_graph_stride, int B, int N, int K, const uint8_t* rowflag, int32_t* idx_out,
+                                    double* rank_out, void* stream);
 
 static inline int egnn_launch_status() {
     hipError_t e = hipGetLastError();

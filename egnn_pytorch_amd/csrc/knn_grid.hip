@@ -1,5 +1,5 @@
-// Cell-grid k-NN selection (gfx950): fp32 coordinates, coor_dim == 3, optional mask, no adjacency or one given as CSR rows (below: "With
-// CSR rows").  Outputs bit-identical to the
+// Cell-grid k-NN selection (gfx950): fp32 or double coordinates (below: "Double coordinates"; the text before it speaks of fp32),
+// coor_dim == 3, optional mask, no adjacency or one given as CSR rows (below: "With CSR rows").  Outputs bit-identical to the
 // streaming selection (knn_stream.hip) for every input with finite coordinates, at a cost per row that is bounded by the row's
 // neighbourhood instead of N.  Distances are egnn_sqdist and keys egnn_knn_rank / egnn_rank_key (egnn_common.h), like every
 // other selection kernel: equality is by construction.
@@ -46,6 +46,26 @@
 // directly: i at -1, the columns != i at 0, then the lowest indices outside both at 1e5, cut at K -- one thread per entry, a binary search
 // in the first K + 1 columns, whatever the degree.  Flagged rows (masked rows of a flagged graph too) go to the streaming kernel's flagged
 // CSR instantiation.  The instantiation without an adjacency is the code it was: its three CSR arguments are appended and never read.
+//
+// Double coordinates (every kernel is a template on the coordinate type T; egnn_knn_select_grid_f64 / _grid_csr_f64).  The same seven
+// launches on the same workspace layout, with three things wider.  The header's origin, inv_h and h are double, and cells are computed
+// from the double coordinates themselves -- never from a value rounded to float, which could put a node in another cell than the one the
+// stop rule assumes.  The sorted record is (x, y, z, index) in double, 32 bytes per node (egnn_knn_grid_workspace_bytes_f64).  Keys are
+// the 64-bit egnn_rank_key(double), so the composite is the pair (key, index) in 16 bytes, compared key first, then index: as unique per
+// candidate as the packed word, and the candidate buffer, kg_compact, the CSR seeds and tau all compare through kg_less.  Distances are
+// egnn_sqdist_any<double, 4> as knn_stream.hip calls it for double -- for C = 3 fl(fl(fl(dx)^2 + fl(dy)^2) + fl(dz)^2) after additions of
+// +0 that change no bit -- and the outputs are bit-identical to egnn_knn_select_stream_f64 / egnn_knn_select_csr_f64; flagged rows go
+// to that kernel's flagged double instantiations.
+// The stop rule in double.  Cells are c = trunc(fl(fl(x - x0) * inv_h)) clamped to [0, G - 1], G <= 1024, in double arithmetic.  Both
+// roundings are relative (2^-53 each; a denormal difference is exact), so with u = (x - x0) * inv_h exact, |fl - u| <= 2^-52 u <= 2^-42
+// inside the box, and a node in cell c has u in [c - 2^-42, c + 1 + 2^-42); a clamped node lies beyond its border cell, on the far side.
+// After ring r every unvisited node differs from the query's cell by >= r + 1 on some axis, so |u_j - u_q| > r - 2^-41 there and the true
+// squared distance is >= (r h')^2 (1 - 2^-40), h' = 1 / inv_h.  The computed distance has five roundings on non-negative terms, relative
+// error < 2^-50 (h >= 1e-15, set by kg_setup_kernel, keeps (r h)^2 >= 1e-30, far above the denormal range of double as well; extents
+// <= 1e18 -- the same flag condition, kept so that both types hand over the same graphs -- keep every term below 3e36, finite).  The
+// bound fl(fl(r h) fl(r h)), h = fl(1 / inv_h), is off by < 2^-50.  Together < 2^-39, far inside the margin (r h)^2 (1 - 2^-8) that
+// the kernel keeps for both types; the rest of the argument -- strictly below, unvisited keys above the K-th, ties decided among
+// visited nodes -- does not depend on the type.
 #include "egnn_common.h"
 
 namespace {
@@ -59,28 +79,79 @@ constexpr int KG_PARTS = 64;                 // chunks of the bbox pass
 constexpr int KG_PW = 16;                    // doubles per chunk record
 constexpr int KG_CAP = 2 * KG_KMAX;          // candidate buffer entries per wave
 
-struct KgHdr {
+template <typename T> struct KgHdr;
+template <> struct KgHdr<float> {
     float x0, y0, z0, inv_h, h;
     int gx, gy, gz, nvalid, flag;
     int pad[6];
 };
+template <> struct KgHdr<double> {
+    double x0, y0, z0, inv_h, h;
+    int gx, gy, gz, nvalid, flag;
+    int pad[1];
+};
+static_assert(sizeof(KgHdr<float>) == 64 && sizeof(KgHdr<double>) == 64, "one 64-byte header per graph");
+
+// the sorted record (x, y, z, index) and the composite (key, index) per coordinate type.  float: a float4 with the index's bits in w, and
+// one 64-bit word (key << 32 | index); double: 32 and 16 bytes
+struct alignas(16) KgRec64 { double x, y, z; int32_t j; int32_t pad; };
+struct alignas(16) KgComp64 { uint64_t key; uint32_t j; uint32_t pad; };
+template <typename T> struct KgTypes;
+template <> struct KgTypes<float> { typedef float4 rec_t; typedef uint64_t comp_t; };
+template <> struct KgTypes<double> { typedef KgRec64 rec_t; typedef KgComp64 comp_t; };
+
+__device__ __forceinline__ float4 kg_rec(float x, float y, float z, int j) { return make_float4(x, y, z, __int_as_float(j)); }
+__device__ __forceinline__ KgRec64 kg_rec(double x, double y, double z, int j) { return KgRec64{x, y, z, j, 0}; }
+__device__ __forceinline__ int kg_rec_index(const float4& r) { return __float_as_int(r.w); }
+__device__ __forceinline__ int kg_rec_index(const KgRec64& r) { return r.j; }
+__device__ __forceinline__ float kg_rec_sqdist(const float4& a, const float4& b)
+{
+    float dx, dy, dz;
+    return egnn_sqdist(a.x, a.y, a.z, b.x, b.y, b.z, dx, dy, dz);
+}
+__device__ __forceinline__ double kg_rec_sqdist(const KgRec64& a, const KgRec64& b)
+{
+    const double pa[3] = {a.x, a.y, a.z}, pb[3] = {b.x, b.y, b.z};
+    return egnn_sqdist_any<double, 4>(pa, pb, 3);
+}
+
+__device__ __forceinline__ uint64_t kg_comp(float rank, int j) { return ((uint64_t)egnn_rank_key(rank) << 32) | (uint32_t)j; }
+__device__ __forceinline__ KgComp64 kg_comp(double rank, int j) { return KgComp64{egnn_rank_key(rank), (uint32_t)j, 0u}; }
+__device__ __forceinline__ bool kg_less(uint64_t a, uint64_t b) { return a < b; }
+__device__ __forceinline__ bool kg_less(const KgComp64& a, const KgComp64& b) { return a.key < b.key || (a.key == b.key && a.j < b.j); }
+__device__ __forceinline__ int32_t kg_comp_index(uint64_t c) { return (int32_t)(uint32_t)c; }
+__device__ __forceinline__ int32_t kg_comp_index(const KgComp64& c) { return (int32_t)c.j; }
+__device__ __forceinline__ float kg_comp_rank(uint64_t c) { return egnn_rank_from_key((uint32_t)(c >> 32)); }
+__device__ __forceinline__ double kg_comp_rank(const KgComp64& c) { return egnn_rank_from_key(c.key); }
+// above every composite a finite ranking value can form
+template <typename C> __device__ __forceinline__ C kg_comp_top();
+template <> __device__ __forceinline__ uint64_t kg_comp_top<uint64_t>() { return ~0ull; }
+template <> __device__ __forceinline__ KgComp64 kg_comp_top<KgComp64>() { return KgComp64{~0ull, ~0u, 0u}; }
+
+__device__ __forceinline__ float kg_min(float a, float b) { return fminf(a, b); }
+__device__ __forceinline__ double kg_min(double a, double b) { return fmin(a, b); }
+__device__ __forceinline__ float kg_max(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ double kg_max(double a, double b) { return fmax(a, b); }
+__device__ __forceinline__ bool kg_finite(float v) { return fabsf(v) < __builtin_inff(); }
+__device__ __forceinline__ bool kg_finite(double v) { return fabs(v) < __builtin_inf(); }
 
 __host__ __device__ inline int kg_cell_cap(int N) { return N / 4 + 64; }
 
 struct KgLayout { size_t hdr, part, flag, cell, cnt, start, sorted, total; };
 
-inline KgLayout kg_layout(int B, int N)
+// rec: bytes per sorted record (16: float, 32: double); nothing else depends on the coordinate type
+inline KgLayout kg_layout(int B, int N, size_t rec)
 {
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     KgLayout L;
     size_t o = 0;
-    L.hdr = o; o = up(o + (size_t)B * sizeof(KgHdr));
+    L.hdr = o; o = up(o + (size_t)B * sizeof(KgHdr<float>));
     L.part = o; o = up(o + (size_t)B * KG_PARTS * KG_PW * sizeof(double));
     L.flag = o; o = up(o + (size_t)B * N);
     L.cell = o; o = up(o + (size_t)B * N * 4);
     L.cnt = o; o = up(o + (size_t)B * kg_cell_cap(N) * 4);
     L.start = o; o = up(o + (size_t)B * (kg_cell_cap(N) + 1) * 4);
-    L.sorted = o; o = up(o + (size_t)B * N * 16);
+    L.sorted = o; o = up(o + (size_t)B * N * rec);
     L.total = o;
     return L;
 }
@@ -92,32 +163,33 @@ __device__ __forceinline__ void kg_wave_sync()
 }
 
 // ---- bbox: chunk p of graph b -> 16 doubles: sum x y z, sum x^2 y^2 z^2, min x y z, max x y z, valid count, non-finite count
-__global__ __launch_bounds__(KG_THREADS) void kg_bbox_kernel(const float* __restrict__ coors, const uint8_t* __restrict__ mask, int N,
+template <typename T>
+__global__ __launch_bounds__(KG_THREADS) void kg_bbox_kernel(const T* __restrict__ coors, const uint8_t* __restrict__ mask, int N,
                                                              int P, double* __restrict__ part)
 {
     __shared__ double sd[6][KG_THREADS];
-    __shared__ float sf[6][KG_THREADS];
+    __shared__ T sf[6][KG_THREADS];
     __shared__ int si[2][KG_THREADS];
     const int tid = threadIdx.x, b = blockIdx.y, p = blockIdx.x;
     const int chunk = (N + P - 1) / P;
     const int lo = p * chunk, hi = min(N, lo + chunk);
-    const float* cb = coors + (size_t)b * N * 3;
+    const T* cb = coors + (size_t)b * N * 3;
     const uint8_t* mb = mask ? mask + (size_t)b * N : nullptr;
     double s[6] = {0, 0, 0, 0, 0, 0};
-    float mn[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
-    float mx[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+    T mn[3] = {(T)__builtin_inff(), (T)__builtin_inff(), (T)__builtin_inff()};
+    T mx[3] = {(T)-__builtin_inff(), (T)-__builtin_inff(), (T)-__builtin_inff()};
     int cnt = 0, bad = 0;
     for (int i = lo + tid; i < hi; i += KG_THREADS) {
         if (mb && !mb[i]) continue;
         ++cnt;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-            const float v = cb[(size_t)i * 3 + a];
-            if (!(fabsf(v) < __builtin_inff())) { ++bad; continue; }
+            const T v = cb[(size_t)i * 3 + a];
+            if (!kg_finite(v)) { ++bad; continue; }
             s[a] += (double)v;
             s[3 + a] += (double)v * (double)v;
-            mn[a] = fminf(mn[a], v);
-            mx[a] = fmaxf(mx[a], v);
+            mn[a] = kg_min(mn[a], v);
+            mx[a] = kg_max(mx[a], v);
         }
     }
 #pragma unroll
@@ -133,8 +205,8 @@ __global__ __launch_bounds__(KG_THREADS) void kg_bbox_kernel(const float* __rest
             for (int a = 0; a < 6; ++a) sd[a][tid] += sd[a][tid + w];
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
-                sf[a][tid] = fminf(sf[a][tid], sf[a][tid + w]);
-                sf[3 + a][tid] = fmaxf(sf[3 + a][tid], sf[3 + a][tid + w]);
+                sf[a][tid] = kg_min(sf[a][tid], sf[a][tid + w]);
+                sf[3 + a][tid] = kg_max(sf[3 + a][tid], sf[3 + a][tid + w]);
             }
             si[0][tid] += si[0][tid + w];
             si[1][tid] += si[1][tid + w];
@@ -152,7 +224,8 @@ __global__ __launch_bounds__(KG_THREADS) void kg_bbox_kernel(const float* __rest
 }
 
 // ---- setup: the graph's header from its chunk records (thread 0, fixed order), then the cell counters cleared
-__global__ __launch_bounds__(KG_THREADS) void kg_setup_kernel(const double* __restrict__ part, int N, int K, int P, KgHdr* __restrict__ hdr,
+template <typename T>
+__global__ __launch_bounds__(KG_THREADS) void kg_setup_kernel(const double* __restrict__ part, int N, int K, int P, KgHdr<T>* __restrict__ hdr,
                                                               int* __restrict__ cnt)
 {
     __shared__ int ncells;
@@ -168,13 +241,13 @@ __global__ __launch_bounds__(KG_THREADS) void kg_setup_kernel(const double* __re
             n += r[12];
             bad += r[13];
         }
-        KgHdr H;
-        H.x0 = H.y0 = H.z0 = 0.f;
-        H.inv_h = H.h = 1.f;
+        KgHdr<T> H;
+        H.x0 = H.y0 = H.z0 = (T)0;
+        H.inv_h = H.h = (T)1;
         H.gx = H.gy = H.gz = 1;
         H.nvalid = (int)n;
         H.flag = (bad > 0 || n < (double)K || n < 1) ? 1 : 0;
-        for (int a = 0; a < 6; ++a) H.pad[a] = 0;
+        for (int a = 0; a < (int)(sizeof(H.pad) / sizeof(int)); ++a) H.pad[a] = 0;
         if (!H.flag) {
             double lo[3], ext[3], emax = 0;
             for (int a = 0; a < 3; ++a) {
@@ -210,9 +283,9 @@ __global__ __launch_bounds__(KG_THREADS) void kg_setup_kernel(const double* __re
                 h *= 1.2599210498948732;
             }
             if ((double)g[0] * (double)g[1] * (double)g[2] > cap) g[0] = g[1] = g[2] = 1;
-            H.inv_h = (float)(1.0 / h);
-            H.h = (float)(1.0 / (double)H.inv_h);
-            H.x0 = (float)lo[0]; H.y0 = (float)lo[1]; H.z0 = (float)lo[2];
+            H.inv_h = (T)(1.0 / h);
+            H.h = (T)(1.0 / (double)H.inv_h);
+            H.x0 = (T)lo[0]; H.y0 = (T)lo[1]; H.z0 = (T)lo[2];
             H.gx = g[0]; H.gy = g[1]; H.gz = g[2];
         }
         hdr[b] = H;
@@ -223,22 +296,24 @@ __global__ __launch_bounds__(KG_THREADS) void kg_setup_kernel(const double* __re
     for (int c = tid; c < ncells; c += KG_THREADS) cb[c] = 0;
 }
 
-__device__ __forceinline__ int kg_axis_cell(float x, float x0, float inv_h, int g)
+template <typename T>
+__device__ __forceinline__ int kg_axis_cell(T x, T x0, T inv_h, int g)
 {
-    const float t = (x - x0) * inv_h;
-    return t > 0.f ? (int)fminf(t, (float)(g - 1)) : 0;
+    const T t = (x - x0) * inv_h;
+    return t > (T)0 ? (int)kg_min(t, (T)(g - 1)) : 0;
 }
 
 // ---- count: the cell of every valid node (-1: masked), one integer atomic per node
-__global__ __launch_bounds__(KG_THREADS) void kg_count_kernel(const float* __restrict__ coors, const uint8_t* __restrict__ mask, int N,
-                                                              const KgHdr* __restrict__ hdr, int* __restrict__ cell_of, int* __restrict__ cnt)
+template <typename T>
+__global__ __launch_bounds__(KG_THREADS) void kg_count_kernel(const T* __restrict__ coors, const uint8_t* __restrict__ mask, int N,
+                                                              const KgHdr<T>* __restrict__ hdr, int* __restrict__ cell_of, int* __restrict__ cnt)
 {
     const int b = blockIdx.y, i = blockIdx.x * KG_THREADS + threadIdx.x;
-    const KgHdr H = hdr[b];
+    const KgHdr<T> H = hdr[b];
     if (H.flag || i >= N) return;
     int c = -1;
     if (!mask || mask[(size_t)b * N + i]) {
-        const float* p = coors + ((size_t)b * N + i) * 3;
+        const T* p = coors + ((size_t)b * N + i) * 3;
         const int cx = kg_axis_cell(p[0], H.x0, H.inv_h, H.gx), cy = kg_axis_cell(p[1], H.y0, H.inv_h, H.gy),
                   cz = kg_axis_cell(p[2], H.z0, H.inv_h, H.gz);
         c = (cz * H.gy + cy) * H.gx + cx;
@@ -248,7 +323,8 @@ __global__ __launch_bounds__(KG_THREADS) void kg_count_kernel(const float* __res
 }
 
 // ---- scan: cell starts (exclusive prefix sums of the counts), the fullest cell against the fallback limit
-__global__ __launch_bounds__(1024) void kg_scan_kernel(int N, KgHdr* __restrict__ hdr, const int* __restrict__ cnt, int* __restrict__ start)
+template <typename T>
+__global__ __launch_bounds__(1024) void kg_scan_kernel(int N, KgHdr<T>* __restrict__ hdr, const int* __restrict__ cnt, int* __restrict__ start)
 {
     __shared__ int sums[1024];
     __shared__ int smax;
@@ -278,27 +354,30 @@ __global__ __launch_bounds__(1024) void kg_scan_kernel(int N, KgHdr* __restrict_
 }
 
 // ---- place: (x, y, z, index) into the cell's range; the counter of a cell doubles as its cursor (it counts back down to 0)
-__global__ __launch_bounds__(KG_THREADS) void kg_place_kernel(const float* __restrict__ coors, int N, const KgHdr* __restrict__ hdr,
+template <typename T>
+__global__ __launch_bounds__(KG_THREADS) void kg_place_kernel(const T* __restrict__ coors, int N, const KgHdr<T>* __restrict__ hdr,
                                                               const int* __restrict__ cell_of, int* __restrict__ cnt,
-                                                              const int* __restrict__ start, float4* __restrict__ sorted)
+                                                              const int* __restrict__ start,
+                                                              typename KgTypes<T>::rec_t* __restrict__ sorted)
 {
     const int b = blockIdx.y, i = blockIdx.x * KG_THREADS + threadIdx.x;
     if (hdr[b].flag || i >= N) return;
     const int c = cell_of[(size_t)b * N + i];
     if (c < 0) return;
     const int pos = start[(size_t)b * (kg_cell_cap(N) + 1) + c] + atomicSub(&cnt[(size_t)b * kg_cell_cap(N) + c], 1) - 1;
-    const float* p = coors + ((size_t)b * N + i) * 3;
-    if (pos >= 0 && pos < N) sorted[(size_t)b * N + pos] = make_float4(p[0], p[1], p[2], __int_as_float(i));
+    const T* p = coors + ((size_t)b * N + i) * 3;
+    if (pos >= 0 && pos < N) sorted[(size_t)b * N + pos] = kg_rec(p[0], p[1], p[2], i);
 }
 
 // the cnt entries of buf ranked by counting: the min(cnt, K) smallest end up sorted in buf[0 ..), tau = the K-th once there are K
-__device__ __forceinline__ void kg_compact(uint64_t* buf, uint64_t* tmp, int& cnt, uint64_t& tau, int K, int lane)
+template <typename C>
+__device__ __forceinline__ void kg_compact(C* buf, C* tmp, int& cnt, C& tau, int K, int lane)
 {
     kg_wave_sync();
     for (int t = lane; t < cnt; t += 64) {
-        const uint64_t c = buf[t];
+        const C c = buf[t];
         int rnk = 0;
-        for (int u = 0; u < cnt; ++u) rnk += buf[u] < c ? 1 : 0;
+        for (int u = 0; u < cnt; ++u) rnk += kg_less(buf[u], c) ? 1 : 0;
         if (rnk < K) tmp[rnk] = c;
     }
     kg_wave_sync();
@@ -323,20 +402,23 @@ __device__ __forceinline__ bool kg_csr_member(const int32_t* __restrict__ col, i
 
 // CSR: every row has an adjacency, row i of graph b = the columns col[rowptr[b rp_stride + i] .. rowptr[b rp_stride + i + 1]); without
 // it the three last arguments are not read.
-template <bool CSR>
-__global__ __launch_bounds__(KG_THREADS) void kg_search_kernel(const uint8_t* __restrict__ mask, const KgHdr* __restrict__ hdr,
+template <typename T, bool CSR>
+__global__ __launch_bounds__(KG_THREADS) void kg_search_kernel(const uint8_t* __restrict__ mask, const KgHdr<T>* __restrict__ hdr,
                                                                const int* __restrict__ cell_of, const int* __restrict__ start,
-                                                               const float4* __restrict__ sorted, uint8_t* __restrict__ rowflag, int N, int K,
-                                                               int32_t* __restrict__ idx_out, float* __restrict__ rank_out,
+                                                               const typename KgTypes<T>::rec_t* __restrict__ sorted,
+                                                               uint8_t* __restrict__ rowflag, int N, int K,
+                                                               int32_t* __restrict__ idx_out, T* __restrict__ rank_out,
                                                                const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                                int64_t rp_stride)
 {
-    __shared__ uint64_t sbuf[KG_THREADS / 64][KG_CAP];
-    __shared__ uint64_t stmp[KG_THREADS / 64][KG_KMAX];
+    typedef typename KgTypes<T>::rec_t rec_t;
+    typedef typename KgTypes<T>::comp_t comp_t;
+    __shared__ comp_t sbuf[KG_THREADS / 64][KG_CAP];                      // (float: 8 KB + 4 KB; double: 16 KB + 8 KB)
+    __shared__ comp_t stmp[KG_THREADS / 64][KG_KMAX];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b = blockIdx.y, base = blockIdx.x * KG_SLOTS;
-    const KgHdr H = hdr[b];
+    const KgHdr<T> H = hdr[b];
     uint8_t* fb = rowflag + (size_t)b * N;
     if (H.flag) {                                                         // the whole graph goes to the streaming kernel
         if (tid < KG_SLOTS && base + tid < N) fb[base + tid] = 1;
@@ -365,14 +447,14 @@ __global__ __launch_bounds__(KG_THREADS) void kg_search_kernel(const uint8_t* __
                     const bool diag = ip < lim && cr[ip] == i;
                     const int nadj = lim - (diag ? 1 : 0);
                     int j;
-                    float rk;
+                    T rk;
                     if (k == 0) {
                         j = i;
-                        rk = -1.f;
+                        rk = (T)-1;
                     } else if (k - 1 < nadj) {
                         const int t = k - 1;
                         j = cr[(diag && t >= ip) ? t + 1 : t];
-                        rk = 0.f;
+                        rk = (T)0;
                     } else {
                         // the m-th index outside S = {i} u row (sorted, L entries): m + t for the first t with S[t] - t > m
                         const int m = k - 1 - nadj, L = lim + (diag ? 0 : 1);
@@ -384,33 +466,33 @@ __global__ __launch_bounds__(KG_THREADS) void kg_search_kernel(const uint8_t* __
                             else t = mid + 1;
                         }
                         j = m + t;
-                        rk = 1e5f;
+                        rk = (T)1e5;
                     }
                     idx_out[ob + k] = j;
                     rank_out[ob + k] = rk;
                 } else {
                     idx_out[ob + k] = k;
-                    rank_out[ob + k] = 1e5f;
+                    rank_out[ob + k] = (T)1e5;
                 }
                 if (k == 0) fb[i] = 0;
             }
         }
     }
-    uint64_t* buf = sbuf[wave];
-    uint64_t* tmp = stmp[wave];
+    comp_t* buf = sbuf[wave];
+    comp_t* tmp = stmp[wave];
     const int* st = start + (size_t)b * (kg_cell_cap(N) + 1);
-    const float4* srt = sorted + (size_t)b * N;
+    const rec_t* srt = sorted + (size_t)b * N;
     const int cap = K + 64 > 2 * K ? (K + 64 + 63) / 64 * 64 : 2 * K;      // (<= KG_CAP: K <= KG_KMAX)
     const int qend = min(base + KG_SLOTS, H.nvalid);
     for (int q = base + wave; q < qend; q += KG_THREADS / 64) {
-        const float4 me = srt[q];
-        const int i = __builtin_amdgcn_readfirstlane(__float_as_int(me.w));
+        const rec_t me = srt[q];
+        const int i = __builtin_amdgcn_readfirstlane(kg_rec_index(me));
         const int c = __builtin_amdgcn_readfirstlane(cell_of[(size_t)b * N + i]);
         const int cx = c % H.gx, cy = (c / H.gx) % H.gy, cz = c / (H.gx * H.gy);
         const int rmax = max(max(max(cx, H.gx - 1 - cx), max(cy, H.gy - 1 - cy)), max(max(cz, H.gz - 1 - cz), 1));
         int cnt = 0;
         bool dirty = false;
-        uint64_t tau = ~0ull;
+        comp_t tau = kg_comp_top<comp_t>();
         const int32_t* cr = nullptr;
         int clen = 0;
         if constexpr (CSR) {
@@ -420,7 +502,7 @@ __global__ __launch_bounds__(KG_THREADS) void kg_search_kernel(const uint8_t* __
             const int64_t lo = rp[0];
             clen = (int)(rp[1] - lo);
             cr = col + lo;                                                // (not read when clen == 0: col may be NULL)
-            if (lane == 0) buf[0] = ((uint64_t)egnn_rank_key(-1.f) << 32) | (uint32_t)i;
+            if (lane == 0) buf[0] = kg_comp((T)-1, i);
             cnt = 1;
             const int lim = min(clen, K + 1);
             for (int t0 = 0; t0 < lim; t0 += 64) {
@@ -430,7 +512,7 @@ __global__ __launch_bounds__(KG_THREADS) void kg_search_kernel(const uint8_t* __
                 const uint64_t bal = __ballot(pass);
                 if (pass) {
                     const int below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
-                    buf[cnt + below] = ((uint64_t)egnn_rank_key(0.f) << 32) | (uint32_t)j;
+                    buf[cnt + below] = kg_comp((T)0, j);
                 }
                 cnt += __builtin_popcountll(bal);
             }
@@ -475,15 +557,13 @@ __global__ __launch_bounds__(KG_THREADS) void kg_search_kernel(const uint8_t* __
                         if (cnt + 64 > cap) kg_compact(buf, tmp, cnt, tau, K, lane);
                         const int p = p0 + lane;
                         bool pass = false;
-                        uint64_t comp = 0;
+                        comp_t comp = comp_t();
                         if (p < e_t) {
-                            const float4 cj = srt[p];
-                            float dx, dy, dz;
-                            const float d = egnn_sqdist(me.x, me.y, me.z, cj.x, cj.y, cj.z, dx, dy, dz);
-                            const int j = __float_as_int(cj.w);
-                            const uint32_t key = egnn_rank_key(egnn_knn_rank<float>(d, true, true, nullptr, i, j));
-                            comp = ((uint64_t)key << 32) | (uint32_t)j;
-                            pass = comp < tau;
+                            const rec_t cj = srt[p];
+                            const T d = kg_rec_sqdist(me, cj);
+                            const int j = kg_rec_index(cj);
+                            comp = kg_comp(egnn_knn_rank<T>(d, true, true, nullptr, i, j), j);
+                            pass = kg_less(comp, tau);
                             // (CSR: i and its row are seeded; the row is searched only for a candidate that would be kept)
                             if constexpr (CSR) pass = pass && j != i && !kg_csr_member(cr, clen, j);
                         }
@@ -500,23 +580,23 @@ __global__ __launch_bounds__(KG_THREADS) void kg_search_kernel(const uint8_t* __
             }
             if (cnt >= K) {
                 if (dirty) { kg_compact(buf, tmp, cnt, tau, K, lane); dirty = false; }
-                const float d2k = egnn_rank_from_key((uint32_t)(tau >> 32));
-                const float rh = (float)r * H.h;
-                if (d2k < rh * rh * (1.f - 0.00390625f)) break;
+                const T d2k = kg_comp_rank(tau);
+                const T rh = (T)r * H.h;
+                if (d2k < rh * rh * ((T)1 - (T)0.00390625)) break;
             }
             if (r >= rmax) break;
         }
         // (every cell visited or the rule above met; nvalid >= K, so K entries, sorted -- CSR: the seeds and the valid nodes outside
         // them are distinct and no fewer)
         kg_wave_sync();
-        const float d2k = egnn_rank_from_key((uint32_t)(tau >> 32));
-        const bool hand_over = cnt < K || (d2k >= 1e5f && H.nvalid < N);
+        const T d2k = kg_comp_rank(tau);
+        const bool hand_over = cnt < K || (d2k >= (T)1e5 && H.nvalid < N);
         if (!hand_over) {
             const size_t ob = ((size_t)b * N + i) * K;
             for (int t = lane; t < K; t += 64) {
-                const uint64_t cc = buf[t];
-                idx_out[ob + t] = (int32_t)(uint32_t)cc;
-                rank_out[ob + t] = egnn_rank_from_key((uint32_t)(cc >> 32));
+                const comp_t cc = buf[t];
+                idx_out[ob + t] = kg_comp_index(cc);
+                rank_out[ob + t] = kg_comp_rank(cc);
             }
         }
         if (lane == 0) fb[i] = hand_over ? 1 : 0;
@@ -530,53 +610,82 @@ extern "C" size_t egnn_knn_grid_workspace_bytes(int B, int N, int K)
 {
     (void)K;
     if (B <= 0 || N <= 0) return 256;
-    return kg_layout(B, N).total;
+    return kg_layout(B, N, sizeof(KgTypes<float>::rec_t)).total;
 }
 
-// both entries: rowptr == NULL selects without an adjacency
-static int kg_select(const float* coors, const uint8_t* mask, const int64_t* rowptr, const int32_t* col, int64_t rp_stride, int B, int N,
-                     int K, int coor_dim, int32_t* idx_out, float* rank_out, void* workspace, size_t workspace_bytes, void* stream)
+extern "C" size_t egnn_knn_grid_workspace_bytes_f64(int B, int N, int K)
 {
+    (void)K;
+    if (B <= 0 || N <= 0) return 256;
+    return kg_layout(B, N, sizeof(KgTypes<double>::rec_t)).total;
+}
+
+extern "C" size_t egnn_knn_grid_rowflag_offset_f64(int B, int N)
+{
+    if (B <= 0 || N <= 0) return 0;
+    return kg_layout(B, N, sizeof(KgTypes<double>::rec_t)).flag;
+}
+
+static int kg_stream_flagged(const float* coors, const uint8_t* mask, const int64_t* rowptr, const int32_t* col, int64_t rp_stride, int B,
+                             int N, int K, const uint8_t* rowflag, int32_t* idx_out, float* rank_out, void* stream)
+{
+    if (rowptr) return egnn_knn_stream_flagged_csr_f32(coors, mask, rowptr, col, rp_stride, B, N, K, rowflag, idx_out, rank_out, stream);
+    return egnn_knn_stream_flagged_f32(coors, mask, B, N, K, rowflag, idx_out, rank_out, stream);
+}
+static int kg_stream_flagged(const double* coors, const uint8_t* mask, const int64_t* rowptr, const int32_t* col, int64_t rp_stride, int B,
+                             int N, int K, const uint8_t* rowflag, int32_t* idx_out, double* rank_out, void* stream)
+{
+    if (rowptr) return egnn_knn_stream_flagged_csr_f64(coors, mask, rowptr, col, rp_stride, B, N, K, rowflag, idx_out, rank_out, stream);
+    return egnn_knn_stream_flagged_f64(coors, mask, B, N, K, rowflag, idx_out, rank_out, stream);
+}
+
+// every entry: rowptr == NULL selects without an adjacency
+template <typename T>
+static int kg_select(const T* coors, const uint8_t* mask, const int64_t* rowptr, const int32_t* col, int64_t rp_stride, int B, int N,
+                     int K, int coor_dim, int32_t* idx_out, T* rank_out, void* workspace, size_t workspace_bytes, void* stream)
+{
+    typedef typename KgTypes<T>::rec_t rec_t;
     if (!coors || !idx_out || !rank_out || !workspace) return EGNN_E_NULLPTR;
     if (B <= 0 || N <= 0 || K <= 0 || K > N) return EGNN_E_SHAPE;
     if (rowptr && rp_stride != 0 && rp_stride != (int64_t)N + 1) return EGNN_E_SHAPE;
     if (coor_dim != 3 || K > KG_KMAX || B > 65535) return EGNN_E_UNSUPPORTED;
-    const KgLayout L = kg_layout(B, N);
+    const KgLayout L = kg_layout(B, N, sizeof(rec_t));
     if (workspace_bytes < L.total) return EGNN_E_SHAPE;
     if (reinterpret_cast<uintptr_t>(workspace) % 16) return EGNN_E_ALIGN;
     char* ws = static_cast<char*>(workspace);
-    KgHdr* hdr = reinterpret_cast<KgHdr*>(ws + L.hdr);
+    KgHdr<T>* hdr = reinterpret_cast<KgHdr<T>*>(ws + L.hdr);
     double* part = reinterpret_cast<double*>(ws + L.part);
     uint8_t* rowflag = reinterpret_cast<uint8_t*>(ws + L.flag);
     int* cell_of = reinterpret_cast<int*>(ws + L.cell);
     int* cnt = reinterpret_cast<int*>(ws + L.cnt);
     int* start = reinterpret_cast<int*>(ws + L.start);
-    float4* sorted = reinterpret_cast<float4*>(ws + L.sorted);
+    rec_t* sorted = reinterpret_cast<rec_t*>(ws + L.sorted);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int P = min(KG_PARTS, (N + 4095) / 4096);
     const dim3 nodes((unsigned)((N + KG_THREADS - 1) / KG_THREADS), (unsigned)B);
-    hipLaunchKernelGGL(kg_bbox_kernel, dim3((unsigned)P, (unsigned)B), dim3(KG_THREADS), 0, st, coors, mask, N, P, part);
-    hipLaunchKernelGGL(kg_setup_kernel, dim3((unsigned)B), dim3(KG_THREADS), 0, st, part, N, K, P, hdr, cnt);
-    hipLaunchKernelGGL(kg_count_kernel, nodes, dim3(KG_THREADS), 0, st, coors, mask, N, hdr, cell_of, cnt);
-    hipLaunchKernelGGL(kg_scan_kernel, dim3((unsigned)B), dim3(1024), 0, st, N, hdr, cnt, start);
-    hipLaunchKernelGGL(kg_place_kernel, nodes, dim3(KG_THREADS), 0, st, coors, N, hdr, cell_of, cnt, start, sorted);
+    hipLaunchKernelGGL(kg_bbox_kernel<T>, dim3((unsigned)P, (unsigned)B), dim3(KG_THREADS), 0, st, coors, mask, N, P, part);
+    hipLaunchKernelGGL(kg_setup_kernel<T>, dim3((unsigned)B), dim3(KG_THREADS), 0, st, (const double*)part, N, K, P, hdr, cnt);
+    hipLaunchKernelGGL(kg_count_kernel<T>, nodes, dim3(KG_THREADS), 0, st, coors, mask, N, (const KgHdr<T>*)hdr, cell_of, cnt);
+    hipLaunchKernelGGL(kg_scan_kernel<T>, dim3((unsigned)B), dim3(1024), 0, st, N, hdr, (const int*)cnt, start);
+    hipLaunchKernelGGL(kg_place_kernel<T>, nodes, dim3(KG_THREADS), 0, st, coors, N, (const KgHdr<T>*)hdr, (const int*)cell_of, cnt,
+                       (const int*)start, sorted);
     const dim3 slots((unsigned)((N + KG_SLOTS - 1) / KG_SLOTS), (unsigned)B);
     if (rowptr)
-        hipLaunchKernelGGL(kg_search_kernel<true>, slots, dim3(KG_THREADS), 0, st, mask, hdr, cell_of, start, sorted, rowflag, N, K, idx_out,
-                           rank_out, rowptr, col, rp_stride);
+        hipLaunchKernelGGL((kg_search_kernel<T, true>), slots, dim3(KG_THREADS), 0, st, mask, (const KgHdr<T>*)hdr, (const int*)cell_of,
+                           (const int*)start, (const rec_t*)sorted, rowflag, N, K, idx_out, rank_out, rowptr, col, rp_stride);
     else
-        hipLaunchKernelGGL(kg_search_kernel<false>, slots, dim3(KG_THREADS), 0, st, mask, hdr, cell_of, start, sorted, rowflag, N, K, idx_out,
-                           rank_out, (const int64_t*)nullptr, (const int32_t*)nullptr, (int64_t)0);
+        hipLaunchKernelGGL((kg_search_kernel<T, false>), slots, dim3(KG_THREADS), 0, st, mask, (const KgHdr<T>*)hdr, (const int*)cell_of,
+                           (const int*)start, (const rec_t*)sorted, rowflag, N, K, idx_out, rank_out, (const int64_t*)nullptr,
+                           (const int32_t*)nullptr, (int64_t)0);
     int rc = egnn_launch_status();
     if (rc != EGNN_OK) return rc;
-    if (rowptr) return egnn_knn_stream_flagged_csr_f32(coors, mask, rowptr, col, rp_stride, B, N, K, rowflag, idx_out, rank_out, stream);
-    return egnn_knn_stream_flagged_f32(coors, mask, B, N, K, rowflag, idx_out, rank_out, stream);
+    return kg_stream_flagged(coors, mask, rowptr, col, rp_stride, B, N, K, rowflag, idx_out, rank_out, stream);
 }
 
 extern "C" int egnn_knn_select_grid_f32(const float* coors, const uint8_t* mask, int B, int N, int K, int coor_dim, int32_t* idx_out,
                                         float* rank_out, void* workspace, size_t workspace_bytes, void* stream)
 {
-    return kg_select(coors, mask, nullptr, nullptr, 0, B, N, K, coor_dim, idx_out, rank_out, workspace, workspace_bytes, stream);
+    return kg_select<float>(coors, mask, nullptr, nullptr, 0, B, N, K, coor_dim, idx_out, rank_out, workspace, workspace_bytes, stream);
 }
 
 extern "C" int egnn_knn_select_grid_csr_f32(const float* coors, const uint8_t* mask, const int64_t* rowptr, const int32_t* col,
@@ -584,5 +693,21 @@ extern "C" int egnn_knn_select_grid_csr_f32(const float* coors, const uint8_t* m
                                             void* workspace, size_t workspace_bytes, void* stream)
 {
     if (!rowptr) return EGNN_E_NULLPTR;
-    return kg_select(coors, mask, rowptr, col, rowptr_graph_stride, B, N, K, coor_dim, idx_out, rank_out, workspace, workspace_bytes, stream);
+    return kg_select<float>(coors, mask, rowptr, col, rowptr_graph_stride, B, N, K, coor_dim, idx_out, rank_out, workspace, workspace_bytes,
+                            stream);
+}
+
+extern "C" int egnn_knn_select_grid_f64(const double* coors, const uint8_t* mask, int B, int N, int K, int coor_dim, int32_t* idx_out,
+                                        double* rank_out, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return kg_select<double>(coors, mask, nullptr, nullptr, 0, B, N, K, coor_dim, idx_out, rank_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int egnn_knn_select_grid_csr_f64(const double* coors, const uint8_t* mask, const int64_t* rowptr, const int32_t* col,
+                                            int64_t rowptr_graph_stride, int B, int N, int K, int coor_dim, int32_t* idx_out, double* rank_out,
+                                            void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!rowptr) return EGNN_E_NULLPTR;
+    return kg_select<double>(coors, mask, rowptr, col, rowptr_graph_stride, B, N, K, coor_dim, idx_out, rank_out, workspace, workspace_bytes,
+                             stream);
 }

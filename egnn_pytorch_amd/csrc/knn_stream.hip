@@ -32,7 +32,7 @@ template <> struct KsKey<double> { typedef uint64_t type; static constexpr int V
 
 // CDM: 3 = egnn_sqdist (float, C == 3), 8 = egnn_sqdist_n (float, C <= 8), 0 = egnn_sqdist_any (float C > 8, every double C)
 // FL: only the rows with rowflag[b N + i] != 0 are selected and written (the rows the cell-grid selection hands over, knn_grid.hip); a
-// workgroup without such a row returns at once.
+// workgroup without such a row returns at once.  Instantiated for C == 3: <float, 3> and, for the float64 grid, <double, 0>.
 // CSR: the adjacency as sorted column ranges (egnn_knn_select_csr_f32 / _f64) -- adj = rowptr, int64 absolute offsets, (N + 1) per graph
 // at a graph stride of adj_bstride entries (0: one graph's rows for all); col = the flat int32 column array (NULL without CSR).  Every
 // row then has an adjacency; its ranking values come from the merging overload of egnn_knn_rank.
@@ -261,6 +261,9 @@ int knn_stream_launch(const T* coors, const uint8_t* mask, const typename KsAdj<
             if (C != 3) return EGNN_E_UNSUPPORTED;
             kern = knn_select_stream_kernel<T, 3, true, CSR>;
         }
+    } else if (rowflag) {                                                // (double: egnn_sqdist_any at every C; the grid is 3-D)
+        if (C != 3) return EGNN_E_UNSUPPORTED;
+        kern = knn_select_stream_kernel<T, 0, true, CSR>;
     }
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -287,6 +290,21 @@ int egnn_knn_stream_flagged_csr_f32(const float* coors, const uint8_t* mask, con
 {
     if (!rowflag || !rowptr) return EGNN_E_NULLPTR;
     return knn_stream_launch<float, true>(coors, mask, rowptr, rowptr_graph_stride, B, N, K, 3, idx_out, rank_out, stream, rowflag, col);
+}
+
+int egnn_knn_stream_flagged_f64(const double* coors, const uint8_t* mask, int B, int N, int K, const uint8_t* rowflag, int32_t* idx_out,
+                                double* rank_out, void* stream)
+{
+    if (!rowflag) return EGNN_E_NULLPTR;
+    return knn_stream_launch<double>(coors, mask, nullptr, 0, B, N, K, 3, idx_out, rank_out, stream, rowflag);
+}
+
+int egnn_knn_stream_flagged_csr_f64(const double* coors, const uint8_t* mask, const int64_t* rowptr, const int32_t* col,
+                                    int64_t rowptr_graph_stride, int B, int N, int K, const uint8_t* rowflag, int32_t* idx_out,
+                                    double* rank_out, void* stream)
+{
+    if (!rowflag || !rowptr) return EGNN_E_NULLPTR;
+    return knn_stream_launch<double, true>(coors, mask, rowptr, rowptr_graph_stride, B, N, K, 3, idx_out, rank_out, stream, rowflag, col);
 }
 
 extern "C" int egnn_knn_select_stream_f32(const float* coors, const uint8_t* mask, const uint8_t* adj, int64_t adj_batch_stride, int B,

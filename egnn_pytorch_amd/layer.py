@@ -42,10 +42,10 @@ _DENSE_PW = os.environ.get("EGNN_DENSE_PW", "1") != "0"            # dense layer
 # C) instead of a dozen Python-side launches: ~200 us of host time per forward become a few tens.  Only with every scheduling switch
 # above at its default -- the C entry implements the default policy -- and never while per-kernel timing is on.
 _C_FORWARD = os.environ.get("EGNN_C_FORWARD", "1") != "0"
-# k-NN graphs of at least this many nodes select their neighbours on the cell grid (csrc/knn_grid.hip: fp32, 3-D, no adjacency
-# or a SparseAdjacency, K <= 128; the same neighbour list bit for bit) instead of the all-pairs kernels.  The default moves no graph up
-# to 65 536 nodes.  One threshold for both kinds of call: with CSR rows the grid beat the CSR streaming kernel in every case measured at
-# 65 536 nodes, the smallest size measured (DESIGN.md section 4.1 has the measurements).
+# k-NN graphs of at least this many nodes select their neighbours on the cell grid (csrc/knn_grid.hip: fp32 or, in a float64 module,
+# float64; 3-D, no adjacency or a SparseAdjacency, K <= 128; the same neighbour list bit for bit) instead of the all-pairs kernels.  The
+# default moves no graph up to 65 536 nodes.  One threshold for both kinds of call and both dtypes: with CSR rows the grid beat the CSR
+# streaming kernel in every case measured at 65 536 nodes, the smallest size measured (DESIGN.md section 4.1 has the measurements).
 _KNN_GRID_MIN_N = int(os.environ.get("EGNN_KNN_GRID_MIN_N", "65537"))
 
 
@@ -431,8 +431,11 @@ class EGNN(nn.Module):
 
     def _use_grid(self, coors, adj_mat, k):
         """the neighbour selection of this call on the cell grid (egnn_knn_select_grid_f32; with a SparseAdjacency
-        egnn_knn_select_grid_csr_f32) rather than the all-pairs kernels.  A dense adjacency stays there: its byte map is N^2 already."""
-        return (coors.dtype == torch.float32 and coors.shape[-1] == 3 and (adj_mat is None or isinstance(adj_mat, SparseAdjacency))
+        egnn_knn_select_grid_csr_f32) rather than the all-pairs kernels.  A dense adjacency stays there: its byte map is N^2 already.
+        float64 coordinates are a float64 module's (`_forward_exact(dtype=torch.float64)`: egnn_knn_select_grid_f64 / _grid_csr_f64);
+        every other caller has converted to float32 before it asks."""
+        return (coors.dtype in (torch.float32, torch.float64) and coors.shape[-1] == 3
+                and (adj_mat is None or isinstance(adj_mat, SparseAdjacency))
                 and 0 < k <= _ops.KNN_GRID_KMAX and coors.shape[1] >= _KNN_GRID_MIN_N)
 
     def _proj_row_mask(self, mask8, b, n, k, cdim, w, want_u, drop):

@@ -151,6 +151,23 @@ int egnn_knn_select_grid_f32(const float* coors, const uint8_t* mask, int B, int
 int egnn_knn_select_grid_csr_f32(const float* coors, const uint8_t* mask, const int64_t* rowptr, const int32_t* col,
                                  int64_t rowptr_graph_stride, int B, int N, int K, int coor_dim, int32_t* idx_out, float* rank_out,
                                  void* workspace, size_t workspace_bytes, void* stream);
+/* The cell grid for double coordinates (a float64 module on 3-D coordinates: no adjacency, or one given as CSR rows).  The two entries
+ * above with `double` for every `float`: the same seven launches, flags, hand-over, limits and error codes in the same order, outputs
+ * bit-identical to egnn_knn_select_stream_f64 / egnn_knn_select_csr_f64 for every input with finite coordinates.  Cells are computed from
+ * the double coordinates, distances and 64-bit keys are those of the streaming kernel, and a candidate is the pair (key, index), compared
+ * key first; the flagged rows are finished by the streaming kernel in double.  The sorted records are twice as wide, so the workspace has
+ * its own query: egnn_knn_grid_workspace_bytes_f64 (positive, non-decreasing in each argument, >= egnn_knn_grid_workspace_bytes), 256-byte
+ * aligned.  egnn_knn_grid_rowflag_offset_f64: the byte offset inside that workspace of the B*N row flags as they stand after a call
+ * (0: the grid wrote the row itself, 1: it handed the row to the streaming kernel) -- for tests that must tell the two apart; nothing else
+ * reads it.  What keeps the all-pairs selection in either precision: a dense adjacency map, coor_dim != 3, K > 128, and the whole-layer
+ * entries. */
+size_t egnn_knn_grid_workspace_bytes_f64(int B, int N, int K);
+size_t egnn_knn_grid_rowflag_offset_f64(int B, int N);
+int egnn_knn_select_grid_f64(const double* coors, const uint8_t* mask, int B, int N, int K, int coor_dim, int32_t* idx_out,
+                             double* rank_out, void* workspace, size_t workspace_bytes, void* stream);
+int egnn_knn_select_grid_csr_f64(const double* coors, const uint8_t* mask, const int64_t* rowptr, const int32_t* col,
+                                 int64_t rowptr_graph_stride, int B, int N, int K, int coor_dim, int32_t* idx_out, double* rank_out,
+                                 void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Sparse adjacency: the N-degree expansion of EGNN_Network (egnn_pytorch.py:414-427; egnn_adj_expand_u8 is its dense form) on CSR rows
