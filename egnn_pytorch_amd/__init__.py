@@ -10,9 +10,10 @@ from ._ops import phase_timer, check_range
 from ._abi import EGNNHipError, EGNNRangeError
 from .sparse_adj import SparseAdjacency
 from .sparse_edges import SparseEdges
+from .segments import GraphSegments
 from . import sharding
 from .graph import graphed
 
 __all__ = ["EGNN", "EGNN_Network", "CoorsNorm", "phase_timer", "sharding", "graphed", "check_range", "EGNNHipError",
-           "EGNNRangeError", "exact_arithmetic", "SparseAdjacency", "SparseEdges"]
+           "EGNNRangeError", "exact_arithmetic", "SparseAdjacency", "SparseEdges", "GraphSegments"]
 __version__ = "0.1.0"

@@ -197,6 +197,9 @@ SIGNATURES = {name: (restype, argtypes) for names, restype, argtypes in (
      (c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p)),
     ("egnn_knn_select_grid_csr_f32 egnn_knn_select_grid_csr_f64", c_int,
      (c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p)),
+    ("egnn_knn_select_segments_f32 egnn_knn_select_segments_f64", c_int,
+     (c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p)),
+    ("egnn_knn_segments_lds_nodes", c_int, (c_int,)),
     # adjacency: CSR expansion, degrees, dense expansion
     ("egnn_adj_csr_workspace_bytes egnn_adj_expand_workspace_bytes", c_size_t, (c_int, c_int)),
     ("egnn_adj_csr_square_count", c_int,

@@ -15,6 +15,7 @@ from ctypes import byref, c_int64
 import torch
 
 from . import _abi
+from .segments import GraphSegments
 from .sparse_adj import SparseAdjacency, SparseLabels
 
 
@@ -409,6 +410,41 @@ def knn_select_stream(coors, mask, adj_mat, k, out=None):
     """knn_select on the streaming kernel (egnn_knn_select_stream_f32 / _f64) whatever the graph's size: the kernel the two entries
     above take for graphs whose keys do not fit in LDS; the same outputs bit for bit."""
     return _knn_select(coors, mask, adj_mat, k, out, "egnn_knn_select_stream")
+
+
+# `knn_select_segments`: the most nodes a workgroup's LDS window holds (egnn_knn_segments_lds_nodes); None = the kernel's own budget.
+# Segments beyond the window are streamed from memory -- the same result: tests lower it to meet both sources at small sizes.
+KNN_SEGMENTS_LDS_NODES = None
+
+
+def knn_select_segments(coors, segments, k, out=None):
+    """(idx int32 (T,K), rank (T,K) in the coordinates' dtype) of a packed batch -- egnn_knn_select_segments_f32 / _f64
+    (csrc/knn_segments.hip): row i of graph [lo, hi) gets its min(K, hi - lo) nearest nodes of that graph as rows of the packed batch,
+    ascending, ties by ascending index; the slots beyond hold (i, +inf).  coors: (T, C) float32 / float64; segments: a GraphSegments on
+    the same device.  out = (idx, rank): caller-allocated outputs."""
+    if not isinstance(segments, GraphSegments):
+        raise TypeError(f"segments must be a GraphSegments (got {type(segments).__name__})")
+    if coors.dim() != 2 or coors.shape[0] != segments.num_nodes:
+        raise ValueError(f"coors shape {tuple(coors.shape)}: expected ({segments.num_nodes}, C) for these segments")
+    if coors.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"knn_select_segments takes float32 or float64 coordinates (got {coors.dtype})")
+    if segments.device != coors.device:
+        raise RuntimeError(f"Expected all tensors to be on the same device: coors is on {coors.device}, the segments on {segments.device}")
+    t, cdim = coors.shape
+    coors = aligned(coors)
+    if out is not None:
+        idx, rank = out
+    else:
+        idx = empty(t, k, dtype=torch.int32, device=coors.device)
+        rank = empty(t, k, dtype=coors.dtype, device=coors.device)
+    lib = _abi.load()
+    lib.egnn_knn_segments_lds_nodes(int(KNN_SEGMENTS_LDS_NODES or 0))
+    name = "egnn_knn_select_segments" + ("_f64" if coors.dtype == torch.float64 else "_f32")
+    with _timed("knn_select_segments"):
+        rc = getattr(lib, name)(_ptr(coors), _ptr(segments.offsets), _ptr(segments.segment_of), segments.num_graphs, t, k, cdim,
+                                max(segments.max_size, 1), _ptr(idx), _ptr(rank), _stream())
+    _abi.check(rc, name)
+    return idx, rank
 
 
 KNN_GRID_KMAX = 128           # the K limit of egnn_knn_select_grid_f32 / _f64 and _grid_csr_f32 / _f64 (csrc/knn_grid.hip: KG_KMAX)

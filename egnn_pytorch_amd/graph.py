@@ -17,6 +17,7 @@ from __future__ import annotations
 import torch
 
 from . import _ops
+from .segments import GraphSegments
 from .sparse_adj import SparseAdjacency
 from .sparse_edges import SparseEdges
 
@@ -39,6 +40,9 @@ def graphed(module, *example_inputs, warmup: int = 2, range_check: str | None = 
     if any(isinstance(a, SparseEdges) for a in list(example_inputs) + list(example_kwargs.values())):
         raise NotImplementedError("graphed(): a SparseEdges is not supported -- its values would be baked into the graph and could not be "
                                   "replaced between replays; run the module eagerly, or pass dense edges")
+    if any(isinstance(a, GraphSegments) for a in list(example_inputs) + list(example_kwargs.values())):
+        raise NotImplementedError("graphed(): a GraphSegments (packed batch) is not supported -- the graph boundaries would be baked into "
+                                  "the graph, and a ragged batch changes them every step; run the module eagerly")
     args = [a.clone() if torch.is_tensor(a) else a for a in example_inputs]
     kwargs = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in example_kwargs.items()}
     dev = next(a for a in list(args) + list(kwargs.values()) if torch.is_tensor(a)).device

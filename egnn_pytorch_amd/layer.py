@@ -24,6 +24,7 @@ from torch import nn
 
 from . import _abi, _dropout, _ops, _weights, autograd as _autograd
 from .attention import GlobalLinearAttention
+from .segments import GraphSegments
 from .sparse_adj import SparseAdjacency, SparseLabels
 from .sparse_edges import SparseEdges
 
@@ -47,6 +48,36 @@ _C_FORWARD = os.environ.get("EGNN_C_FORWARD", "1") != "0"
 # default moves no graph up to 65 536 nodes.  One threshold for both kinds of call and both dtypes: with CSR rows the grid beat the CSR
 # streaming kernel in every case measured at 65 536 nodes, the smallest size measured (DESIGN.md section 4.1 has the measurements).
 _KNN_GRID_MIN_N = int(os.environ.get("EGNN_KNN_GRID_MIN_N", "65537"))
+
+
+# A packed batch (`mask=GraphSegments`) is one graph of T nodes to the kernels, so the single-graph limits would apply to T: the fused
+# kernels' 32-bit offsets (`EGNN._fused_covers`) and, under autograd, the fused backward's (autograd.FusedBackwardLimit).  Graphs are
+# independent: a packed call beyond the limit is cut at graph boundaries into several calls.  None: the limit of each call from those
+# rules (`EGNN._packed_node_limit`); an int: that many nodes (tests lower it).
+_PACKED_MAX_NODES = None
+# the GraphSegments of the packed call in flight (per thread / context, like `_exact_now`): the neighbour selection of the layer's
+# launch sequence takes the segmented kernel while it is set
+_segments_now = contextvars.ContextVar("egnn_segments_now", default=None)
+
+
+def _packed_pieces(segments, limit, k):
+    """[(row slice, GraphSegments)] of a packed batch beyond `limit` nodes: `segments.split` pieces, cut at graph boundaries.  A piece
+    of fewer than K rows (the selection needs K <= T, as every call does) joins a neighbour: the split leaves K - 1 rows of room for
+    that, so a piece passes the limit only where such a piece has no neighbour but graphs that leave no such room on their own."""
+    room = limit - (k - 1) if limit >= 2 * k else limit
+    pieces = list(segments.split(max(room, 1)))
+    i = 0
+    while len(pieces) > 1 and i < len(pieces):
+        if pieces[i][1].num_nodes >= k:
+            i += 1
+            continue
+        fits = [j for j in (i - 1, i + 1) if 0 <= j < len(pieces) and pieces[j][1].num_nodes + pieces[i][1].num_nodes <= limit]
+        j = fits[0] if fits else (i - 1 if i > 0 else i + 1)
+        lo, hi = min(i, j), max(i, j)
+        merged = GraphSegments.from_sizes(pieces[lo][1].sizes + pieces[hi][1].sizes, device=segments.device)
+        pieces[lo:hi + 1] = [(slice(pieces[lo][0].start, pieces[hi][0].stop), merged)]
+        i = lo
+    return pieces
 
 
 def _default_policy():
@@ -303,6 +334,8 @@ class EGNN(nn.Module):
     def _call(self, feats, coors, edges, mask, adj_mat, order_hint):
         """(node_out, coors_out, order): inference under no_grad, or -- when a graph has to be recorded -- through
         autograd.EGNNFunction (HIP forward, recompute-in-backward)."""
+        if isinstance(mask, GraphSegments):                         # a packed batch: feats (T, dim), coors (T, C)
+            return self._call_packed(feats, coors, edges, mask, adj_mat, order_hint)
         if _ops.RANGE_CHECK == "deferred" and feats.is_cuda:
             _ops.check_range(feats.device, wait=False)              # an earlier call's status, if it has arrived
         if isinstance(edges, EdgeLookup):
@@ -318,6 +351,68 @@ class EGNN(nn.Module):
             with torch.no_grad():
                 node_out, coors_out, order = self._forward_with_hint(feats, coors, edges, mask, adj_mat, order_hint)[:3]
         return node_out, coors_out, order
+
+    # ------------------------------------------------------------------ packed batches
+    def _check_packed(self, feats, coors, edges, segments, adj_mat):
+        """the refusals and shape checks of a packed call, before any launch"""
+        if adj_mat is not None:
+            raise NotImplementedError("a packed batch (mask=GraphSegments) with adj_mat is not supported: the adjacency ranking of the "
+                                      "segmented selection is a follow-up (DESIGN.md section 9); pad the batch, or drop adj_mat")
+        if edges is not None:
+            raise NotImplementedError("a packed batch (mask=GraphSegments) with edges is not supported: per-pair edge features of a "
+                                      "packed batch are a follow-up (DESIGN.md section 9); pad the batch, or drop edges")
+        if self.num_nearest_neighbors <= 0:
+            raise NotImplementedError("a packed batch (mask=GraphSegments) on a dense layer (num_nearest_neighbors = 0) is not supported: "
+                                      "all pairs of a ragged batch have no fixed K (DESIGN.md section 9); set num_nearest_neighbors")
+        if feats.dim() != 2 or coors.dim() != 2 or feats.shape[0] != coors.shape[0]:
+            raise ValueError(f"feats {tuple(feats.shape)} / coors {tuple(coors.shape)}: a packed batch takes (T,dim) and (T,C)")
+        if feats.shape[0] != segments.num_nodes:
+            raise ValueError(f"feats holds {feats.shape[0]} rows, the segments {segments.num_nodes} nodes")
+        if segments.device != feats.device:
+            raise RuntimeError(f"Expected all tensors to be on the same device: feats is on {feats.device}, the segments on "
+                               f"{segments.device}")
+
+    def _packed_node_limit(self, k, training):
+        """the most nodes one call of a packed batch may hold (`_PACKED_MAX_NODES`): what `_fused_covers` admits for one graph whatever K
+        is and, under autograd, what the fused backward does; the plain kernels (float64 modules, the wide-range path) address with 64 bits"""
+        if _PACKED_MAX_NODES is not None:
+            return int(_PACKED_MAX_NODES)
+        if self.float64_kernels() or exact_active():
+            return 2 ** 31 - 1
+        h = 2 * (2 * self.fourier_features + 2 * self.dim + self.edge_dim + 1)
+        limit = 0x80000000 // ((h + 32) * 8)
+        if training:
+            limit = min(limit, _autograd._fused_largest_graph(k, _abi.load().egnn_padded_hidden(h)))
+        return limit
+
+    def _call_packed(self, feats, coors, edges, segments, adj_mat, order_hint):
+        """`_call` for feats (T, dim), coors (T, C) and a GraphSegments: one call with B = 1, N = T whose neighbour lists stay inside
+        the segments -- or, beyond `_packed_node_limit`, one call per `_packed_pieces` piece, concatenated (under autograd each piece
+        records its own EGNNFunction)."""
+        self._check_packed(feats, coors, edges, segments, adj_mat)
+        t, k = segments.num_nodes, self.num_nearest_neighbors
+        if k > t:
+            raise RuntimeError("selected index k out of range")      # torch.topk's error upstream: K against T (a graph below K is legal)
+        limit = self._packed_node_limit(k, _autograd.wants_grad(self, feats, coors))
+        if segments.num_graphs > 1 and t > limit:
+            outs = [self._call_packed_one(feats[sl], coors[sl], piece, None) for sl, piece in _packed_pieces(segments, limit, k)]
+            return torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs]), None
+        return self._call_packed_one(feats, coors, segments, order_hint)
+
+    def _call_packed_one(self, feats, coors, segments, order_hint):
+        # The edge kernels and the backward consult a slot's validity only when a node mask is present, and the empty slots of a graph
+        # below K are told by it (rank = +inf > the radius): the call carries an all-true mask.
+        mask = torch.ones(1, feats.shape[0], dtype=torch.bool, device=feats.device)
+        if sum(1 for n in segments.sizes if n) == 1:
+            # one graph: the ordinary one-graph call, on today's selection (the cell grid beyond 65 536 nodes included)
+            node_out, coors_out, order = self._call(feats[None], coors[None], None, mask, None, order_hint)
+        else:
+            tok = _segments_now.set(segments)
+            try:
+                node_out, coors_out, order = self._call(feats[None], coors[None], None, mask, None, order_hint)
+            finally:
+                _segments_now.reset(tok)
+        return node_out[0], coors_out[0], order
 
     def _forward_hip_checked(self, feats, coors, edges, mask, adj_mat, order_hint, want_u=False, drop_seed=None):
         """(node_out, coors_out, order, idx, rank, valid_radius, u, proj) -- what autograd.EGNNFunction.forward needs; u = the
@@ -350,14 +445,15 @@ class EGNN(nn.Module):
                     drop_seed = _dropout.draw_seed()
                 out = self._forward_exact(feats.double(), coors.double(),
                                           edges if (edges is None or isinstance(edges, EdgeLookup)) else edges.double(), mask, adj_mat,
-                                          self._neighbour_count(n, adj_mat),
+                                          self._neighbour_count(n, adj_mat, torch.float64),
                                           dtype=torch.float64, want_u=want_u,
                                           drop=(self.dropout_p, drop_seed) if self.dropout_active() else None)
             if f_dtype != torch.float64 or c_dtype != torch.float64:
                 out = (out[0].to(f_dtype), out[1].to(c_dtype)) + tuple(out[2:])
             return out
         if (_C_FORWARD and _default_policy() and not want_u and not selection and drop_seed is None and f_dtype == torch.float32
-                and c_dtype == torch.float32 and _ops._timer is None and not self.dropout_active() and not exact_active()):
+                and c_dtype == torch.float32 and _ops._timer is None and not self.dropout_active() and not exact_active()
+                and _segments_now.get() is None):                 # (a packed batch: the C entry selects inside the library)
             out = self._forward_c(feats, coors, edges, mask, adj_mat, order_hint)
             if out is not None:
                 return out
@@ -387,12 +483,16 @@ class EGNN(nn.Module):
         """the k-NN path (a neighbour list of K per node) rather than the dense all-pairs one"""
         return self.num_nearest_neighbors > 0 or self.only_sparse_neighbors
 
-    def _neighbour_count(self, n, adj_mat):
+    def _neighbour_count(self, n, adj_mat, dtype=torch.float32):
         """(K, valid_radius) of a call on N-node graphs (egnn_pytorch.py:240-252): N on the dense path; on the k-NN path the module's
-        K -- or, for only_sparse_neighbors with an adjacency, its maximum degree and radius 0."""
+        K -- or, for only_sparse_neighbors with an adjacency, its maximum degree and radius 0.  A packed call (`_segments_now`) caps the
+        radius at the largest finite value of `dtype`, the dtype of its ranks: the empty slots of a graph below K rank at +inf and must
+        fail `rank <= valid_radius` in the forward and in what the backward saves."""
         if not self._use_nearest():
             return n, self.valid_radius
         k, valid_radius = self.num_nearest_neighbors, self.valid_radius
+        if _segments_now.get() is not None:
+            valid_radius = min(valid_radius, torch.finfo(dtype).max)
         if adj_mat is not None and self.only_sparse_neighbors:
             with torch.cuda.device(adj_mat.device):
                 k, valid_radius = _ops.adj_max_degree(adj_mat), 0.0   # host sync, as upstream (:249)
@@ -434,7 +534,7 @@ class EGNN(nn.Module):
         egnn_knn_select_grid_csr_f32) rather than the all-pairs kernels.  A dense adjacency stays there: its byte map is N^2 already.
         float64 coordinates are a float64 module's (`_forward_exact(dtype=torch.float64)`: egnn_knn_select_grid_f64 / _grid_csr_f64);
         every other caller has converted to float32 before it asks."""
-        return (coors.dtype in (torch.float32, torch.float64) and coors.shape[-1] == 3
+        return (_segments_now.get() is None and coors.dtype in (torch.float32, torch.float64) and coors.shape[-1] == 3
                 and (adj_mat is None or isinstance(adj_mat, SparseAdjacency))
                 and 0 < k <= _ops.KNN_GRID_KMAX and coors.shape[1] >= _KNN_GRID_MIN_N)
 
@@ -471,9 +571,14 @@ class EGNN(nn.Module):
         idx_o, rank_o, order_o, slots_o, grid_ws = outs
         mask8 = _ops._u8(mask)                                      # (a view: the caller made the mask contiguous before the fork)
 
+        segments = _segments_now.get()                              # (read here: `select` may run under another stream's context)
+
         def select():
             # (the Morton order launched AHEAD of the selection was measured in round 6: +- 0.3 %, not kept)
-            if grid_ws is not None:
+            if segments is not None:                                # a packed batch (B = 1): neighbours inside the node's own graph
+                _ops.knn_select_segments(coors[0], segments, k, out=(idx_o[0], rank_o[0]))
+                idx_, rank_ = idx_o, rank_o
+            elif grid_ws is not None:
                 idx_, rank_ = _ops.knn_select_grid(coors, mask, k, out=(idx_o, rank_o), ws=grid_ws, adj=adj_mat)
             else:
                 idx_, rank_ = _ops.knn_select(coors, mask, adj_mat, k, out=(idx_o, rank_o))
@@ -734,7 +839,9 @@ class EGNN(nn.Module):
         k, valid_radius = kr
         idx = rank = None
         if self._use_nearest() and k > 0:
-            if self._use_grid(coors, adj_mat, k):                        # (the same list bit for bit, sub-quadratic: `_KNN_GRID_MIN_N`)
+            if _segments_now.get() is not None:                          # a packed batch (B = 1): neighbours inside the node's own graph
+                idx, rank = (t[None] for t in _ops.knn_select_segments(coors[0], _segments_now.get(), k))
+            elif self._use_grid(coors, adj_mat, k):                      # (the same list bit for bit, sub-quadratic: `_KNN_GRID_MIN_N`)
                 idx, rank = _ops.knn_select_grid(coors, mask, k, adj=adj_mat)
             else:
                 idx, rank = _ops.knn_select(coors, mask, adj_mat, k)
@@ -891,7 +998,45 @@ class EGNN_Network(nn.Module):
                 out = self._forward(feats, coors, adj_mat, edges, mask, return_coor_changes)
         return out
 
+    def _forward_packed(self, feats, coors, adj_mat, edges, segments, return_coor_changes, early=None):
+        """`_forward` for a packed batch: tokens (T,) or features (T, dim), coors (T, C), a GraphSegments where the mask goes; the
+        position embedding is indexed by each node's index inside its own graph."""
+        if self.global_tokens is not None:
+            raise NotImplementedError("a packed batch (mask=GraphSegments) with global_linear_attn_every > 0 is not supported: attention "
+                                      "segmented by graph is a kernel of its own (DESIGN.md section 9); pad the batch")
+        if self.num_adj_degrees is not None:
+            raise NotImplementedError("a packed batch (mask=GraphSegments) with num_adj_degrees is not supported: the adjacency of a "
+                                      "packed batch is a follow-up (DESIGN.md section 9); pad the batch")
+        if edges is not None or self.has_edges:
+            raise NotImplementedError("a packed batch (mask=GraphSegments) with edges is not supported: per-pair edge features of a "
+                                      "packed batch are a follow-up (DESIGN.md section 9); pad the batch")
+        if adj_mat is not None:
+            raise NotImplementedError("a packed batch (mask=GraphSegments) with adj_mat is not supported: the adjacency ranking of the "
+                                      "segmented selection is a follow-up (DESIGN.md section 9); pad the batch, or drop adj_mat")
+        if feats.dim() != (1 if self.token_emb is not None else 2) or feats.shape[0] != segments.num_nodes:
+            raise ValueError(f"feats shape {tuple(feats.shape)}: a packed batch of {segments.num_nodes} nodes takes "
+                             f"{'tokens (T,)' if self.token_emb is not None else 'features (T,dim)'}")
+        if self.token_emb is not None:
+            feats = self.token_emb(feats)
+        if self.pos_emb is not None:
+            n = segments.max_size
+            assert n <= self.num_positions, \
+                f"given sequence length {n} must be less than the number of positions {self.num_positions} set at init"
+            feats = feats + self.pos_emb(segments.positions)
+        coor_changes = [coors]
+        order = None
+        for ind, (_, egnn) in enumerate(self.layers):
+            if early is not None:
+                early.last = ind == len(self.layers) - 1
+            feats, coors, order = egnn._call(feats, coors, None, segments, None, order)
+            coor_changes.append(coors)
+        if return_coor_changes:
+            return feats, coors, coor_changes
+        return feats, coors
+
     def _forward(self, feats, coors, adj_mat, edges, mask, return_coor_changes, early=None):
+        if isinstance(mask, GraphSegments):
+            return self._forward_packed(feats, coors, adj_mat, edges, mask, return_coor_changes, early)
         b = feats.shape[0]
         if self.token_emb is not None:
             feats = self.token_emb(feats)

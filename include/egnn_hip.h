@@ -169,6 +169,25 @@ int egnn_knn_select_grid_csr_f64(const double* coors, const uint8_t* mask, const
                                  int64_t rowptr_graph_stride, int B, int N, int K, int coor_dim, int32_t* idx_out, double* rank_out,
                                  void* workspace, size_t workspace_bytes, void* stream);
 
+/* Segmented selection (csrc/knn_segments.hip): a PACKED batch -- the nodes of G graphs concatenated as coors (T, coor_dim), graph g
+ * owning the rows [offsets[g], offsets[g + 1]); offsets: int64 (G + 1) on the device, offsets[0] = 0, offsets[G] = T, non-decreasing
+ * (empty graphs allowed); segment_of: int32 (T), the graph of every row; max_segment: the largest graph, known to the host (it sizes the
+ * LDS window only: a wrong value costs time, never the result).  No mask, no adjacency.  Row i of segment [lo, hi) receives the
+ * min(K, hi - lo) candidates j in [lo, hi) with the smallest squared distance (itself included), ascending, ties by ascending index --
+ * the values and the policy of egnn_knn_select_f32 / _f64 on that graph alone.  idx_out (T, K) holds rows of the packed batch
+ * (lo + local index); slots k >= hi - lo are empty: idx = i, rank = +inf.  One launch on `stream`, deterministic.  The entries trust
+ * offsets / segment_of (egnn_pytorch_amd.GraphSegments validates them); out-of-range entries are clamped into the arrays.
+ * Errors, all returned before any launch: EGNN_E_NULLPTR (any pointer), EGNN_E_SHAPE (non-positive G, T, K or max_segment,
+ * max_segment > T), EGNN_E_K_GT_N (K > T), EGNN_E_UNSUPPORTED (coor_dim outside 1..64, K > 1024).
+ * egnn_knn_segments_lds_nodes: the most nodes a workgroup's LDS window may hold -- limit > 0 sets it, 0 restores the built-in budget
+ * (what 64 KiB leave), limit < 0 changes nothing; returns the setting before the call.  Segments beyond the window are streamed from
+ * memory: the same result.  Process-wide and not synchronised: for tests that want both sources at small sizes. */
+int egnn_knn_select_segments_f32(const float* coors, const int64_t* offsets, const int32_t* segment_of, int G, int T, int K, int coor_dim,
+                                 int max_segment, int32_t* idx_out, float* rank_out, void* stream);
+int egnn_knn_select_segments_f64(const double* coors, const int64_t* offsets, const int32_t* segment_of, int G, int T, int K, int coor_dim,
+                                 int max_segment, int32_t* idx_out, double* rank_out, void* stream);
+int egnn_knn_segments_lds_nodes(int limit);
+
 /* ---------------------------------------------------------------------------------------------
  * Sparse adjacency: the N-degree expansion of EGNN_Network (egnn_pytorch.py:414-427; egnn_adj_expand_u8 is its dense form) on CSR rows
  * (csrc/adj_csr.hip).  Row pointers are int64 (G, N + 1) ABSOLUTE offsets into a flat int32 column array, columns strictly ascending

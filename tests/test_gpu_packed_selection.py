@@ -1,0 +1,157 @@
+"""The segmented selection (csrc/knn_segments.hip, `_ops.knn_select_segments`) against the all-pairs selection on the padded batch.
+
+Yardstick: `_ops.knn_select` on the (G, N_max, C) padded batch with the prefix mask, which the existing tests pin bit for bit to the
+reference.  For every real node i of graph g (rows [lo, lo + n) of the packed batch):
+    slots k <  min(K, n):  idx_packed - lo == idx_padded, and the rank bits are equal;
+    slots k >= min(K, n):  idx == i, rank == +inf.
+The padded call ranks its padding at 1e5, so it is the per-graph selection only while every squared distance stays below that: asserted
+of the inputs.
+
+One batch holds the sizes 0, 1, 2, K - 1, K, K + 1, 63, 64, 65, 257 and 128 / 129.  Every comparison runs twice: on the kernel's own LDS
+budget (every segment of these sizes is read from the workgroup's LDS window) and with the window lowered to 128 nodes
+(`_ops.KNN_SEGMENTS_LDS_NODES`), where 128 is the largest segment that fits and 129 the smallest that is streamed from memory."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+KS = (1, 8, 32, 48, 64, 65, 128)
+SWITCH = 128
+INF_BITS = {torch.float32: 0x7F800000, torch.float64: 0x7FF0000000000000}
+
+
+def _sizes(k):
+    return (0, 1, 2, k - 1, k, k + 1, 63, 64, 65, 257, SWITCH, SWITCH + 1)
+
+
+def _bits(t):
+    return t.view(torch.int32 if t.dtype == torch.float32 else torch.int64)
+
+
+@functools.lru_cache(maxsize=None)
+def _batch(sizes, cdim, dtype, geometry, seed=0):
+    """(segments, packed coors (T, C), padded coors (G, N_max, C), prefix mask) on the device"""
+    from egnn_pytorch_amd import GraphSegments
+    seg = GraphSegments.from_sizes(sizes, device="cuda")
+    g = torch.Generator().manual_seed(seed)
+    t = seg.num_nodes
+    if geometry == "random":
+        x = torch.randn(t, cdim, generator=g) * 3.0
+    elif geometry == "lattice":                          # ties inside a row and across the K boundary
+        x = torch.randint(0, 4, (t, cdim), generator=g).float()
+    else:                                                # "identical": the segment of 65 nodes is one point, the rest a coarse lattice
+        x = torch.randint(0, 3, (t, cdim), generator=g).float()
+        at = sizes.index(65)
+        x[seg.host_offsets[at]:seg.host_offsets[at + 1]] = 1.5
+    x = x.to(dtype).cuda()
+    span = x.max(0).values - x.min(0).values             # every squared distance is below the rank of a padded candidate
+    assert float((span.double() ** 2).sum()) < 1e5
+    return seg, x, seg.unpack(x), seg.prefix_mask()
+
+
+@functools.lru_cache(maxsize=None)
+def _padded(sizes, cdim, dtype, geometry, k):
+    from egnn_pytorch_amd import _ops
+    _, _, xp, mask = _batch(sizes, cdim, dtype, geometry)
+    idx, rank = _ops.knn_select(xp, mask, None, k)
+    torch.cuda.synchronize()
+    return idx, rank
+
+
+def _packed(seg, x, k, lds_nodes=None):
+    from egnn_pytorch_amd import _ops
+    saved = _ops.KNN_SEGMENTS_LDS_NODES
+    _ops.KNN_SEGMENTS_LDS_NODES = lds_nodes
+    try:
+        idx, rank = _ops.knn_select_segments(x, seg, k)
+        torch.cuda.synchronize()
+    finally:
+        _ops.KNN_SEGMENTS_LDS_NODES = saved
+    return idx, rank
+
+
+def _check(seg, k, idx, rank, pidx, prank, what):
+    assert idx.shape == rank.shape == (seg.num_nodes, k) and idx.dtype == torch.int32
+    off = seg.host_offsets
+    for g, n in enumerate(seg.sizes):
+        if n == 0:
+            continue
+        lo, m = off[g], min(k, n)
+        assert torch.equal(idx[lo:lo + n, :m] - lo, pidx[g, :n, :m]), (what, "graph", g, "size", n, "indices")
+        assert torch.equal(_bits(rank[lo:lo + n, :m]), _bits(prank[g, :n, :m])), (what, "graph", g, "size", n, "rank bits")
+        rows = torch.arange(lo, lo + n, device=idx.device, dtype=torch.int32)[:, None].expand(n, k - m)
+        assert torch.equal(idx[lo:lo + n, m:], rows), (what, "graph", g, "size", n, "empty slots' indices")
+        assert bool((_bits(rank[lo:lo + n, m:]) == INF_BITS[rank.dtype]).all()), (what, "graph", g, "size", n, "empty slots' ranks")
+
+
+def _compare(cdim, dtype, geometry, k):
+    sizes = _sizes(k)
+    seg, x, _, _ = _batch(sizes, cdim, dtype, geometry)
+    assert k <= seg.num_nodes
+    pidx, prank = _padded(sizes, cdim, dtype, geometry, k)
+    for lds_nodes in (None, SWITCH):
+        idx, rank = _packed(seg, x, k, lds_nodes)
+        _check(seg, k, idx, rank, pidx, prank, (geometry, cdim, dtype, k, lds_nodes))
+
+
+@pytest.mark.parametrize("k", KS)
+@pytest.mark.parametrize("dtype,cdim", [(torch.float32, 3), (torch.float32, 2), (torch.float32, 5), (torch.float32, 9),
+                                        (torch.float64, 3), (torch.float64, 9)],
+                         ids=["f32_c3", "f32_c2", "f32_c5", "f32_c9", "f64_c3", "f64_c9"])
+def test_random_coordinates_match_the_padded_selection(dtype, cdim, k):
+    _compare(cdim, dtype, "random", k)
+
+
+@pytest.mark.parametrize("geometry", ["lattice", "identical"])
+@pytest.mark.parametrize("k", (8, 65))
+@pytest.mark.parametrize("dtype,cdim", [(torch.float32, 3), (torch.float32, 5), (torch.float32, 9), (torch.float64, 3)],
+                         ids=["f32_c3", "f32_c5", "f32_c9", "f64_c3"])
+def test_tied_coordinates_match_the_padded_selection(dtype, cdim, k, geometry):
+    _compare(cdim, dtype, geometry, k)
+
+
+@pytest.mark.parametrize("lds_nodes", (None, SWITCH))
+@pytest.mark.parametrize("geometry", ["random", "lattice"])
+def test_graphs_in_reversed_order_give_the_same_lists(geometry, lds_nodes):
+    """the same graphs packed in the opposite order: every list is the same, re-based to the graph's new first row"""
+    from egnn_pytorch_amd import GraphSegments
+    k = 32
+    sizes = _sizes(k)
+    seg, x, _, _ = _batch(sizes, 3, torch.float32, geometry)
+    off = seg.host_offsets
+    parts = [x[off[g]:off[g + 1]] for g in range(len(sizes))]
+    rseg = GraphSegments.from_sizes(tuple(reversed(sizes)), device="cuda")
+    idx, rank = _packed(seg, x, k, lds_nodes)
+    ridx, rrank = _packed(rseg, torch.cat(parts[::-1]), k, lds_nodes)
+    roff = rseg.host_offsets
+    for g, n in enumerate(sizes):
+        lo, rlo = off[g], roff[len(sizes) - 1 - g]
+        assert torch.equal(idx[lo:lo + n] - lo, ridx[rlo:rlo + n] - rlo), (g, n)
+        assert torch.equal(_bits(rank[lo:lo + n]), _bits(rrank[rlo:rlo + n])), (g, n)
+
+
+@pytest.mark.parametrize("lds_nodes", (None, SWITCH))
+def test_two_runs_give_equal_bits(lds_nodes):
+    k = 48
+    seg, x, _, _ = _batch(_sizes(k), 3, torch.float32, "lattice")
+    a = _packed(seg, x, k, lds_nodes)
+    b = _packed(seg, x, k, lds_nodes)
+    assert torch.equal(a[0], b[0]) and torch.equal(_bits(a[1]), _bits(b[1]))
+
+
+def test_wrapper_refuses_what_the_kernel_does_not_take():
+    from egnn_pytorch_amd import GraphSegments, _ops
+    seg = GraphSegments.from_sizes((3, 4), device="cuda")
+    x = torch.zeros(7, 3, device="cuda")
+    with pytest.raises(RuntimeError, match="selected index k out of range"):
+        _ops.knn_select_segments(x, seg, 8)                                   # K > T, as torch.topk upstream
+    with pytest.raises(ValueError, match="expected \\(7, C\\)"):
+        _ops.knn_select_segments(x[:6], seg, 2)
+    with pytest.raises(TypeError, match="float32 or float64"):
+        _ops.knn_select_segments(x.half(), seg, 2)
+    with pytest.raises(RuntimeError, match="same device"):
+        _ops.knn_select_segments(x, GraphSegments.from_sizes((3, 4)), 2)
+    assert np.array_equal(_ops.knn_select_segments(x, seg, 2)[0].cpu().numpy()[:, 0], np.array([0, 0, 0, 3, 3, 3, 3]))
