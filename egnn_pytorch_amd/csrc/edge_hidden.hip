@@ -291,7 +291,9 @@ int edge_hidden_launch(const egnn_edge_hidden_args* args, int which, void* strea
     if (which == EH_FWD) {
         if (m <= 16) return run(edge_hidden_fwd_kernel<T, 16>);
         if (m <= 32) return run(edge_hidden_fwd_kernel<T, 32>);
-        if (m <= 64 && !f64) return run(edge_hidden_fwd_kernel<T, 64>);
+        if constexpr (!f64) {                                            // (constexpr: the double kernel is not even instantiated)
+            if (m <= 64) return run(edge_hidden_fwd_kernel<T, 64>);
+        }
         return run(edge_hidden_fwd_kernel<T, 0>);
     }
     if (which == EH_BWD) {
@@ -302,7 +304,9 @@ int edge_hidden_launch(const egnn_edge_hidden_args* args, int which, void* strea
     }
     // (two register arrays of m_dim values: up to 32 channels (16 in float64) in registers, wider heads through their output row)
     if (m <= 16) return run(edge_hidden_bwd2_kernel<T, 16>);
-    if (m <= 32 && !f64) return run(edge_hidden_bwd2_kernel<T, 32>);
+    if constexpr (!f64) {
+        if (m <= 32) return run(edge_hidden_bwd2_kernel<T, 32>);
+    }
     return run(edge_hidden_bwd2_kernel<T, 0>);
 }
 

@@ -9,7 +9,11 @@ of the inputs.
 
 One batch holds the sizes 0, 1, 2, K - 1, K, K + 1, 63, 64, 65, 257 and 128 / 129.  Every comparison runs twice: on the kernel's own LDS
 budget (every segment of these sizes is read from the workgroup's LDS window) and with the window lowered to 128 nodes
-(`_ops.KNN_SEGMENTS_LDS_NODES`), where 128 is the largest segment that fits and 129 the smallest that is streamed from memory."""
+(`_ops.KNN_SEGMENTS_LDS_NODES`), where 128 is the largest segment that fits and 129 the smallest that is streamed from memory.
+
+A second batch holds two coincident segments of 200 and 300 nodes: every key of a row is equal, so with K <= 64 more candidates survive
+the pruning bound than its list of 128 holds and the row falls back to the radix passes, which then have to resolve the K-th candidate
+on the index digits alone -- one digit for 200 nodes, two for 300."""
 import functools
 
 import numpy as np
@@ -42,6 +46,8 @@ def _batch(sizes, cdim, dtype, geometry, seed=0):
         x = torch.randn(t, cdim, generator=g) * 3.0
     elif geometry == "lattice":                          # ties inside a row and across the K boundary
         x = torch.randint(0, 4, (t, cdim), generator=g).float()
+    elif geometry == "coincident":                       # every segment is one point of its own: all keys of a row are equal
+        x = torch.cat([torch.randn(1, cdim, generator=g).expand(n, cdim) for n in sizes])
     else:                                                # "identical": the segment of 65 nodes is one point, the rest a coarse lattice
         x = torch.randint(0, 3, (t, cdim), generator=g).float()
         at = sizes.index(65)
@@ -87,8 +93,8 @@ def _check(seg, k, idx, rank, pidx, prank, what):
         assert bool((_bits(rank[lo:lo + n, m:]) == INF_BITS[rank.dtype]).all()), (what, "graph", g, "size", n, "empty slots' ranks")
 
 
-def _compare(cdim, dtype, geometry, k):
-    sizes = _sizes(k)
+def _compare(cdim, dtype, geometry, k, sizes=None):
+    sizes = _sizes(k) if sizes is None else sizes
     seg, x, _, _ = _batch(sizes, cdim, dtype, geometry)
     assert k <= seg.num_nodes
     pidx, prank = _padded(sizes, cdim, dtype, geometry, k)
@@ -111,6 +117,22 @@ def test_random_coordinates_match_the_padded_selection(dtype, cdim, k):
                          ids=["f32_c3", "f32_c5", "f32_c9", "f64_c3"])
 def test_tied_coordinates_match_the_padded_selection(dtype, cdim, k, geometry):
     _compare(cdim, dtype, geometry, k)
+
+
+COINCIDENT = (200, 300)                                  # survivors of the pruning bound: 200, 300 > 128; index digits: one, two
+
+
+@pytest.mark.parametrize("k", (8, 33, 64))
+@pytest.mark.parametrize("dtype,cdim", [(torch.float32, 3), (torch.float32, 9), (torch.float64, 3)], ids=["f32_c3", "f32_c9", "f64_c3"])
+def test_coincident_segments_fall_back_to_the_radix_passes_on_the_index_digits(dtype, cdim, k):
+    """K <= 64 and every key of a row equal: the pruning path keeps all n > 128 candidates, which do not fit its list, and the radix
+    passes walk every key digit without resolving anything before they reach the index digits.  The padded selection orders ties by
+    ascending index, so every list is lo .. lo + K - 1 with rank 0."""
+    assert all(n > 128 for n in COINCIDENT) and (COINCIDENT[0] - 1).bit_length() <= 8 < (COINCIDENT[1] - 1).bit_length() and k <= 64
+    _compare(cdim, dtype, "coincident", k, sizes=COINCIDENT)
+    pidx, prank = _padded(COINCIDENT, cdim, dtype, "coincident", k)
+    for g, n in enumerate(COINCIDENT):                   # (the yardstick itself, on this geometry: ties by ascending index)
+        assert torch.equal(pidx[g, :n], torch.arange(k, device="cuda", dtype=pidx.dtype).expand(n, k)) and not bool(prank[g, :n].any())
 
 
 @pytest.mark.parametrize("lds_nodes", (None, SWITCH))
