@@ -200,6 +200,16 @@ SIGNATURES = {name: (restype, argtypes) for names, restype, argtypes in (
     ("egnn_knn_select_segments_f32 egnn_knn_select_segments_f64", c_int,
      (c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p)),
     ("egnn_knn_segments_lds_nodes", c_int, (c_int,)),
+    # per-graph readout of a packed batch
+    ("egnn_segment_reduce_chunk_rows", c_int, ()),
+    ("egnn_segment_reduce_workspace_bytes", c_size_t, (c_int, c_int64, c_int, c_int)),
+    ("egnn_segment_reduce_f32 egnn_segment_reduce_f64", c_int,
+     (c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_int, c_void_p,
+      c_void_p, c_void_p, c_size_t, c_void_p)),
+    ("egnn_segment_broadcast_f32 egnn_segment_broadcast_f64", c_int, (c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p)),
+    ("egnn_segment_scatter_rows_f32 egnn_segment_scatter_rows_f64", c_int,
+     (c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p)),
+    ("egnn_segment_gather_rows_f32 egnn_segment_gather_rows_f64", c_int, (c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p)),
     # adjacency: CSR expansion, degrees, dense expansion
     ("egnn_adj_csr_workspace_bytes egnn_adj_expand_workspace_bytes", c_size_t, (c_int, c_int)),
     ("egnn_adj_csr_square_count", c_int,

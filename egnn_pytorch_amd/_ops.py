@@ -447,6 +447,100 @@ def knn_select_segments(coors, segments, k, out=None):
     return idx, rank
 
 
+SEGMENT_OPS = {"sum": 0, "mean": 1, "max": 2, "min": 3}
+
+
+def _segment_args(x, segments, rows, what):
+    """the checks the segment readout wrappers share: a (rows, D) float32 / float64 matrix on the segments' device"""
+    if not isinstance(segments, GraphSegments):
+        raise TypeError(f"segments must be a GraphSegments (got {type(segments).__name__})")
+    if x.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"{what} takes float32 or float64 rows (got {x.dtype})")
+    if x.dim() != 2 or x.shape[0] != rows or x.shape[1] < 1:
+        raise ValueError(f"{what}: shape {tuple(x.shape)}: expected ({rows}, D) with D >= 1 for these segments")
+    if segments.device != x.device:
+        raise RuntimeError(f"Expected all tensors to be on the same device: the rows are on {x.device}, the segments on {segments.device}")
+    if segments.num_nodes < 1:
+        raise ValueError(f"{what}: a packed batch without a node has no kernel to run")
+    return "_f64" if x.dtype == torch.float64 else "_f32"
+
+
+def segment_reduce(x, segments, op="sum"):
+    """(T, D) node rows -> (G, D) graph rows -- egnn_segment_reduce_f32 / _f64 (csrc/segment_reduce.hip): op "sum" / "mean" return out,
+    "max" / "min" return (out, rows int32 (G, D): the winning row of the packed batch per graph and column).  Fixed order, no atomics;
+    the order for a graph depends on its size and D only.  x: float32 / float64; rows at any pitch (a column slice of a wider matrix is
+    read in place, 16-byte loads where D, the pitch and the base allow them -- the same bits either way); anything else (a transposed
+    view) is copied first."""
+    sfx = _segment_args(x, segments, segments.num_nodes, "segment_reduce")
+    if op not in SEGMENT_OPS:
+        raise ValueError(f"segment_reduce: op = {op!r}: expected one of {tuple(SEGMENT_OPS)}")
+    t, d = x.shape
+    if x.stride(1) != 1 or x.stride(0) < d:
+        x = x.contiguous()
+    g = segments.num_graphs
+    tab = segments._reduce_tables()
+    out = empty(g, d, dtype=x.dtype, device=x.device)
+    rows = empty(g, d, dtype=torch.int32, device=x.device) if SEGMENT_OPS[op] >= 2 else None
+    lib = _abi.load()
+    ws = None
+    if tab.n_multi:
+        ws = empty(lib.egnn_segment_reduce_workspace_bytes(g, t, d, x.element_size()), dtype=torch.uint8, device=x.device)
+    name = "egnn_segment_reduce" + sfx
+    with _timed("segment_reduce"):
+        rc = getattr(lib, name)(_ptr(x), x.stride(0), _ptr(segments.offsets), _ptr(tab.chunk_row), _ptr(tab.chunk_seg), _ptr(tab.chunk_slot),
+                                tab.n_chunks, _ptr(tab.multi_seg), _ptr(tab.multi_slot), tab.n_multi, g, t, d, SEGMENT_OPS[op], _ptr(out),
+                                _ptr(rows), _ptr(ws), 0 if ws is None else ws.numel(), _stream())
+    _abi.check(rc, name)
+    return out if rows is None else (out, rows)
+
+
+def segment_broadcast(g, segments):
+    """(G, D) graph rows -> (T, D): every node receives its graph's row -- egnn_segment_broadcast_f32 / _f64"""
+    sfx = _segment_args(g, segments, segments.num_graphs, "segment_broadcast")
+    g = g.contiguous()
+    out = empty(segments.num_nodes, g.shape[1], dtype=g.dtype, device=g.device)
+    name = "egnn_segment_broadcast" + sfx
+    with _timed("segment_broadcast"):
+        rc = getattr(_abi.load(), name)(_ptr(g), _ptr(segments.segment_of), segments.num_graphs, segments.num_nodes, g.shape[1], _ptr(out),
+                                        _stream())
+    _abi.check(rc, name)
+    return out
+
+
+def _segment_rows(rows, g):
+    if rows.dtype != torch.int32 or tuple(rows.shape) != tuple(g) or not rows.is_contiguous():
+        raise ValueError(f"rows must be a contiguous int32 {tuple(g)} tensor (got {rows.dtype} {tuple(rows.shape)})")
+    return rows
+
+
+def segment_scatter_rows(g, rows, segments):
+    """(G, D) graph rows -> (T, D): g[s, c] at row rows[s, c] of column c, 0 elsewhere (the backward of `segment_reduce`'s max / min:
+    one store per element, no atomics) -- egnn_segment_scatter_rows_f32 / _f64"""
+    sfx = _segment_args(g, segments, segments.num_graphs, "segment_scatter_rows")
+    g = g.contiguous()
+    _segment_rows(rows, g.shape)
+    out = empty(segments.num_nodes, g.shape[1], dtype=g.dtype, device=g.device)
+    name = "egnn_segment_scatter_rows" + sfx
+    with _timed("segment_scatter_rows"):
+        rc = getattr(_abi.load(), name)(_ptr(g), _ptr(rows), _ptr(segments.segment_of), segments.num_graphs, segments.num_nodes, g.shape[1],
+                                        _ptr(out), _stream())
+    _abi.check(rc, name)
+    return out
+
+
+def segment_gather_rows(x, rows, segments):
+    """(T, D) node rows -> (G, D): x[rows[s, c], c] (the transpose of `segment_scatter_rows`) -- egnn_segment_gather_rows_f32 / _f64"""
+    sfx = _segment_args(x, segments, segments.num_nodes, "segment_gather_rows")
+    x = x.contiguous()
+    _segment_rows(rows, (segments.num_graphs, x.shape[1]))
+    out = empty(segments.num_graphs, x.shape[1], dtype=x.dtype, device=x.device)
+    name = "egnn_segment_gather_rows" + sfx
+    with _timed("segment_gather_rows"):
+        rc = getattr(_abi.load(), name)(_ptr(x), _ptr(rows), segments.num_graphs, segments.num_nodes, x.shape[1], _ptr(out), _stream())
+    _abi.check(rc, name)
+    return out
+
+
 KNN_GRID_KMAX = 128           # the K limit of egnn_knn_select_grid_f32 / _f64 and _grid_csr_f32 / _f64 (csrc/knn_grid.hip: KG_KMAX)
 
 

@@ -9,10 +9,22 @@ cross a segment boundary; the segmented selection (csrc/knn_segments.hip, `_ops.
 It is built once by the caller, like `SparseAdjacency`, and keeps the offsets on the device (for the kernel) and on the host (sizes,
 the largest graph, the chunking of `split`): no forward synchronises to read them.  Construction, `pack` and `unpack` are ordinary
 tensor code on whatever device the inputs live on, so they work on CPU tensors.
+
+Graph-level work stays packed: `reduce` takes (T, ...) node rows to (G, ...) graph rows (sum, mean, max, min), `broadcast` goes back and
+`center` removes every graph's mean.  On the device they run the ordered, atomic-free kernels of csrc/segment_reduce.hip -- the bits
+of a graph's result depend on its own rows only -- and are differentiable to any order; on CPU tensors, ordinary torch code with the
+same tie and empty-graph rules.
 """
 from __future__ import annotations
 
+import collections
+
 import torch
+
+# rows of a chunk of the segmented reduction (csrc/segment_reduce.hip: SR_ROWS; egnn_segment_reduce_chunk_rows() of the library)
+SEGMENT_CHUNK_ROWS = 128
+
+_ReduceTables = collections.namedtuple("_ReduceTables", "chunk_row chunk_seg chunk_slot n_chunks multi_seg multi_slot n_multi")
 
 
 class GraphSegments:
@@ -45,6 +57,8 @@ class GraphSegments:
         self.offsets = torch.tensor(host, dtype=torch.int64, device=dev)
         self._derived = None
         self._slots = None                                   # (B, N) of the padded batch `from_mask` came from, and its real slots
+        self._tables = None                                  # the chunk tables of `reduce` on the device
+        self._inv = {}                                       # dtype -> (G, 1) 1 / size
 
     # ------------------------------------------------------------------ constructors
     @classmethod
@@ -191,6 +205,110 @@ class GraphSegments:
         sizes = self.offsets[1:] - self.offsets[:-1]
         return torch.arange(self.max_size, device=self.device)[None, :] < sizes[:, None]
 
+    # ------------------------------------------------------------------ readout: node rows <-> graph rows
+    def _reduce_tables(self):
+        """The chunk tables of csrc/segment_reduce.hip (include/egnn_hip.h: egnn_segment_reduce_f32), built on the host from the host
+        offsets, uploaded once and kept: every graph cut into chunks of SEGMENT_CHUNK_ROWS rows from its own first row (an empty graph:
+        one chunk without rows); the chunks of a graph that has several own consecutive partial slots."""
+        if self._tables is None:
+            r = SEGMENT_CHUNK_ROWS
+            off = torch.tensor(self._host, dtype=torch.int64)
+            sizes = off[1:] - off[:-1]
+            nch = torch.clamp((sizes + (r - 1)) // r, min=1)
+            seg = torch.repeat_interleave(torch.arange(self.num_graphs), nch)
+            first = torch.cumsum(nch, 0) - nch                                       # the first chunk of every graph
+            row = off[:-1][seg] + (torch.arange(seg.numel()) - first[seg]) * r
+            multi = nch > 1
+            slot0 = torch.cumsum(torch.where(multi, nch, torch.zeros_like(nch)), 0) - nch   # (read at the graphs of several chunks only)
+            slot = torch.where(multi[seg], slot0[seg] + (torch.arange(seg.numel()) - first[seg]), torch.full_like(seg, -1))
+            mseg = multi.nonzero().reshape(-1)
+
+            def up(t):
+                return t.to(torch.int32).to(self.device)
+
+            self._tables = _ReduceTables(up(row), up(seg), up(slot), int(seg.numel()), up(mseg) if mseg.numel() else None,
+                                         up(slot0[mseg]) if mseg.numel() else None, int(mseg.numel()))
+        return self._tables
+
+    def _inv_sizes(self, dtype):
+        """(G, 1): 1 / n of every graph, 0 for an empty one -- host sizes, uploaded once per dtype"""
+        if dtype not in self._inv:
+            self._inv[dtype] = torch.tensor([1.0 / n if n else 0.0 for n in self.sizes], dtype=torch.float64).to(dtype).to(self.device)[:, None]
+        return self._inv[dtype]
+
+    def _readout_rows(self, x, rows, what, lead):
+        """the checks of `reduce` / `broadcast` -> x as a (rows, D) matrix in the dtype the kernels run (float32 or float64)"""
+        if not torch.is_tensor(x):
+            raise TypeError(f"{what}: expected a tensor (got {type(x).__name__})")
+        if not x.dtype.is_floating_point:
+            raise TypeError(f"{what} takes floating-point values (got {x.dtype})")
+        if x.dim() < 1 or x.shape[0] != rows:
+            raise ValueError(f"{what}: x shape {tuple(x.shape)}: expected ({rows}, ...): one row per {lead} of these segments")
+        if x.device != self.device:
+            raise RuntimeError(f"Expected all tensors to be on the same device: x is on {x.device}, the segments on {self.device}")
+        d = 1
+        for v in x.shape[1:]:
+            d *= v
+        if d < 1:
+            raise ValueError(f"{what}: x shape {tuple(x.shape)} holds no column")
+        x2 = x.reshape(rows, d)
+        if x2.dtype in (torch.float16, torch.bfloat16):
+            x2 = x2.float()                                                          # accumulated in fp32, returned in the caller's dtype
+        return x2
+
+    def reduce(self, x, op="sum"):
+        """(T, ...) node rows -> (G, ...) graph rows: op "sum", "mean", "max" or "min" over the nodes of every graph, per column.
+        Empty graphs give 0 for sum / mean (zero gradient); max / min of a batch that holds one raise ValueError.  max / min: a NaN
+        wins (as in torch.amax), ties go to the lowest row, and the gradient goes to that row alone.  On the device: the ordered,
+        atomic-free kernels of csrc/segment_reduce.hip -- a graph's bits depend on its own rows only, not on the batch around it;
+        float16 / bfloat16 accumulate in fp32.  Differentiable to any order; reads nothing back."""
+        if op not in ("sum", "mean", "max", "min"):
+            raise ValueError(f"reduce: op = {op!r}: expected \"sum\", \"mean\", \"max\" or \"min\"")
+        x2 = self._readout_rows(x, self.num_nodes, "reduce", "node")
+        if op in ("max", "min") and min(self.sizes) == 0:
+            raise ValueError(f"reduce: {op} of an empty graph is undefined (graph {self.sizes.index(0)} holds no node)")
+        if op in ("sum", "mean"):
+            if self.num_nodes == 0:
+                out = x2.new_zeros(self.num_graphs, x2.shape[1]) + x2.sum(0, keepdim=True)
+            elif x2.is_cuda:
+                out = _SegmentSum.apply(x2, self, op == "mean")
+            else:
+                out = torch.zeros(self.num_graphs, x2.shape[1], dtype=x2.dtype).index_add(0, self.segment_of.to(torch.int64), x2)
+                if op == "mean":
+                    out = out * self._inv_sizes(x2.dtype)
+        elif x2.is_cuda:
+            out = _SegmentExtreme.apply(x2, self, op == "max")
+        else:
+            out = x2.gather(0, self._winners_host(x2.detach(), op == "max").to(torch.int64))
+        return out.to(x.dtype).reshape(self.num_graphs, *x.shape[1:])
+
+    def _winners_host(self, x2, is_max):
+        """CPU tensors: int32 (G, D), the row `reduce` selects -- the first NaN of a column, else the first occurrence of the extreme"""
+        rows = []
+        for a, b in zip(self._host, self._host[1:]):
+            s = x2[a:b]
+            best = s.amax(0, keepdim=True) if is_max else s.amin(0, keepdim=True)
+            hit = torch.where(torch.isnan(best), torch.isnan(s), s == best)
+            at = torch.arange(a, b, dtype=torch.int64)[:, None].expand_as(s)
+            rows.append(torch.where(hit, at, torch.full_like(at, b)).amin(0))
+        return torch.stack(rows).to(torch.int32)
+
+    def broadcast(self, g):
+        """(G, ...) graph rows -> (T, ...): every node receives its graph's row.  Differentiable to any order (its backward is
+        reduce "sum")."""
+        g2 = self._readout_rows(g, self.num_graphs, "broadcast", "graph")
+        if self.num_nodes == 0:
+            out = g2[:0]
+        elif g2.is_cuda:
+            out = _SegmentBroadcast.apply(g2, self)
+        else:
+            out = g2.index_select(0, self.segment_of.to(torch.int64))
+        return out.to(g.dtype).reshape(self.num_nodes, *g.shape[1:])
+
+    def center(self, x):
+        """x - broadcast(reduce(x, "mean")): every graph moved to zero mean (coordinates: the zero-centre-of-mass projection)"""
+        return x - self.broadcast(self.reduce(x, "mean"))
+
     # ------------------------------------------------------------------ chunks
     def split(self, max_nodes):
         """Yields (row_slice, GraphSegments) pieces cut at graph boundaries, each with at most `max_nodes` rows -- greedily, in order.
@@ -211,3 +329,69 @@ class GraphSegments:
 
     def __repr__(self):
         return f"GraphSegments(graphs={self.num_graphs}, nodes={self.num_nodes}, max_size={self.max_size}, device={self.device})"
+
+
+# ---------------------------------------------------------------------- the readout under autograd (device tensors)
+# Each backward is a call of another Function of this group, so a graph recorded with create_graph=True differentiates again without a
+# path of its own: sum / mean <-> broadcast, max / min -> scatter to the winning rows <-> gather at them.
+class _SegmentSum(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, seg, mean):
+        from . import _ops
+        ctx.seg, ctx.mean = seg, mean
+        return _ops.segment_reduce(x, seg, "mean" if mean else "sum")
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.mean:
+            g = g * ctx.seg._inv_sizes(g.dtype)
+        return _SegmentBroadcast.apply(g, ctx.seg), None, None
+
+
+class _SegmentBroadcast(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, seg):
+        from . import _ops
+        ctx.seg = seg
+        return _ops.segment_broadcast(g, seg)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _SegmentSum.apply(g, ctx.seg, False), None
+
+
+class _SegmentExtreme(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, seg, is_max):
+        from . import _ops
+        out, rows = _ops.segment_reduce(x, seg, "max" if is_max else "min")
+        ctx.seg, ctx.rows = seg, rows
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        return _SegmentScatter.apply(g, ctx.rows, ctx.seg), None, None
+
+
+class _SegmentScatter(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, g, rows, seg):
+        from . import _ops
+        ctx.seg, ctx.rows = seg, rows
+        return _ops.segment_scatter_rows(g, rows, seg)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _SegmentGather.apply(g, ctx.rows, ctx.seg), None, None
+
+
+class _SegmentGather(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, rows, seg):
+        from . import _ops
+        ctx.seg, ctx.rows = seg, rows
+        return _ops.segment_gather_rows(x, rows, seg)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _SegmentScatter.apply(g, ctx.rows, ctx.seg), None, None

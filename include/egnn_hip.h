@@ -188,6 +188,43 @@ int egnn_knn_select_segments_f64(const double* coors, const int64_t* offsets, co
                                  int max_segment, int32_t* idx_out, double* rank_out, void* stream);
 int egnn_knn_segments_lds_nodes(int limit);
 
+/* Per-graph readout of a packed batch (csrc/segment_reduce.hip): x (T, D) node rows at a pitch of ldx elements -> out (G, D), contiguous;
+ * op: 0 sum, 1 mean (the sum, one division by n; an empty graph: 0), 2 max, 3 min (per column; a NaN wins, ties go to the lowest row;
+ * rows_out (G, D) int32 receives the winning rows of the packed batch -- required for 2 and 3, unused otherwise).  No float atomics;
+ * the order of additions for a graph is a function of its size and D only, the same on the 16-byte load path
+ * (D % 4 == 0, x and the pitch 16-byte aligned) and the scalar one (anything else): chosen here, no alignment is required.
+ * The chunk tables are the caller's (egnn_pytorch_amd.GraphSegments builds them on the host from its offsets, once), int32 on the device:
+ * every graph is cut into chunks of egnn_segment_reduce_chunk_rows() rows from its own first row, an empty graph is one chunk of no
+ * rows; chunk_row / chunk_seg (n_chunks): first row and graph of each chunk, in row order; chunk_slot (n_chunks): -1 for the only chunk
+ * of a graph (its result is written directly), else its partial's slot in the workspace, the slots of one graph consecutive in chunk
+ * order; multi_seg / multi_slot (n_multi): the graphs of more than one chunk and their first slot (NULL when n_multi = 0, as may be the
+ * workspace).  workspace: egnn_segment_reduce_workspace_bytes(G, T, D, sizeof element) bytes, 16-byte aligned (positive, non-decreasing
+ * in G, T and D; 0 for a bad argument).  One launch, two when n_multi > 0, on `stream`; nothing is read back.  Entries of the tables
+ * out of range are clamped into the arrays.
+ * Errors, all returned before any launch: EGNN_E_NULLPTR; EGNN_E_SHAPE (G, T, D <= 0, ldx < D, n_chunks < G, n_multi outside
+ * 0..n_chunks, a workspace that is too small); EGNN_E_UNSUPPORTED (an unknown op, T >= 2^31, D beyond 65 535 column tiles);
+ * EGNN_E_ALIGN (workspace).
+ * egnn_segment_broadcast: out (T, D) = g[segment_of[t], :].  egnn_segment_scatter_rows: out[t, c] = g[s, c] where rows[s, c] == t for
+ * s = segment_of[t], else 0 -- the transpose of max / min's selection: every element stored once, no atomics.  egnn_segment_gather_rows:
+ * out[s, c] = x[rows[s, c], c] (0 where rows holds no row of the batch) -- the transpose of that.  g, rows, x, out contiguous.  Errors:
+ * EGNN_E_NULLPTR, EGNN_E_SHAPE (G, T, D <= 0), EGNN_E_UNSUPPORTED (T >= 2^31), before any launch. */
+int egnn_segment_reduce_chunk_rows(void);
+size_t egnn_segment_reduce_workspace_bytes(int G, int64_t T, int D, int elem_bytes);
+int egnn_segment_reduce_f32(const float* x, int64_t ldx, const int64_t* offsets, const int32_t* chunk_row, const int32_t* chunk_seg,
+                            const int32_t* chunk_slot, int n_chunks, const int32_t* multi_seg, const int32_t* multi_slot, int n_multi, int G,
+                            int64_t T, int D, int op, float* out, int32_t* rows_out, void* workspace, size_t workspace_bytes, void* stream);
+int egnn_segment_reduce_f64(const double* x, int64_t ldx, const int64_t* offsets, const int32_t* chunk_row, const int32_t* chunk_seg,
+                            const int32_t* chunk_slot, int n_chunks, const int32_t* multi_seg, const int32_t* multi_slot, int n_multi, int G,
+                            int64_t T, int D, int op, double* out, int32_t* rows_out, void* workspace, size_t workspace_bytes, void* stream);
+int egnn_segment_broadcast_f32(const float* g, const int32_t* segment_of, int G, int64_t T, int D, float* out, void* stream);
+int egnn_segment_broadcast_f64(const double* g, const int32_t* segment_of, int G, int64_t T, int D, double* out, void* stream);
+int egnn_segment_scatter_rows_f32(const float* g, const int32_t* rows, const int32_t* segment_of, int G, int64_t T, int D, float* out,
+                                  void* stream);
+int egnn_segment_scatter_rows_f64(const double* g, const int32_t* rows, const int32_t* segment_of, int G, int64_t T, int D, double* out,
+                                  void* stream);
+int egnn_segment_gather_rows_f32(const float* x, const int32_t* rows, int G, int64_t T, int D, float* out, void* stream);
+int egnn_segment_gather_rows_f64(const double* x, const int32_t* rows, int G, int64_t T, int D, double* out, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Sparse adjacency: the N-degree expansion of EGNN_Network (egnn_pytorch.py:414-427; egnn_adj_expand_u8 is its dense form) on CSR rows
  * (csrc/adj_csr.hip).  Row pointers are int64 (G, N + 1) ABSOLUTE offsets into a flat int32 column array, columns strictly ascending
