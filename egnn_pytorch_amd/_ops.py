@@ -375,6 +375,29 @@ def check_range(device=None, wait=True):
             _raise_range(bits, "an earlier call", origin="earlier")
 
 
+def _dtype_suffix(dtype):
+    """the suffix of an entry's float32 / float64 twins for tensors of `dtype`"""
+    return "_f64" if dtype == torch.float64 else "_f32"
+
+
+def _knn_outputs(out, coors, *shape):
+    """(idx int32, rank in the coordinates' dtype) of a selection, both of `shape`: `out` where the caller allocated them, else new on
+    the current stream"""
+    if out is not None:
+        return out
+    return empty(*shape, dtype=torch.int32, device=coors.device), empty(*shape, dtype=coors.dtype, device=coors.device)
+
+
+def _csr_args(adj, coors):
+    """(rowptr, col, graph stride of rowptr) as the CSR entries take them, of a SparseAdjacency checked against (B, N, C) coordinates"""
+    b, n = coors.shape[:2]
+    if adj.n != n or (adj.batched and adj.num_graphs != b):
+        raise ValueError(f"adj_mat shape {tuple(adj.shape)} != {(b, n, n)} or {(n, n)}")
+    if adj.device != coors.device:
+        raise RuntimeError(f"Expected all tensors to be on the same device: coors is on {coors.device}, adj_mat on {adj.device}")
+    return _ptr(adj.rowptr), _ptr(adj.col) if adj.col.numel() else None, 0 if adj.shared else n + 1
+
+
 def knn_select(coors, mask, adj_mat, k, out=None):
     """(idx int32 (B,N,K), rank (B,N,K) in the coordinates' dtype) -- egnn_knn_select_f32; float64 coordinates (a float64 module):
     egnn_knn_select_f64.  out = (idx, rank): caller-allocated outputs (the side-stream fork allocates them on the launch stream)."""
@@ -387,21 +410,12 @@ def knn_select_csr(coors, mask, adj, k, out=None):
     """knn_select with the adjacency as a SparseAdjacency -- egnn_knn_select_csr_f32 / _f64: the streaming kernel on sorted column ranges
     at every N; the same outputs bit for bit as knn_select with `adj.to_dense()`, without the (N, N) map."""
     b, n, cdim = coors.shape
-    if adj.n != n or (adj.batched and adj.num_graphs != b):
-        raise ValueError(f"adj_mat shape {tuple(adj.shape)} != {(b, n, n)} or {(n, n)}")
-    if adj.device != coors.device:
-        raise RuntimeError(f"Expected all tensors to be on the same device: coors is on {coors.device}, adj_mat on {adj.device}")
-    f64 = coors.dtype == torch.float64
-    if out is not None:
-        idx, rank = out
-    else:
-        idx = empty(b, n, k, dtype=torch.int32, device=coors.device)
-        rank = empty(b, n, k, dtype=coors.dtype, device=coors.device)
+    csr = _csr_args(adj, coors)
+    idx, rank = _knn_outputs(out, coors, b, n, k)
     m8 = _u8(mask)
-    name = "egnn_knn_select_csr" + ("_f64" if f64 else "_f32")
+    name = "egnn_knn_select_csr" + _dtype_suffix(coors.dtype)
     with _timed("knn_select"):
-        rc = getattr(_abi.load(), name)(_ptr(coors), _ptr(m8), _ptr(adj.rowptr), _ptr(adj.col) if adj.col.numel() else None,
-                                        0 if adj.shared else n + 1, b, n, k, cdim, _ptr(idx), _ptr(rank), _stream())
+        rc = getattr(_abi.load(), name)(_ptr(coors), _ptr(m8), *csr, b, n, k, cdim, _ptr(idx), _ptr(rank), _stream())
     _abi.check(rc, name)
     return idx, rank
 
@@ -432,14 +446,10 @@ def knn_select_segments(coors, segments, k, out=None):
         raise RuntimeError(f"Expected all tensors to be on the same device: coors is on {coors.device}, the segments on {segments.device}")
     t, cdim = coors.shape
     coors = aligned(coors)
-    if out is not None:
-        idx, rank = out
-    else:
-        idx = empty(t, k, dtype=torch.int32, device=coors.device)
-        rank = empty(t, k, dtype=coors.dtype, device=coors.device)
+    idx, rank = _knn_outputs(out, coors, t, k)
     lib = _abi.load()
     lib.egnn_knn_segments_lds_nodes(int(KNN_SEGMENTS_LDS_NODES or 0))
-    name = "egnn_knn_select_segments" + ("_f64" if coors.dtype == torch.float64 else "_f32")
+    name = "egnn_knn_select_segments" + _dtype_suffix(coors.dtype)
     with _timed("knn_select_segments"):
         rc = getattr(lib, name)(_ptr(coors), _ptr(segments.offsets), _ptr(segments.segment_of), segments.num_graphs, t, k, cdim,
                                 max(segments.max_size, 1), _ptr(idx), _ptr(rank), _stream())
@@ -462,7 +472,7 @@ def _segment_args(x, segments, rows, what):
         raise RuntimeError(f"Expected all tensors to be on the same device: the rows are on {x.device}, the segments on {segments.device}")
     if segments.num_nodes < 1:
         raise ValueError(f"{what}: a packed batch without a node has no kernel to run")
-    return "_f64" if x.dtype == torch.float64 else "_f32"
+    return _dtype_suffix(x.dtype)
 
 
 def segment_reduce(x, segments, op="sum"):
@@ -546,11 +556,9 @@ KNN_GRID_KMAX = 128           # the K limit of egnn_knn_select_grid_f32 / _f64 a
 
 def _grid_suffix(dtype):
     """the entry suffix of the cell-grid selection for coordinates of `dtype`: float32, or float64 (a float64 module)"""
-    if dtype == torch.float32:
-        return "_f32"
-    if dtype == torch.float64:
-        return "_f64"
-    raise TypeError(f"knn_select_grid takes float32 or float64 coordinates (got {dtype})")
+    if dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"knn_select_grid takes float32 or float64 coordinates (got {dtype})")
+    return _dtype_suffix(dtype)
 
 
 def knn_grid_workspace(b, n, k, device, dtype=torch.float32):
@@ -568,44 +576,25 @@ def knn_select_grid(coors, mask, k, out=None, ws=None, adj=None):
     adj: None or a SparseAdjacency (egnn_knn_select_grid_csr_f32 / _f64: the outputs of `knn_select_csr`); a dense map has no grid entry."""
     b, n, cdim = coors.shape
     sfx = _grid_suffix(coors.dtype)
+    csr = ()
     if adj is not None:
         if not isinstance(adj, SparseAdjacency):
             raise TypeError("knn_select_grid takes the adjacency as a SparseAdjacency (a dense map selects on the all-pairs kernels)")
-        if adj.n != n or (adj.batched and adj.num_graphs != b):
-            raise ValueError(f"adj_mat shape {tuple(adj.shape)} != {(b, n, n)} or {(n, n)}")
-        if adj.device != coors.device:
-            raise RuntimeError(f"Expected all tensors to be on the same device: coors is on {coors.device}, adj_mat on {adj.device}")
-    if out is not None:
-        idx, rank = out
-    else:
-        idx = empty(b, n, k, dtype=torch.int32, device=coors.device)
-        rank = empty(b, n, k, dtype=coors.dtype, device=coors.device)
+        csr = _csr_args(adj, coors)
+    idx, rank = _knn_outputs(out, coors, b, n, k)
     m8 = _u8(mask)
     if ws is None:
         ws = knn_grid_workspace(b, n, k, coors.device, coors.dtype)
-    if adj is not None:
-        name = "egnn_knn_select_grid_csr" + sfx
-        with _timed("knn_select_grid"):
-            rc = getattr(_abi.load(), name)(_ptr(coors), _ptr(m8), _ptr(adj.rowptr), _ptr(adj.col) if adj.col.numel() else None,
-                                            0 if adj.shared else n + 1, b, n, k, cdim, _ptr(idx), _ptr(rank), _ptr(ws), ws.numel(),
-                                            _stream())
-        _abi.check(rc, name)
-        return idx, rank
-    name = "egnn_knn_select_grid" + sfx
+    name = ("egnn_knn_select_grid_csr" if csr else "egnn_knn_select_grid") + sfx
     with _timed("knn_select_grid"):
-        rc = getattr(_abi.load(), name)(_ptr(coors), _ptr(m8), b, n, k, cdim, _ptr(idx), _ptr(rank), _ptr(ws), ws.numel(), _stream())
+        rc = getattr(_abi.load(), name)(_ptr(coors), _ptr(m8), *csr, b, n, k, cdim, _ptr(idx), _ptr(rank), _ptr(ws), ws.numel(), _stream())
     _abi.check(rc, name)
     return idx, rank
 
 
 def _knn_select(coors, mask, adj_mat, k, out, entry):
     b, n, cdim = coors.shape
-    f64 = coors.dtype == torch.float64
-    if out is not None:
-        idx, rank = out
-    else:
-        idx = empty(b, n, k, dtype=torch.int32, device=coors.device)
-        rank = empty(b, n, k, dtype=coors.dtype, device=coors.device)
+    idx, rank = _knn_outputs(out, coors, b, n, k)
     m8 = _u8(mask)
     a8 = _u8(adj_mat)
     stride = 0
@@ -616,7 +605,7 @@ def _knn_select(coors, mask, adj_mat, k, out, entry):
             stride = n * n
         elif a8.shape != (n, n):
             raise ValueError(f"adj_mat shape {tuple(a8.shape)} != {(n, n)}")
-    name = entry + ("_f64" if f64 else "_f32")
+    name = entry + _dtype_suffix(coors.dtype)
     with _timed("knn_select"):
         rc = getattr(_abi.load(), name)(_ptr(coors), _ptr(m8), _ptr(a8), stride, b, n, k, cdim, _ptr(idx), _ptr(rank), _stream())
     _abi.check(rc, name)

@@ -9,10 +9,10 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-pass-failed -Wno-inline-a
 rm -rf "$HERE/obj"
 mkdir -p "$HERE/obj"
 pids=()
-for f in knn_select knn_stream knn_grid knn_segments spatial_order adj_expand adj_csr linear_hl node_mlp_fused edge_fused edge_pw edge_exact edge_exact_bwd edge_hidden edge_bwd edge_tail node_ops layer_api segment_sum segment_reduce edge_csr entry_lists global_attn global_attn_bwd linear_f32 node_prep_f32 fp64 linear_split; do
+for f in knn_select knn_rows knn_stream knn_grid knn_segments spatial_order adj_expand adj_csr linear_hl node_mlp_fused edge_fused edge_pw edge_exact edge_exact_bwd edge_hidden edge_bwd edge_tail node_ops layer_api segment_sum segment_reduce edge_csr entry_lists global_attn global_attn_bwd linear_f32 node_prep_f32 fp64 linear_split; do
   EXTRA=""
   # the ranking kernel must reproduce the reference's un-fused ((dx*dx+dy*dy)+dz*dz) bit for bit
-  [ "$f" = knn_select ] || [ "$f" = knn_stream ] || [ "$f" = knn_grid ] || [ "$f" = knn_segments ] && EXTRA="-ffp-contract=off"
+  [ "$f" = knn_select ] || [ "$f" = knn_rows ] || [ "$f" = knn_stream ] || [ "$f" = knn_grid ] || [ "$f" = knn_segments ] && EXTRA="-ffp-contract=off"
   ( "$HIPCC" $FLAGS $EXTRA -c "$HERE/$f.hip" -o "$HERE/obj/$f.o" 2> "$HERE/obj/$f.res" ) &
   pids+=($!)
 done
@@ -43,7 +43,7 @@ for res in "$HERE"/obj/*.res; do
     [ "$f" = edge_fused_c ] && { EXTRA="-DEGNN_EDGE_GENERIC_C"; src=edge_fused; }
     [ "$f" = edge_fused_d ] && { EXTRA="-DEGNN_EDGE_DROP_TU"; src=edge_fused; }
     [ "$f" = edge_fused_cd ] && { EXTRA="-DEGNN_EDGE_DROP_TU -DEGNN_EDGE_GENERIC_C"; src=edge_fused; }
-    [ "$f" = knn_select ] || [ "$f" = knn_stream ] || [ "$f" = knn_grid ] || [ "$f" = knn_segments ] && EXTRA="-ffp-contract=off"
+    [ "$f" = knn_select ] || [ "$f" = knn_rows ] || [ "$f" = knn_stream ] || [ "$f" = knn_grid ] || [ "$f" = knn_segments ] && EXTRA="-ffp-contract=off"
     "$HIPCC" --offload-arch=gfx950 -O3 -std=c++17 -Wno-pass-failed -Wno-inline-asm $EXTRA -S --cuda-device-only \
         -o "$HERE/obj/$f.s" "$HERE/$src.hip" 2> /dev/null
     if ! python3 "$HERE/check_scratch.py" "$HERE/obj/$f.s"; then

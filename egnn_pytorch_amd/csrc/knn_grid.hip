@@ -66,7 +66,7 @@
 // bound fl(fl(r h) fl(r h)), h = fl(1 / inv_h), is off by < 2^-50.  Together < 2^-39, far inside the margin (r h)^2 (1 - 2^-8) that
 // the kernel keeps for both types; the rest of the argument -- strictly below, unvisited keys above the K-th, ties decided among
 // visited nodes -- does not depend on the type.
-#include "egnn_common.h"
+#include "knn_core.h"
 
 namespace {
 
@@ -154,12 +154,6 @@ inline KgLayout kg_layout(int B, int N, size_t rec)
     L.sorted = o; o = up(o + (size_t)B * N * rec);
     L.total = o;
     return L;
-}
-
-__device__ __forceinline__ void kg_wave_sync()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
 }
 
 // ---- bbox: chunk p of graph b -> 16 doubles: sum x y z, sum x^2 y^2 z^2, min x y z, max x y z, valid count, non-finite count
@@ -373,17 +367,17 @@ __global__ __launch_bounds__(KG_THREADS) void kg_place_kernel(const T* __restric
 template <typename C>
 __device__ __forceinline__ void kg_compact(C* buf, C* tmp, int& cnt, C& tau, int K, int lane)
 {
-    kg_wave_sync();
+    egnn_wave_lds_sync();
     for (int t = lane; t < cnt; t += 64) {
         const C c = buf[t];
         int rnk = 0;
         for (int u = 0; u < cnt; ++u) rnk += kg_less(buf[u], c) ? 1 : 0;
         if (rnk < K) tmp[rnk] = c;
     }
-    kg_wave_sync();
+    egnn_wave_lds_sync();
     const int n = cnt < K ? cnt : K;
     for (int t = lane; t < n; t += 64) buf[t] = tmp[t];
-    kg_wave_sync();
+    egnn_wave_lds_sync();
     cnt = n;
     if (n == K) tau = buf[K - 1];
 }
@@ -588,7 +582,7 @@ __global__ __launch_bounds__(KG_THREADS) void kg_search_kernel(const uint8_t* __
         }
         // (every cell visited or the rule above met; nvalid >= K, so K entries, sorted -- CSR: the seeds and the valid nodes outside
         // them are distinct and no fewer)
-        kg_wave_sync();
+        egnn_wave_lds_sync();
         const T d2k = kg_comp_rank(tau);
         const bool hand_over = cnt < K || (d2k >= (T)1e5 && H.nvalid < N);
         if (!hand_over) {
@@ -600,7 +594,7 @@ __global__ __launch_bounds__(KG_THREADS) void kg_search_kernel(const uint8_t* __
             }
         }
         if (lane == 0) fb[i] = hand_over ? 1 : 0;
-        kg_wave_sync();
+        egnn_wave_lds_sync();
     }
 }
 

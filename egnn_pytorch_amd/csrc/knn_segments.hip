@@ -14,7 +14,7 @@
 // them from memory (the packed coordinates are L2-resident) -- the same code on another source, decided per row, wave-uniform.
 //
 // Selection (both sources): nothing is stored per candidate.  Radix select over the 8-bit digits of the composite (key, local index)
-// -- egnn_rank_key's digits first, then the index's -- exactly knn_stream.hip's, with one wave and one 256-bin LDS histogram per row:
+// -- egnn_rank_key's digits first, then the index's -- knn_stream.hip's, on the same arithmetic (knn_core.h), with one wave and one 256-bin LDS histogram per row:
 //   pass:  every candidate whose composite matches the resolved prefix bumps the bin of its next digit (integer LDS atomics); the bin
 //          holding the K-th smallest extends the prefix; the row is resolved once that bin holds exactly what is still missing.
 //   pick:  the candidates whose composite prefix is <= the resolved one (exactly min(K, n)) are compacted into the wave's list by
@@ -26,7 +26,7 @@
 // wave's list, where they are ranked by counting and the first K written.  No atomics, two walks instead of three or four.  A row whose
 // survivors do not fit the list (heavily tied keys) takes the radix passes after all.
 // Deterministic: the output order is the (key, index) order and only integer counters are atomic.
-#include "egnn_common.h"
+#include "knn_core.h"
 
 namespace {
 
@@ -37,23 +37,12 @@ constexpr size_t SG_LDS_BYTES = 64 * 1024;               // per workgroup: two w
 
 int g_lds_nodes = 0;                                     // egnn_knn_segments_lds_nodes: 0 = the built-in budget
 
-template <typename T> struct SgKey;
-template <> struct SgKey<float> { typedef uint32_t type; static constexpr int V = 8; };
-template <> struct SgKey<double> { typedef uint64_t type; static constexpr int V = 4; };
-
-__device__ __forceinline__ void sg_wave_lds_sync() {
-    // same-wave LDS hand-off (knn_select.hip): DS operations of one wave execute in issue order; the wait makes the
-    // store -> other-lane load dependency explicit, the wave barrier pins the compiler's ordering
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-}
-
 template <bool V> struct SgSrc { static constexpr bool lds = V; };
 
 __host__ __device__ constexpr size_t sg_up8(size_t b) { return (b + 7) / 8 * 8; }
 // LDS bytes of one wave's block: the pick list (keys, local indices), the histogram, the query's coordinates (CDM == 0)
 template <typename T> __host__ __device__ constexpr size_t sg_wave_bytes(int Lp, int CQ) {
-    return sg_up8((size_t)Lp * (sizeof(typename SgKey<T>::type) + 4) + 256 * 4 + (size_t)CQ * sizeof(T));
+    return sg_up8((size_t)Lp * (sizeof(typename egnn_knn_key<T>::type) + 4) + 256 * 4 + (size_t)CQ * sizeof(T));
 }
 constexpr int SG_SURVIVORS = 128;                        // the least the pick list holds: what the pruning path may rank (two per lane)
 
@@ -64,7 +53,7 @@ __global__ __launch_bounds__(SG_THREADS) void knn_select_segments_kernel(
     const T* __restrict__ coors, const int64_t* __restrict__ offsets, const int32_t* __restrict__ segment_of, int G, int NT, int K, int C,
     int W, int Lp, int32_t* __restrict__ idx_out, T* __restrict__ rank_out)
 {
-    typedef typename SgKey<T>::type key_t;
+    typedef typename egnn_knn_key<T>::type key_t;
     constexpr int KB = 8 * (int)sizeof(key_t);           // key bits
     constexpr int KD = KB / 8;                           // key digits
     constexpr int PB = KB / 2;                           // leading key bits the pruning bound resolves (float: sign, exponent, 7 mantissa bits)
@@ -127,25 +116,11 @@ __global__ __launch_bounds__(SG_THREADS) void knn_select_segments_kernel(
             constexpr bool LDS = decltype(source)::lds;
             const int w0 = lo - (int)wlo;                // the segment's first node in the window (LDS)
             const T* cb = coors + (size_t)lo * C;        // ... and in memory
+            // (no mask, no adjacency: the key of the squared distance itself.  The window is component-major for CDM != 0)
+            const T* qi = CDM == 0 ? qs : ci;
             auto key_of = [&](int jl) -> key_t {
-                T d;
-                if constexpr (CDM == 3) {
-                    float dx, dy, dz;
-                    if constexpr (LDS) d = egnn_sqdist(ci[0], ci[1], ci[2], xs[w0 + jl], xs[W + w0 + jl], xs[2 * W + w0 + jl], dx, dy, dz);
-                    else d = egnn_sqdist(ci[0], ci[1], ci[2], cb[(size_t)jl * 3], cb[(size_t)jl * 3 + 1], cb[(size_t)jl * 3 + 2], dx, dy, dz);
-                } else if constexpr (CDM == 8) {
-                    float cj[8], rel[8];
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) {
-                        if constexpr (LDS) cj[c] = c < C ? xs[(size_t)c * W + w0 + jl] : 0.f;
-                        else cj[c] = c < C ? cb[(size_t)jl * C + c] : 0.f;
-                    }
-                    d = egnn_sqdist_n<8>(ci, cj, C, rel);
-                } else {
-                    if constexpr (LDS) d = egnn_sqdist_any<T, SgKey<T>::V>(qs, xs + (size_t)(w0 + jl) * CS, C);
-                    else d = egnn_sqdist_any<T, SgKey<T>::V>(qs, cb + (size_t)jl * C, C);
-                }
-                return egnn_rank_key(d);
+                const T* cj = !LDS ? cb + (size_t)jl * (CDM == 3 ? 3 : C) : (CDM == 0 ? xs + (size_t)(w0 + jl) * CS : xs + w0 + jl);
+                return egnn_knn_key_of<T, CDM>(qi, cj, (LDS && CDM != 0) ? W : 1, C, true, nullptr, (const uint8_t*)nullptr, i, jl);
             };
 
             const bool all = n <= K;                     // every candidate is selected: no search
@@ -178,21 +153,12 @@ __global__ __launch_bounds__(SG_THREADS) void knn_select_segments_kernel(
                     if (take && pos < SG_SURVIVORS) { selk[pos] = kj; selj[pos] = jl; }
                     S += __popcll(bs);
                 }
-                sg_wave_lds_sync();
+                egnn_wave_lds_sync();
                 if (S <= SG_SURVIVORS) {                 // wave-uniform (S >= K)
-                    for (int t = lane; t < S; t += 64) {
-                        const key_t mk = selk[t];
-                        const int mj = selj[t];
-                        int rnk = 0;
-                        for (int u = 0; u < S; ++u) rnk += (selk[u] < mk || (selk[u] == mk && selj[u] < mj)) ? 1 : 0;
-                        if (rnk < K) {
-                            idx_out[ob + rnk] = lo + mj;
-                            rank_out[ob + rnk] = (T)egnn_rank_from_key(mk);
-                        }
-                    }
+                    egnn_knn_write_sorted<T>(selk, selj, S, K, lane, 64, lo, idx_out + ob, rank_out + ob);
                     return;
                 }
-                sg_wave_lds_sync();                      // (the ranking above did not run, but the list is rewritten below)
+                egnn_wave_lds_sync();                      // (the ranking above did not run, but the list is rewritten below)
             }
 
             // ---- radix passes over (key, local index); all control flow is wave-uniform
@@ -205,44 +171,27 @@ __global__ __launch_bounds__(SG_THREADS) void knn_select_segments_kernel(
             while (!all && L < KD + IBP / 8) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) hist[4 * lane + q] = 0;
-                sg_wave_lds_sync();
-                const int kl = L < KD ? L : KD, il = L - kl;             // resolved key / index digits
+                egnn_wave_lds_sync();
                 for (int jl = lane; jl < n; jl += 64) {
                     const key_t kj = key_of(jl);
-                    if (kl > 0 && (kj >> (KB - 8 * kl)) != P) continue;
-                    if (il > 0 && ((uint32_t)jl >> (IBP - 8 * il)) != PJ) continue;
-                    const int dig = L < KD ? (int)((kj >> (KB - 8 * (L + 1))) & 0xff) : (int)(((uint32_t)jl >> (IBP - 8 * (L - KD + 1))) & 0xffu);
-                    atomicAdd(&hist[dig], 1);
+                    if (!egnn_knn_has_prefix(kj, (uint32_t)jl, P, PJ, L, IBP)) continue;
+                    atomicAdd(&hist[egnn_knn_digit(kj, (uint32_t)jl, L, IBP)], 1);
                 }
-                sg_wave_lds_sync();
+                egnn_wave_lds_sync();
                 // the bin holding the need-th candidate (lane l owns bins 4 l .. 4 l + 3)
-                int c4[4], sum = 0;
+                int c4[4];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) { c4[q] = hist[4 * lane + q]; sum += c4[q]; }
-                const int incl = egnn_wave_inclusive_scan(sum);
-                const uint64_t hit = __ballot(incl >= need);
-                if (hit == 0ull) break;                  // (cannot happen: the prefix holds >= need candidates)
-                const int src = __builtin_ctzll(hit);
-                int dig = 0, before = incl - sum, inbin = 0;
-                if (lane == src) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        if (before + c4[q] >= need) { dig = 4 * lane + q; inbin = c4[q]; break; }
-                        before += c4[q];
-                    }
-                }
-                dig = __builtin_amdgcn_readlane(dig, src);
-                before = __builtin_amdgcn_readlane(before, src);
-                inbin = __builtin_amdgcn_readlane(inbin, src);
-                if (L < KD) P = (P << 8) | (key_t)dig;
-                else PJ = (PJ << 8) | (uint32_t)dig;
+                for (int q = 0; q < 4; ++q) c4[q] = hist[4 * lane + q];
+                egnn_knn_bin bin;
+                if (!egnn_knn_find_bin(c4, need, lane, bin)) break;      // (cannot happen: the prefix holds >= need candidates)
+                if (L < KD) P = (P << 8) | (key_t)bin.digit;
+                else PJ = (PJ << 8) | (uint32_t)bin.digit;
                 ++L;
-                need -= before;
-                if (inbin == need) break;                // resolved: the bin is taken whole
+                need -= bin.before;
+                if (bin.in_bin == need) break;           // resolved: the bin is taken whole
             }
 
             // ---- pick: the candidates whose composite prefix is <= the resolved one, in index order
-            const int kl = L < KD ? L : KD, il = L - kl;                 // (kl >= 1 unless `all`)
             int base = 0;
             for (int j0 = 0; j0 < n; j0 += 64) {
                 const int jl = j0 + lane;
@@ -250,35 +199,23 @@ __global__ __launch_bounds__(SG_THREADS) void knn_select_segments_kernel(
                 key_t kj = 0;
                 if (jl < n) {
                     kj = key_of(jl);
-                    take = all;
-                    if (!all) {
-                        const key_t kp = kj >> (KB - 8 * kl);
-                        take = kp < P;
-                        if (kp == P) take = il == 0 || ((uint32_t)jl >> (IBP - 8 * il)) <= PJ;
-                    }
+                    take = all || egnn_knn_take(kj, (uint32_t)jl, P, PJ, L, IBP);        // (L >= 1 unless `all`)
                 }
                 const uint64_t bs = __ballot(take);
                 const int pos = base + __popcll(bs & lt_mask);
                 if (take && pos < Ksel) { selk[pos] = kj; selj[pos] = jl; }
                 base += __popcll(bs);
             }
-            sg_wave_lds_sync();
+            egnn_wave_lds_sync();
             // ---- rank by counting on (key, index)
-            for (int t = lane; t < Ksel; t += 64) {
-                const key_t mk = selk[t];
-                const int mj = selj[t];
-                int rnk = 0;
-                for (int u = 0; u < Ksel; ++u) rnk += (selk[u] < mk || (selk[u] == mk && selj[u] < mj)) ? 1 : 0;
-                idx_out[ob + rnk] = lo + mj;
-                rank_out[ob + rnk] = (T)egnn_rank_from_key(mk);
-            }
+            egnn_knn_write_sorted<T>(selk, selj, Ksel, Ksel, lane, 64, lo, idx_out + ob, rank_out + ob);
         };
-        sg_wave_lds_sync();                              // (the query's coordinates, CDM == 0)
+        egnn_wave_lds_sync();                              // (the query's coordinates, CDM == 0)
         if (inwin) select_row(SgSrc<true>());
         else select_row(SgSrc<false>());
         // ---- empty slots of a graph smaller than K
         for (int k = Ksel + lane; k < K; k += 64) { idx_out[ob + k] = i; rank_out[ob + k] = (T)__builtin_inff(); }
-        sg_wave_lds_sync();                              // the next row reuses the list, the histogram and the query
+        egnn_wave_lds_sync();                              // the next row reuses the list, the histogram and the query
     }
 }
 
@@ -286,11 +223,10 @@ template <typename T>
 int knn_segments_launch(const T* coors, const int64_t* offsets, const int32_t* segment_of, int G, int NT, int K, int C, int max_segment,
                         int32_t* idx_out, T* rank_out, void* stream)
 {
-    if (!coors || !offsets || !segment_of || !idx_out || !rank_out) return EGNN_E_NULLPTR;
-    if (G <= 0 || NT <= 0 || K <= 0 || max_segment <= 0 || max_segment > NT) return EGNN_E_SHAPE;
-    if (C < 1 || C > 64) return EGNN_E_UNSUPPORTED;
-    if (K > NT) return EGNN_E_K_GT_N;
-    if (K > 1024) return EGNN_E_UNSUPPORTED;
+    if (!offsets || !segment_of) return EGNN_E_NULLPTR;
+    // (one batch of NT nodes; the segment table's shape conditions are reported where the batch count's would be)
+    const int rc = egnn_knn_check_args(coors, idx_out, rank_out, (G > 0 && max_segment > 0 && max_segment <= NT) ? 1 : 0, NT, K, C);
+    if (rc != EGNN_OK) return rc;
     const bool any = sizeof(T) == 8 || C > 8;
     const int Lp = K > SG_SURVIVORS ? (K + 1) & ~1 : SG_SURVIVORS;
     const size_t waves = SG_WAVES * sg_wave_bytes<T>(Lp, any ? C : 0);

@@ -13,18 +13,12 @@
 // ranking.  Both are deterministic: ascending value, ties by ascending index -- the tie policy of SURVEY.md §8c(5).
 //
 // Bound: VALU (N compares x 32 bits per row); HBM traffic is only coors in + (idx, rank) out.
-#include "egnn_common.h"
+#include "knn_core.h"
 
 namespace {
 
 __device__ __forceinline__ uint32_t f2key(float f) { return egnn_rank_key(f); }
 __device__ __forceinline__ float key2f(uint32_t k) { return egnn_rank_from_key(k); }
-__device__ __forceinline__ void wave_lds_sync() {
-    // same-wave LDS hand-off: DS operations of one wave execute in issue order; the explicit wait makes the
-    // store -> other-lane load dependency independent of that, the wave barrier pins the compiler's ordering.
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-}
 
 #ifndef EGNN_KNN_BITS
 #define EGNN_KNN_BITS 16
@@ -190,7 +184,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(
             if (k0[c] <= M0) sel0[p0++] = ((uint64_t)k0[c] << 32) | (uint32_t)(c * 64 + lane);
             if (k1[c] <= M1) sel1[p1++] = ((uint64_t)k1[c] << 32) | (uint32_t)(c * 64 + lane);
         }
-        wave_lds_sync();
+        egnn_wave_lds_sync();
         const uint64_t mine0 = lane < S0 ? sel0[lane] : ~0ull;
         const uint64_t mine1 = lane < S1 ? sel1[lane] : ~0ull;
         int rnk0 = 0, rnk1 = 0;
@@ -210,7 +204,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(
             idx_out[ob1 + rnk1] = (int32_t)(uint32_t)(mine1 & 0xFFFFFFFFull);
             rank_out[ob1 + rnk1] = key2f((uint32_t)(mine1 >> 32));
         }
-        wave_lds_sync();
+        egnn_wave_lds_sync();
         return true;
     };
 #endif
@@ -380,7 +374,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(
 #pragma unroll
                 for (int c = 0; c < CPL; ++c)
                     if (key[c] <= M) selbuf[pos++] = ((uint64_t)key[c] << 32) | (uint32_t)(c * 64 + lane);
-                wave_lds_sync();
+                egnn_wave_lds_sync();
                 const uint64_t mine0 = lane < S ? selbuf[lane] : ~0ull;
                 const uint64_t mine1 = lane + 64 < S ? selbuf[lane + 64] : ~0ull;
                 int rnk0 = 0, rnk1 = 0;
@@ -401,7 +395,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(
                     idx_out[obase + rnk1] = (int32_t)(uint32_t)(mine1 & 0xFFFFFFFFull);
                     rank_out[obase + rnk1] = key2f((uint32_t)(mine1 >> 32));
                 }
-                wave_lds_sync();
+                egnn_wave_lds_sync();
                 done = true;
             }
         }
@@ -440,7 +434,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(
                     ((uint64_t)key[c] << 32) | (uint32_t)(c * 64 + lane);
             base += __popcll(bs);
         }
-        wave_lds_sync();
+        egnn_wave_lds_sync();
 
         // ---- sort the K survivors by (value, index): rank by counting
         for (int t = lane; t < K; t += 64) {
@@ -450,132 +444,8 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(
             idx_out[obase + rnk] = (int32_t)(uint32_t)(mine & 0xFFFFFFFFull);
             rank_out[obase + rnk] = key2f((uint32_t)(mine >> 32));
         }
-        wave_lds_sync();
+        egnn_wave_lds_sync();
     }
-}
-
-// ---- large graphs (N beyond what a wave keeps in registers: 8192 nodes with 3-D coordinates, 4096 otherwise).  One WORKGROUP per
-// query row: the row's N ranking keys (the same bit-exact values) live in LDS -- up to 32 768 -- instead of registers; the K-th
-// smallest key by the same 32-step radix descent (per-thread counts over a contiguous slice, wave sums, one cross-wave sum per step),
-// the index-ordered pick among the ties with the K-th value through a block-wide exclusive scan, rank-by-counting on (value, index).
-// Coordinates are read from global memory (a graph's 12 N bytes are L2-resident).  Deterministic, same tie policy; ~10 us per row,
-// rows spread over the chip: a rarely used path (the reference's topk has no size limit, egnn_pytorch.py:258), not a fast one.
-template <int CDM>
-__global__ __launch_bounds__(KNN_THREADS) void knn_select_large_kernel(
-    const float* __restrict__ coors, const uint8_t* __restrict__ mask, const uint8_t* __restrict__ adj,
-    int64_t adj_bstride, int N, int K, int Cdim, int32_t* __restrict__ idx_out, float* __restrict__ rank_out)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint32_t* keys = reinterpret_cast<uint32_t*>(smem);                  // [N]
-    uint64_t* sel = reinterpret_cast<uint64_t*>(smem + ((size_t)N * 4 + 7) / 8 * 8);     // [K]
-    int* red = reinterpret_cast<int*>(sel + K);                          // [2 * KNN_WAVES + 2]
-    const int C = (CDM == 3) ? 3 : Cdim;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int b = blockIdx.y, i = blockIdx.x;
-    const float* cb = coors + (size_t)b * N * C;
-    const uint8_t* mb = mask ? mask + (size_t)b * N : nullptr;
-    const bool mi = mb ? mb[i] != 0 : true;
-    const uint8_t* adjrow = adj ? adj + (size_t)b * adj_bstride + (size_t)i * N : nullptr;
-    const size_t obase = ((size_t)b * N + i) * K;
-    if (!mi && !adjrow) {                                                // a masked row: all keys 1e5, the first K indices (see above)
-        for (int k = tid; k < K; k += KNN_THREADS) { idx_out[obase + k] = k; rank_out[obase + k] = 1e5f; }
-        return;
-    }
-    float ci[CDM];
-#pragma unroll
-    for (int c = 0; c < CDM; ++c) ci[c] = c < C ? cb[(size_t)i * C + c] : 0.f;
-    for (int j = tid; j < N; j += KNN_THREADS) {
-        float rk;
-        if (CDM == 3) {
-            float dx, dy, dz;
-            rk = egnn_sqdist(ci[0], ci[1], ci[2], cb[(size_t)j * 3], cb[(size_t)j * 3 + 1], cb[(size_t)j * 3 + 2], dx, dy, dz);
-        } else {
-            float cj[CDM], rel[CDM];
-#pragma unroll
-            for (int c = 0; c < CDM; ++c) cj[c] = c < C ? cb[(size_t)j * C + c] : 0.f;
-            rk = egnn_sqdist_n<CDM>(ci, cj, C, rel);
-        }
-        keys[j] = f2key(egnn_knn_rank<float>(rk, mi, mb ? mb[j] != 0 : true, adjrow, i, j));       // :240-256
-    }
-    __syncthreads();
-
-    // block-wide sum of a per-thread count (every thread gets it)
-    auto block_sum = [&](int v, int slot) {
-        v = egnn_wave_sum(v);
-        if (lane == 0) red[slot * KNN_WAVES + wave] = v;
-        __syncthreads();
-        int t = 0;
-#pragma unroll
-        for (int w = 0; w < KNN_WAVES; ++w) t += red[slot * KNN_WAVES + w];
-        return t;
-    };
-    // contiguous slice of candidate indices per thread (index order = thread order: the tie pick below relies on it)
-    const int per = (N + KNN_THREADS - 1) / KNN_THREADS;
-    const int j0 = tid * per, j1 = (j0 + per) < N ? (j0 + per) : N;
-
-    // ---- exact K-th smallest key T by bitwise radix descent
-    uint32_t T = 0;
-    int below = 0;
-    for (int bit = 31; bit >= 0; --bit) {
-        const uint32_t want = T >> bit;
-        int cnt = 0;
-        for (int j = j0; j < j1; ++j) cnt += (keys[j] >> bit) == want ? 1 : 0;
-        cnt = block_sum(cnt, bit & 1);                                   // (alternating slots: one barrier per step)
-        if (below + cnt < K) {
-            below += cnt;
-            T |= (1u << bit);
-        }
-    }
-    // ---- pick: everything below T, then the lowest-index `need` candidates equal to T
-    const int need = K - below;
-    int nless = 0, neq = 0;
-    for (int j = j0; j < j1; ++j) {
-        nless += keys[j] < T ? 1 : 0;
-        neq += keys[j] == T ? 1 : 0;
-    }
-    // exclusive scans over the threads (wave scan + cross-wave offsets)
-    __syncthreads();
-    const int il = egnn_wave_inclusive_scan(nless), ie = egnn_wave_inclusive_scan(neq);
-    if (lane == 63) { red[wave] = il; red[KNN_WAVES + wave] = ie; }
-    __syncthreads();
-    int offl = il - nless, offe = ie - neq;
-    for (int w = 0; w < wave; ++w) { offl += red[w]; offe += red[KNN_WAVES + w]; }
-    // selected entries: the `below` smaller ones first (any order), then the ties in index order
-    int pl = offl, pe = offe;
-    for (int j = j0; j < j1; ++j) {
-        const uint32_t kj = keys[j];
-        if (kj < T) sel[pl++] = ((uint64_t)kj << 32) | (uint32_t)j;
-        else if (kj == T) {
-            if (pe < need) sel[below + pe] = ((uint64_t)kj << 32) | (uint32_t)j;
-            ++pe;
-        }
-    }
-    __syncthreads();
-    // ---- sort the K selected by (value, index): rank by counting
-    for (int t = tid; t < K; t += KNN_THREADS) {
-        const uint64_t mine = sel[t];
-        int rnk = 0;
-        for (int u = 0; u < K; ++u) rnk += (sel[u] < mine) ? 1 : 0;
-        idx_out[obase + rnk] = (int32_t)(uint32_t)(mine & 0xFFFFFFFFull);
-        rank_out[obase + rnk] = key2f((uint32_t)(mine >> 32));
-    }
-}
-
-template <int CDM>
-int launch_knn_large(const float* coors, const uint8_t* mask, const uint8_t* adj, int64_t adj_bstride, int B, int N,
-                     int K, int C, int32_t* idx_out, float* rank_out, hipStream_t s)
-{
-    const size_t lds = ((size_t)N * 4 + 7) / 8 * 8 + (size_t)K * 8 + (2 * KNN_WAVES + 2) * sizeof(int);
-    if (lds > 160 * 1024) return EGNN_E_UNSUPPORTED;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(knn_select_large_kernel<CDM>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL((knn_select_large_kernel<CDM>), dim3(N, B), dim3(KNN_THREADS), lds, s, coors, mask, adj, adj_bstride, N, K, C,
-                       idx_out, rank_out);
-    return egnn_launch_status();
 }
 
 __global__ __launch_bounds__(256) void adj_max_degree_kernel(const uint8_t* __restrict__ adj, int64_t rows,
@@ -631,30 +501,25 @@ int launch_knn(const float* coors, const uint8_t* mask, const uint8_t* adj, int6
 
 }  // namespace
 
-// internal (fp64.hip: the one-workgroup-per-row kernel for any coordinate dimension)
-int egnn_knn_select_any_f32(const float* coors, const uint8_t* mask, const uint8_t* adj, int64_t adj_batch_stride, int B, int N, int K,
-                            int coor_dim, int32_t* idx_out, float* rank_out, void* stream);
+// internal (knn_rows.hip: one workgroup per row, the row's keys in LDS; hands on to the streaming kernel where they do not fit)
+int egnn_knn_select_rows_f32(const float* coors, const uint8_t* mask, const uint8_t* adj, int64_t adj_batch_stride, int B, int N, int K,
+                             int coor_dim, int32_t* idx_out, float* rank_out, void* stream);
 
 extern "C" int egnn_knn_select_f32(const float* coors, const uint8_t* mask, const uint8_t* adj,
                                    int64_t adj_batch_stride, int B, int N, int K, int coor_dim, int32_t* idx_out,
                                    float* rank_out, void* stream)
 {
-    if (!coors || !idx_out || !rank_out) return EGNN_E_NULLPTR;
-    if (B <= 0 || N <= 0 || K <= 0) return EGNN_E_SHAPE;
-    if (coor_dim < 1 || coor_dim > 64) return EGNN_E_UNSUPPORTED;
-    // more than 8 coordinates: one workgroup per row, coordinates read from memory, the reference's summation tree for any length
-    if (coor_dim > 8) return egnn_knn_select_any_f32(coors, mask, adj, adj_batch_stride, B, N, K, coor_dim, idx_out, rank_out, stream);
+    const int rc = egnn_knn_check_args(coors, idx_out, rank_out, B, N, K, coor_dim);
+    if (rc != EGNN_OK) return rc;
     const int C = coor_dim;
-    if (K > N) return EGNN_E_K_GT_N;
-    if (K > 1024 || B > 65535) return EGNN_E_UNSUPPORTED;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // candidate keys live in registers (ceil(N / 64) per lane) and the graph's coordinates in LDS: N <= 8192 for 3-D coordinates
-    // (128 keys per lane, 104 KB), N <= 4096 otherwise; larger graphs: one workgroup per row with the keys in LDS, up to 32 768 nodes;
+    // (128 keys per lane, 104 KB), N <= 4096 otherwise, at most 8 coordinates (the reference's summation tree for any length is
+    // egnn_sqdist_any's).  Everything else: one workgroup per row with the keys in LDS (knn_rows.hip), up to 32 768 nodes for C <= 8;
     // beyond that the streaming kernel (knn_stream.hip), which recomputes the keys on every pass
-    if (N > (C == 3 ? 8192 : 4096)) {
-        if (N > 32768) return egnn_knn_select_stream_f32(coors, mask, adj, adj_batch_stride, B, N, K, C, idx_out, rank_out, stream);
-        return C == 3 ? launch_knn_large<3>(coors, mask, adj, adj_batch_stride, B, N, K, C, idx_out, rank_out, s)
-                      : launch_knn_large<8>(coors, mask, adj, adj_batch_stride, B, N, K, C, idx_out, rank_out, s);
+    if (C > 8 || N > (C == 3 ? 8192 : 4096)) {
+        if (C <= 8 && N > 32768) return egnn_knn_select_stream_f32(coors, mask, adj, adj_batch_stride, B, N, K, C, idx_out, rank_out, stream);
+        return egnn_knn_select_rows_f32(coors, mask, adj, adj_batch_stride, B, N, K, C, idx_out, rank_out, stream);
     }
     if (N <= 64) return launch_knn<1>(coors, mask, adj, adj_batch_stride, B, N, K, C, idx_out, rank_out, s);
     if (N <= 128) return launch_knn<2>(coors, mask, adj, adj_batch_stride, B, N, K, C, idx_out, rank_out, s);

@@ -1,9 +1,9 @@
 // Streaming k-NN selection (gfx950): rows whose ranking keys do not fit in LDS -- graphs beyond the one-workgroup-per-row kernels
-// (knn_select.hip: 32 768 nodes with C <= 8; fp64.hip: ~40 000 (float) / ~20 000 (double) nodes).  The reference's topk
+// (knn_rows.hip: 32 768 nodes with C <= 8; otherwise ~40 000 (float) / ~20 000 (double) nodes).  The reference's topk
 // (egnn_pytorch.py:258) has no size limit.
 //
 // No key is stored.  Every pass recomputes a row's N ranking values from the coordinates, the mask and the adjacency row (the same
-// operations as the other selection kernels: egnn_sqdist / egnn_sqdist_n / egnn_sqdist_any and egnn_knn_rank, egnn_common.h); the
+// operations as the other selection kernels: knn_core.h::egnn_knn_key_of); the
 // graph's coordinates stay in L2.  Selection is a radix select over 8-bit digits of the composite (key, index) -- the key's digits
 // first, then the index's -- which is unique per candidate, so the K smallest composites are exactly the top-K with the lowest-index
 // tie policy and no index-ordered scan is needed:
@@ -18,17 +18,13 @@
 // order is the (key, index) order.
 // Instantiations: the adjacency as a byte row or as CSR rows (CSR), every row or only the rows a flag byte names (FL: the rows the cell-grid
 // selection hands over, knn_grid.hip) -- all four combinations; `rowflag` and `col` are separate arguments.
-#include "egnn_common.h"
+#include "knn_core.h"
 
 namespace {
 
 constexpr int KS_THREADS = 256;
 constexpr int KS_RMAX = 16;                 // query rows per workgroup (fewer for large K: the pick lists live in LDS)
 constexpr int KS_HSTRIDE = 257;             // histogram row stride (words): rows' equal bins on different banks
-
-template <typename T> struct KsKey;
-template <> struct KsKey<float> { typedef uint32_t type; static constexpr int V = 8; };
-template <> struct KsKey<double> { typedef uint64_t type; static constexpr int V = 4; };
 
 // CDM: 3 = egnn_sqdist (float, C == 3), 8 = egnn_sqdist_n (float, C <= 8), 0 = egnn_sqdist_any (float C > 8, every double C)
 // FL: only the rows with rowflag[b N + i] != 0 are selected and written (the rows the cell-grid selection hands over, knn_grid.hip); a
@@ -47,9 +43,8 @@ __global__ __launch_bounds__(KS_THREADS) void knn_select_stream_kernel(
     int N, int K, int C, int R, int IBP, int32_t* __restrict__ idx_out, T* __restrict__ rank_out,
     const uint8_t* __restrict__ rowflag, const int32_t* __restrict__ col)
 {
-    typedef typename KsKey<T>::type key_t;
-    constexpr int KB = 8 * (int)sizeof(key_t);           // key bits
-    constexpr int KD = KB / 8;                           // key digits
+    typedef typename egnn_knn_key<T>::type key_t;
+    constexpr int KD = (int)sizeof(key_t);               // key digits
     extern __shared__ __attribute__((aligned(16))) char smem[];
     key_t* pk = reinterpret_cast<key_t*>(smem);                          // [KS_RMAX] resolved key prefix (right-aligned)
     uint32_t* pj = reinterpret_cast<uint32_t*>(pk + KS_RMAX);           // [KS_RMAX] resolved index prefix
@@ -124,23 +119,12 @@ __global__ __launch_bounds__(KS_THREADS) void knn_select_stream_kernel(
     T ci[CR];
 #pragma unroll
     for (int c = 0; c < CR; ++c) ci[c] = (CDM != 0 && c < C && i < N) ? cb[(size_t)i * C + c] : (T)0;
-    const T* qrow = qs + (size_t)r * C;
+    const T* qi = CDM == 0 ? qs + (size_t)r * C : ci;
 
+    const int CJ = CDM == 3 ? 3 : C;                                     // a node's coordinates in memory (a constant where CDM fixes it)
     auto key_of = [&](int j) -> key_t {
-        T d;
-        if constexpr (CDM == 3) {
-            float dx, dy, dz;
-            d = egnn_sqdist(ci[0], ci[1], ci[2], cb[(size_t)j * 3], cb[(size_t)j * 3 + 1], cb[(size_t)j * 3 + 2], dx, dy, dz);
-        } else if constexpr (CDM == 8) {
-            float cj[8], rel[8];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) cj[c] = c < C ? cb[(size_t)j * C + c] : 0.f;
-            d = egnn_sqdist_n<8>(ci, cj, C, rel);
-        } else {
-            d = egnn_sqdist_any<T, KsKey<T>::V>(qrow, cb + (size_t)j * C, C);
-        }
-        if constexpr (CSR) return egnn_rank_key(egnn_knn_rank<T>(d, mi, mb ? mb[j] != 0 : true, csr, i, j));
-        else return egnn_rank_key(egnn_knn_rank<T>(d, mi, mb ? mb[j] != 0 : true, adjrow, i, j));
+        if constexpr (CSR) return egnn_knn_key_of<T, CDM>(qi, cb + (size_t)j * CJ, 1, C, mi, mb, csr, i, j);
+        else return egnn_knn_key_of<T, CDM>(qi, cb + (size_t)j * CJ, 1, C, mi, mb, adjrow, i, j);
     };
     __syncthreads();
 
@@ -150,16 +134,13 @@ __global__ __launch_bounds__(KS_THREADS) void knn_select_stream_kernel(
         const bool mine = state[r] == 0;
         const key_t P = pk[r];
         const uint32_t PJ = pj[r];
-        const int kl = L < KD ? L : KD, il = L - kl;                     // resolved key / index digits
         if (mine) {
             int* h = hist + r * KS_HSTRIDE;
             if constexpr (CSR) egnn_csr_rewind(csr);
             for (int j = s; j < N; j += S) {
                 const key_t kj = key_of(j);
-                if (kl > 0 && (kj >> (KB - 8 * kl)) != P) continue;
-                if (il > 0 && ((uint32_t)j >> (IBP - 8 * il)) != PJ) continue;
-                const int dig = L < KD ? (int)((kj >> (KB - 8 * (L + 1))) & 0xff) : (int)(((uint32_t)j >> (IBP - 8 * (L - KD + 1))) & 0xffu);
-                atomicAdd(&h[dig], 1);
+                if (!egnn_knn_has_prefix(kj, (uint32_t)j, P, PJ, L, IBP)) continue;
+                atomicAdd(&h[egnn_knn_digit(kj, (uint32_t)j, L, IBP)], 1);
             }
         }
         __syncthreads();
@@ -167,31 +148,19 @@ __global__ __launch_bounds__(KS_THREADS) void knn_select_stream_kernel(
         for (int rr = wave; rr < R; rr += KS_THREADS / 64) {
             if (state[rr] != 0) continue;                                // (wave-uniform)
             int* h = hist + rr * KS_HSTRIDE;
-            int c4[4], sum = 0;
+            int c4[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) { c4[q] = h[4 * lane + q]; sum += c4[q]; h[4 * lane + q] = 0; }
-            const int incl = egnn_wave_inclusive_scan(sum);
+            for (int q = 0; q < 4; ++q) { c4[q] = h[4 * lane + q]; h[4 * lane + q] = 0; }
             const int nd = need[rr];
-            const uint64_t hit = __ballot(incl >= nd);
-            const int src = __builtin_ctzll(hit);                        // (the row holds >= nd candidates with its prefix: hit != 0)
-            int dig = 0, before = incl - sum, inbin = 0;
-            if (lane == src) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    if (before + c4[q] >= nd) { dig = 4 * lane + q; inbin = c4[q]; break; }
-                    before += c4[q];
-                }
-            }
-            dig = __builtin_amdgcn_readlane(dig, src);
-            before = __builtin_amdgcn_readlane(before, src);
-            inbin = __builtin_amdgcn_readlane(inbin, src);
+            egnn_knn_bin bin;
+            egnn_knn_find_bin(c4, nd, lane, bin);                        // (found: the row holds >= nd candidates with its prefix)
             if (lane == 0) {
                 const int L0 = lvl[rr];
-                if (L0 < KD) pk[rr] = (pk[rr] << 8) | (key_t)dig;
-                else pj[rr] = (pj[rr] << 8) | (uint32_t)dig;
+                if (L0 < KD) pk[rr] = (pk[rr] << 8) | (key_t)bin.digit;
+                else pj[rr] = (pj[rr] << 8) | (uint32_t)bin.digit;
                 lvl[rr] = L0 + 1;
-                need[rr] = nd - before;
-                if (inbin == nd - before) { state[rr] = 1; atomicSub(active, 1); }
+                need[rr] = nd - bin.before;
+                if (bin.in_bin == nd - bin.before) { state[rr] = 1; atomicSub(active, 1); }
             }
         }
         __syncthreads();
@@ -202,16 +171,12 @@ __global__ __launch_bounds__(KS_THREADS) void knn_select_stream_kernel(
         const int L = lvl[r];
         const key_t P = pk[r];
         const uint32_t PJ = pj[r];
-        const int kl = L < KD ? L : KD, il = L - kl;                     // (kl >= 1: at least one pass)
         key_t* sk = selk + (size_t)r * K;
         int* sj = selj + (size_t)r * K;
         if constexpr (CSR) egnn_csr_rewind(csr);
         for (int j = s; j < N; j += S) {
             const key_t kj = key_of(j);
-            const key_t kp = kj >> (KB - 8 * kl);
-            bool take = kp < P;
-            if (kp == P) take = il == 0 || ((uint32_t)j >> (IBP - 8 * il)) <= PJ;
-            if (take) {
+            if (egnn_knn_take(kj, (uint32_t)j, P, PJ, L, IBP)) {                  // (L >= 1: at least one pass)
                 const int pos = atomicAdd(&cnt[r], 1);
                 if (pos < K) { sk[pos] = kj; sj[pos] = j; }
             }
@@ -226,8 +191,7 @@ __global__ __launch_bounds__(KS_THREADS) void knn_select_stream_kernel(
         const int* sj = selj + (size_t)rr * K;
         const key_t mk = sk[t];
         const int mj = sj[t];
-        int rnk = 0;
-        for (int u = 0; u < K; ++u) rnk += (sk[u] < mk || (sk[u] == mk && sj[u] < mj)) ? 1 : 0;
+        const int rnk = egnn_knn_rank_in(sk, sj, K, mk, mj);
         const size_t ob = ((size_t)b * N + (size_t)blockIdx.x * R + rr) * K;
         idx_out[ob + rnk] = mj;
         rank_out[ob + rnk] = (T)egnn_rank_from_key(mk);
@@ -238,12 +202,9 @@ template <typename T, bool CSR = false>
 int knn_stream_launch(const T* coors, const uint8_t* mask, const typename KsAdj<CSR>::adj_t* adj, int64_t adj_bstride, int B, int N, int K,
                       int C, int32_t* idx_out, T* rank_out, void* stream, const uint8_t* rowflag = nullptr, const int32_t* col = nullptr)
 {
-    if (!coors || !idx_out || !rank_out) return EGNN_E_NULLPTR;
-    if (B <= 0 || N <= 0 || K <= 0) return EGNN_E_SHAPE;
-    if (C < 1 || C > 64) return EGNN_E_UNSUPPORTED;
-    if (K > N) return EGNN_E_K_GT_N;
-    if (K > 1024 || B > 65535) return EGNN_E_UNSUPPORTED;
-    typedef typename KsKey<T>::type key_t;
+    const int rc = egnn_knn_check_args(coors, idx_out, rank_out, B, N, K, C);
+    if (rc != EGNN_OK) return rc;
+    typedef typename egnn_knn_key<T>::type key_t;
     // rows per workgroup: 16, fewer where the R pick lists ((key, index) per entry) would pass 64 KB
     int R = KS_RMAX;
     while (R > 1 && (size_t)R * K * (sizeof(key_t) + 4) > 64 * 1024) R >>= 1;

@@ -560,6 +560,18 @@ class EGNN(nn.Module):
                 _ops.empty(b * n * k, 4, dtype=torch.int32, device=dev) if (_SLOT_PREP and coors.shape[-1] == 3) else None,
                 _ops.knn_grid_workspace(b, n, k, dev) if self._use_grid(coors, adj_mat, k) else None)
 
+    def _knn_route(self, coors, mask, adj_mat, k, out=None, ws=None):
+        """(idx, rank), both (B, N, K), of this call's neighbour selection on the route its inputs decide: a packed batch (B = 1) inside
+        every node's own graph, else the cell grid where `_use_grid` says so, else the all-pairs kernels -- the same list bit for bit on
+        the last two.  out = (idx, rank), ws = the grid's workspace: allocated by the caller (`_select_outputs`), or here when None."""
+        segments = _segments_now.get()
+        if segments is not None:
+            idx, rank = _ops.knn_select_segments(coors[0], segments, k, out=None if out is None else (out[0][0], out[1][0]))
+            return idx[None], rank[None]
+        if self._use_grid(coors, adj_mat, k):                            # (sub-quadratic: `_KNN_GRID_MIN_N`)
+            return _ops.knn_select_grid(coors, mask, k, out=out, ws=ws, adj=adj_mat)
+        return _ops.knn_select(coors, mask, adj_mat, k, out=out)
+
     def _select_neighbors(self, coors, mask, adj_mat, order_hint, k, valid_radius, outs, fork=None):
         """(idx, rank, order, slots) of egnn_pytorch.py:230-260 for fp32 coordinates on the device, K > 0: the K nearest neighbours, the
         Morton order the edge pass schedules by, the per-slot records, written into `outs` (`_select_outputs`).  Neighbour selection
@@ -571,17 +583,9 @@ class EGNN(nn.Module):
         idx_o, rank_o, order_o, slots_o, grid_ws = outs
         mask8 = _ops._u8(mask)                                      # (a view: the caller made the mask contiguous before the fork)
 
-        segments = _segments_now.get()                              # (read here: `select` may run under another stream's context)
-
         def select():
             # (the Morton order launched AHEAD of the selection was measured in round 6: +- 0.3 %, not kept)
-            if segments is not None:                                # a packed batch (B = 1): neighbours inside the node's own graph
-                _ops.knn_select_segments(coors[0], segments, k, out=(idx_o[0], rank_o[0]))
-                idx_, rank_ = idx_o, rank_o
-            elif grid_ws is not None:
-                idx_, rank_ = _ops.knn_select_grid(coors, mask, k, out=(idx_o, rank_o), ws=grid_ws, adj=adj_mat)
-            else:
-                idx_, rank_ = _ops.knn_select(coors, mask, adj_mat, k, out=(idx_o, rank_o))
+            idx_, rank_ = self._knn_route(coors, mask, adj_mat, k, out=(idx_o, rank_o), ws=grid_ws)
             order_ = order_o if order_o is None or order_o is order_hint else _ops.spatial_order(coors, out=order_o, mask8=mask8)
             # the edge pass's setup as one coalesced record per slot instead of a chain of dependent loads
             slots_ = _ops.slot_prep(coors, mask8, idx_, rank_, order_, valid_radius, out=slots_o) if slots_o is not None else None
@@ -839,12 +843,7 @@ class EGNN(nn.Module):
         k, valid_radius = kr
         idx = rank = None
         if self._use_nearest() and k > 0:
-            if _segments_now.get() is not None:                          # a packed batch (B = 1): neighbours inside the node's own graph
-                idx, rank = (t[None] for t in _ops.knn_select_segments(coors[0], _segments_now.get(), k))
-            elif self._use_grid(coors, adj_mat, k):                      # (the same list bit for bit, sub-quadratic: `_KNN_GRID_MIN_N`)
-                idx, rank = _ops.knn_select_grid(coors, mask, k, adj=adj_mat)
-            else:
-                idx, rank = _ops.knn_select(coors, mask, adj_mat, k)
+            idx, rank = self._knn_route(coors, mask, adj_mat, k)
         f32 = lambda t: t.detach().to(dtype).contiguous()                # noqa: E731  (the module's tensors in the compute dtype)
         node_out, coors_out, m_i = feats, coors, None
         u_pre = proj_keep = None                                         # want_u (forward under autograd): u (E, m_dim) and the projection table

@@ -5,7 +5,7 @@ numpy oracle (oracle/egnn_oracle.py: pairwise / inner_sum, build_ranking, topk_s
 reference under the tie policy of SURVEY.md §8c(5) -- ascending value, ties by ascending index -- and the comparison is bit for bit:
 
 1. the four selection kernels (the register kernel with its pair path / two-smallest-keys pruning / hand-over to the radix descent,
-   knn_select_any_kernel, the workgroup-per-row kernel, the streaming kernel), alone and with an adjacency, against the oracle;
+   the workgroup-per-row kernel in its four instantiations, the streaming kernel), alone and with an adjacency, against the oracle;
 2. the Morton order and the destination lists on these inputs;
 3. layers and a network, forward, against the oracle (neighbour lists bit for bit, outputs at the parity bar, the launch paths bit
    identical to each other);
@@ -116,6 +116,9 @@ def _build_geometry(name, dtype):
     if name.startswith("point"):
         n = int(name[5:])
         return _batch([point(n), point(n)], rng, dt), _ragged(n, n - n // 4)
+    if name == "line300_30valid":
+        # fewer valid nodes than K = 40 in every row: the ties at 1e5 straddle K and are picked in index order
+        return _batch([line(300), line(300)], rng, dt), np.broadcast_to(np.arange(300) < 30, (2, 300)).copy()
     if name.startswith("line"):
         n = int(name[4:])
         return _batch([line(n), line(n)], rng, dt), _ragged(n, n - n // 4)
@@ -232,13 +235,14 @@ def test_register_kernel_other_dimensions_against_the_oracle(name):
 
 
 ANY_KERNEL = [("hypercube9", 16, "float32"), ("hypercube9", 32, "float32"), ("hypercube9", 64, "float32"),
-              ("lattice8", 7, "float64"), ("lattice8", 33, "float64"), ("dups16x4", 7, "float64"), ("dups16x4", 33, "float64")]
+              ("lattice8", 7, "float64"), ("lattice8", 33, "float64"), ("dups16x4", 7, "float64"), ("dups16x4", 33, "float64"),
+              ("line300_30valid", 40, "float64")]
 
 
 @pytest.mark.parametrize("name,k,dtype", ANY_KERNEL, ids=[f"knn_select_any_kernel-{n}-k{k}-{d}" for n, k, d in ANY_KERNEL])
 def test_any_kernel_against_the_oracle(name, k, dtype):
-    """csrc/fp64.hip: more than 8 coordinates in float32 (K = 16, 32, 64 end inside a Hamming shell: 10, 46 and 130 would end on one),
-    and float64 coordinates."""
+    """csrc/knn_rows.hip, the instantiations that read through pointers: more than 8 coordinates in float32 (K = 16, 32, 64 end inside
+    a Hamming shell: 10, 46 and 130 would end on one), and float64 coordinates (the last case: 30 valid nodes, K = 40)."""
     _check_selection("knn_select", name, k, dtype)
 
 

@@ -101,20 +101,34 @@ def test_knn_select_rows_decided_by_the_adjacency(n, band, k, use_mask, three_d,
     np.testing.assert_array_equal(ref_idx.astype(np.int32), idx.cpu().numpy())
 
 
+def _check_large_graph_other_dimensions(cdim, n, k, valid, chain, seed):
+    """one graph of n nodes with cdim != 3 coordinates, beyond the 4096 candidates a wave keeps: the first `valid` nodes real (None: all),
+    chain: a band-1 adjacency with the diagonal; bit for bit against the oracle"""
+    from egnn_pytorch_amd import _ops
+    rng = np.random.default_rng(seed)
+    coors = rng.standard_normal((1, n, cdim)).astype(np.float32)
+    mask = None if valid is None else (np.arange(n)[None, :] < valid)
+    i = np.arange(n)
+    adj = (np.abs(i[:, None] - i[None, :]) <= 1) if chain else None
+    _, dist = O.pairwise(coors)
+    ranking, _ = O.build_ranking(dist, mask, adj)
+    ref_val, ref_idx = O.topk_smallest(ranking, k)
+    idx, rank = _ops.knn_select(_dev(coors), _dev(mask), _dev(adj), k)
+    np.testing.assert_array_equal(ref_val.view(np.uint32), rank.cpu().numpy().view(np.uint32))
+    np.testing.assert_array_equal(ref_idx.astype(np.int32), idx.cpu().numpy())
+
+
 def test_knn_select_large_graph_other_coordinate_dimensions():
     """N = 4500 with 5-D coordinates (a wave keeps at most 4096 such candidates): the workgroup-per-row kernel with the reference's
     summation order for C = 5 (s0, s4, s1, s2, s3)."""
-    from egnn_pytorch_amd import _ops
-    rng = np.random.default_rng(45)
-    n, k = 4500, 24
-    coors = rng.standard_normal((1, n, 5)).astype(np.float32)
-    mask = (np.arange(n)[None, :] < 4100)
-    _, dist = O.pairwise(coors)
-    ranking, _ = O.build_ranking(dist, mask, None)
-    ref_val, ref_idx = O.topk_smallest(ranking, k)
-    idx, rank = _ops.knn_select(_dev(coors), _dev(mask), None, k)
-    np.testing.assert_array_equal(ref_val.view(np.uint32), rank.cpu().numpy().view(np.uint32))
-    np.testing.assert_array_equal(ref_idx.astype(np.int32), idx.cpu().numpy())
+    _check_large_graph_other_dimensions(5, 4500, 24, 4100, False, seed=45)
+
+
+@pytest.mark.parametrize("cdim,k,valid,chain", [(8, 24, 3900, False), (2, 8, None, True)], ids=["c8-k24-prefix_mask", "c2-k8-chain_adjacency"])
+def test_knn_select_large_graph_left_to_right_dimensions(cdim, k, valid, chain):
+    """N = 4100, the smallest size class of knn_select_rows_kernel<float, 8> (csrc/knn_rows.hip): the left-to-right summation order of
+    C = 8 and C = 2 (C = 5 above takes the other order of egnn_sqdist_n), and an adjacency row entering that kernel's keys."""
+    _check_large_graph_other_dimensions(cdim, 4100, k, valid, chain, seed=4100 + cdim)
 
 
 @pytest.mark.parametrize("cdim,n,k,use_mask,use_adj", [(9, 200, 16, True, False), (11, 64, 8, True, True), (16, 300, 32, False, False),

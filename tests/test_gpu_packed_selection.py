@@ -13,7 +13,9 @@ budget (every segment of these sizes is read from the workgroup's LDS window) an
 
 A second batch holds two coincident segments of 200 and 300 nodes: every key of a row is equal, so with K <= 64 more candidates survive
 the pruning bound than its list of 128 holds and the row falls back to the radix passes, which then have to resolve the K-th candidate
-on the index digits alone -- one digit for 200 nodes, two for 300."""
+on the index digits alone -- one digit for 200 nodes, two for 300.
+
+Every comparison also checks the packed lists against the numpy oracle directly (`_check_oracle`)."""
 import functools
 
 import numpy as np
@@ -93,6 +95,26 @@ def _check(seg, k, idx, rank, pidx, prank, what):
         assert bool((_bits(rank[lo:lo + n, m:]) == INF_BITS[rank.dtype]).all()), (what, "graph", g, "size", n, "empty slots' ranks")
 
 
+def _check_oracle(seg, x, k, idx, rank, what):
+    """The filled slots against the numpy oracle, graph by graph (oracle/egnn_oracle.py: pairwise, build_ranking, topk_smallest with its
+    stable sort).  The segmented kernel and the padded yardstick share their arithmetic (csrc/knn_core.h) and would go wrong together, so
+    the packed lists are pinned to the oracle on their own."""
+    from oracle import egnn_oracle as O
+    xc, ic, rc = x.cpu().numpy(), idx.cpu().numpy(), rank.cpu().numpy()
+    bits = np.uint32 if rc.dtype == np.float32 else np.uint64
+    off = seg.host_offsets
+    for g, n in enumerate(seg.sizes):
+        if n == 0:
+            continue
+        lo, m = off[g], min(k, n)
+        _, dist = O.pairwise(xc[None, lo:lo + n])
+        ranking, _ = O.build_ranking(dist, None, None)
+        ref_val, ref_idx = O.topk_smallest(ranking, m)
+        np.testing.assert_array_equal(ref_idx[0].astype(np.int32), ic[lo:lo + n, :m] - lo, err_msg=f"{what} graph {g} size {n}")
+        np.testing.assert_array_equal(np.ascontiguousarray(ref_val[0]).view(bits), np.ascontiguousarray(rc[lo:lo + n, :m]).view(bits),
+                                      err_msg=f"{what} graph {g} size {n}")
+
+
 def _compare(cdim, dtype, geometry, k, sizes=None):
     sizes = _sizes(k) if sizes is None else sizes
     seg, x, _, _ = _batch(sizes, cdim, dtype, geometry)
@@ -101,6 +123,7 @@ def _compare(cdim, dtype, geometry, k, sizes=None):
     for lds_nodes in (None, SWITCH):
         idx, rank = _packed(seg, x, k, lds_nodes)
         _check(seg, k, idx, rank, pidx, prank, (geometry, cdim, dtype, k, lds_nodes))
+        _check_oracle(seg, x, k, idx, rank, (geometry, cdim, dtype, k, lds_nodes))
 
 
 @pytest.mark.parametrize("k", KS)
