@@ -762,11 +762,15 @@ class PackedHL:
 def split_f16(x2d):
     """fp32 (rows, cols) -> packed fp16 (hi, lo) pair for egnn_linear_hl_f32 -- egnn_split_f16."""
     rows, cols = x2d.shape
+    # a view of rows of a wider matrix goes in by its row stride; any other layout (transposed, expanded, off a 16-byte boundary) as a copy
+    ldx = x2d.stride(0) if rows > 1 else cols
+    if x2d.stride(1) != 1 or ldx < cols or x2d.data_ptr() % 16 or (ldx != cols and ldx % 4):
+        x2d, ldx = aligned(x2d.contiguous()), cols
     kp = _kpad(cols)
     hi = _packed_empty(rows, kp, x2d.device)
     lo = _packed_empty(rows, kp, x2d.device)
     with _timed("split_f16"):
-        rc = _abi.load().egnn_split_f16(_ptr(x2d), cols, rows, cols, _ptr(hi), _ptr(lo), kp, _status_ptr(x2d.device),
+        rc = _abi.load().egnn_split_f16(_ptr(x2d), ldx, rows, cols, _ptr(hi), _ptr(lo), kp, _status_ptr(x2d.device),
                                         _stream())
     _abi.check(rc, "egnn_split_f16")
     return PackedHL(hi, lo, rows, kp)
@@ -1016,6 +1020,7 @@ def node_prep_hl(feats2d, m_i, gamma, beta, eps, m_dim, with_raw=False):
     zero (the edge pass writes them in place).  with_raw: also return feats itself as a packed pair (the projection's
     A operand), produced in the same pass."""
     rows, dim = feats2d.shape
+    feats2d, m_i = aligned(feats2d), aligned(m_i)            # (the entry reads rows of `dim` floats: a strided view goes in as a copy)
     kp = _kpad(dim + m_dim)
     hi = _packed_empty(rows, kp, feats2d.device)
     lo = _packed_empty(rows, kp, feats2d.device)

@@ -596,10 +596,10 @@ extern "C" int egnn_edge_tail_bwd_f32(const egnn_edge_tail_args* args, void* str
     const int64_t E = (int64_t)a.B * a.N * a.K;
     const int64_t blocks = (E + 255) / 256;
     if (blocks >= ((int64_t)1 << 31)) return EGNN_E_SHAPE;
-    if (a.amax_gu && hipMemsetAsync(a.amax_gu, 0, sizeof(uint32_t), static_cast<hipStream_t>(stream)) != hipSuccess) return (int)hipGetLastError();
     // (EGNN_TAIL_SCALAR=1: the reduce variant with coors_mlp as per-lane FMAs, for A/B and debugging)
     static const bool scalar_tail = [] { const char* v = getenv("EGNN_TAIL_SCALAR"); return v && v[0] == '1'; }();
-    if (a.drop_thr && (!a.part || scalar_tail)) return EGNN_E_UNSUPPORTED;       // (dropout: the matrix-core variant only)
+    if (a.drop_thr && (!a.part || scalar_tail)) return EGNN_E_UNSUPPORTED;       // (dropout: the matrix-core variant only; refused before anything is enqueued)
+    if (a.amax_gu && hipMemsetAsync(a.amax_gu, 0, sizeof(uint32_t), static_cast<hipStream_t>(stream)) != hipSuccess) return (int)hipGetLastError();
     if (a.part && !scalar_tail && a.drop_thr) hipLaunchKernelGGL(edge_tail_mfma_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     else if (a.part && !scalar_tail) hipLaunchKernelGGL(edge_tail_mfma_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     else if (a.part) hipLaunchKernelGGL(edge_tail_bwd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);

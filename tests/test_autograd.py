@@ -403,17 +403,17 @@ def test_split_k_transposed_product_equals_plain_product():
         torch.testing.assert_close(u, v)
 
 
-def _tail_case(kw, use_mask, dense, dtype, device, n=9, b=2):
+def _tail_case(kw, use_mask, dense, dtype, device, n=9, b=2, seed=0):
     """Inputs of the per-edge tail for one configuration + what autograd of `layer_tail` says (tests below)."""
     from egnn_pytorch_amd import EGNN, autograd as A
-    torch.manual_seed(0)
+    torch.manual_seed(seed)
     layer = EGNN(**kw).to(device=device, dtype=dtype)
     with torch.no_grad():
         for nme, p in layer.named_parameters():
             p.mul_(8.0 if nme.startswith("edge_gate") else 40.0)      # (the gate: large enough to matter, not saturated everywhere)
     m = layer.m_dim
     k = n if dense else kw["num_nearest_neighbors"]
-    g = torch.Generator().manual_seed(1)
+    g = torch.Generator().manual_seed(1 + seed)
     rnd = lambda *shape: torch.randn(*shape, dtype=torch.float64, generator=g).to(device=device, dtype=dtype)
     feats, coors = rnd(b, n, kw["dim"]), rnd(b, n, 3)
     idx = None if dense else torch.randint(0, n, (b, n, k), generator=g).to(device)
@@ -460,6 +460,21 @@ TAIL_CASES = [(dict(dim=8, num_nearest_neighbors=5), False, False),
               (dict(dim=8, m_dim=12, soft_edges=True, m_pool_method="mean"), False, True)]
 
 
+def _tail_gpu_seed(kw):
+    """The seed of a case at the device tests' shape (n = 40, b = 3).  Seed 0 leaves the clamp-0.6 case with every unmasked edge
+    clamped at -0.6 there: d/d w = 0 everywhere, and the coors_mlp gradients would be compared as 0 == 0."""
+    return 43 if kw.get("coor_weights_clamp_value") == 0.6 else 0
+
+
+def _assert_tail_case_is_active(kw, want, pm):
+    """(the clamp leaves some weights active) -- at the shape the kernels are run at: d/d coors_mlp is not identically zero, and where a
+    clamp acts, unmasked edges sit on both sides of it"""
+    assert float((want["g_w"][None, :] @ want["a3"]).abs().max()) > 0 and float(want["g_hid"].abs().max()) > 0
+    if kw.get("coor_weights_clamp_value") == 0.6:
+        live = want["g_w"][pm.reshape(-1)] if pm is not None else want["g_w"]
+        assert bool((live == 0).any()) and bool((live != 0).any())
+
+
 def _tail_param_grads(r):
     return {"coors_mlp.0.weight": r["g_hid"].t() @ r["m"], "coors_mlp.0.bias": r["g_hid"].sum(0),
             "coors_mlp.3.weight": r["g_w"][None, :] @ r["a3"], "coors_mlp.3.bias": r["g_w"].sum()[None],
@@ -486,10 +501,11 @@ def test_closed_form_tail_backward_equals_autograd(kw, use_mask, dense):
 def test_tail_kernel_matches_closed_form(kw, use_mask, dense):
     """egnn_edge_tail_bwd_f32 (one edge per lane) against its torch specification evaluated in float64 on the same inputs."""
     from egnn_pytorch_amd import _ops, autograd as A
-    layer, u, coors, idx, pm, gc, g_msum, _ = _tail_case(kw, use_mask, dense, torch.float32, "cuda", n=40, b=3)
+    layer, u, coors, idx, pm, gc, g_msum, _ = _tail_case(kw, use_mask, dense, torch.float32, "cuda", n=40, b=3, seed=_tail_gpu_seed(kw))
     b, n, k, m = u.shape
     layer64 = __import__("copy").deepcopy(layer).double()
     want = A.tail_edge_backward(layer64, u.double(), coors.double(), idx, pm, gc.double(), g_msum.double())
+    _assert_tail_case_is_active(kw, want, pm)
     e = b * n * k
     u16 = torch.zeros(b, n, k, 16, device="cuda"); u16[..., :m] = u
     gm16 = torch.zeros(b, n, 16, device="cuda"); gm16[..., :m] = g_msum
@@ -533,10 +549,11 @@ def test_tail_kernel_reduce_mode_and_pool_match_closed_form(kw, use_mask, dense)
     against the float64 specification: gU / g_rel as in the plain mode, the summed terms against the spec's tall products, the
     by-products rel / dist, two runs bit-identical; and egnn_edge_pool_f32 against the masked, gated message sum."""
     from egnn_pytorch_amd import _ops, autograd as A
-    layer, u, coors, idx, pm, gc, g_msum, _ = _tail_case(kw, use_mask, dense, torch.float32, "cuda", n=40, b=3)
+    layer, u, coors, idx, pm, gc, g_msum, _ = _tail_case(kw, use_mask, dense, torch.float32, "cuda", n=40, b=3, seed=_tail_gpu_seed(kw))
     b, n, k, m = u.shape
     layer64 = __import__("copy").deepcopy(layer).double()
     want = A.tail_edge_backward(layer64, u.double(), coors.double(), idx, pm, gc.double(), g_msum.double())
+    _assert_tail_case_is_active(kw, want, pm)
     e = b * n * k
     u16 = torch.zeros(b, n, k, 16, device="cuda"); u16[..., :m] = u
     gm16 = torch.zeros(b, n, 16, device="cuda"); gm16[..., :m] = g_msum
