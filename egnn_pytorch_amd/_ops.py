@@ -1581,51 +1581,35 @@ def edge_pool(u16, gate, pair_mask, b, n, k):
     return out
 
 
+# The `sums` row of `edge_tail_bwd(reduce=True)`: the columns of one wave's row of `part` (csrc/edge_tail.hip: PART_*), of
+# TAIL_PART_FLOATS = egnn_edge_tail_part_floats() floats -- what follows the last slice is zero padding.
+TAIL_PART_FLOATS = 1192
+TAIL_SUMS = {
+    "W3": slice(0, 1024),            # d/d coors_mlp.0.weight, (64, 16) zero padded
+    "b3": slice(1024, 1088),         # d/d coors_mlp.0.bias
+    "W4": slice(1088, 1152),         # d/d coors_mlp.3.weight
+    "gU": slice(1152, 1168),         # column sums of gU = d/d edge_mlp's last bias
+    "gate_w": slice(1168, 1184),     # d/d edge_gate.0.weight
+    "b4": slice(1184, 1185),         # d/d coors_mlp.3.bias
+    "scale": slice(1185, 1186),      # d/d CoorsNorm.scale
+    "gate_b": slice(1186, 1187),     # d/d edge_gate.0.bias
+}
+
+
 def edge_tail_bwd(u16, coors, idx32, pair_mask, g_coors_out, g_msum16, w3p, b3p, w4p, b4, scale, eps, clamp, b, n, k, gate=None,
                   reduce=False, want_rel=False, drop=None, eid0=0):
     """egnn_edge_tail_bwd_f32 (include/egnn_hip.h): the per-edge closed-form backward behind edge_mlp's second Linear.
     Returns (gU (E, 16), g_rel (E, 4), g_hid (E, 64), a3 (E, 64), g_w (E,), g_scale (E,) or None); with gate = (gate_w (16) zero
     padded, gate_b (1)) -- soft_edges -- a seventh element g_gate (E,) = d loss / d (gate pre-activation).
-    reduce: the kernel sums the parameter gradients' per-edge terms itself -- returns (gU, g_rel, sums (1192,), rel (E, 4) or None,
-    dist (E,) or None, bits of max |gU| (1-element int32 tensor)): sums = [d/d W3 (64 x 16) | d/d b3 (64) | d/d W4 (64) | column sums of gU (16) | d/d gate_w (16) | d/d b4 |
-    d/d CoorsNorm.scale | d/d gate_b | 0...]; want_rel: also x_i - x_j and |x_i - x_j|^2 per edge."""
+    reduce: the kernel sums the parameter gradients' per-edge terms itself -- returns (gU, g_rel, sums (TAIL_PART_FLOATS,), rel (E, 4)
+    or None, dist (E,) or None, bits of max |gU| (1-element int32 tensor)), sums laid out as TAIL_SUMS says; want_rel: also x_i - x_j
+    and |x_i - x_j|^2 per edge."""
     dev = u16.device
     e = b * n * k
     f32 = dict(dtype=torch.float32, device=dev)
+    lib = _abi.load()
     gu = empty(e, 16, **f32)
     g_rel = empty(e, 4, **f32)
-    if reduce:
-        lib = _abi.load()
-        pf = lib.egnn_edge_tail_part_floats()
-        n_waves = (e + 255) // 256 * 4
-        part = empty(n_waves, pf, **f32)
-        a = _abi.EdgeTailArgs()
-        a.B, a.N, a.K, a.norm_coors = b, n, k, int(scale is not None)
-        a.clamp = -1.0 if clamp is None else float(clamp)
-        a.eps = float(eps)
-        a.u, a.coors, a.idx, a.pair_mask = u16.data_ptr(), coors.data_ptr(), _ptr(idx32), _ptr(pair_mask)
-        a.g_coors_out, a.g_msum = g_coors_out.data_ptr(), g_msum16.data_ptr()
-        a.W3, a.b3, a.W4, a.b4, a.scale = w3p.data_ptr(), b3p.data_ptr(), w4p.data_ptr(), b4.data_ptr(), _ptr(scale)
-        a.gU, a.g_rel, a.part = gu.data_ptr(), g_rel.data_ptr(), part.data_ptr()
-        gu_bits = torch.empty(1, dtype=torch.int32, device=dev)
-        a.amax_gu = gu_bits.data_ptr()
-        if drop is not None:                                  # training-mode dropout in coors_mlp: the forward's hash mask (p, seed), edges numbered from eid0
-            from . import _dropout
-            a.drop_thr, a.drop_seed, a.drop_inv_keep, a.drop_eid0 = _dropout.threshold(drop[0]), int(drop[1]), _dropout.inv_keep(drop[0]), int(eid0)
-        if gate is not None:
-            a.gate_w, a.gate_b = gate[0].data_ptr(), gate[1].data_ptr()
-        rel = dist = None
-        if want_rel:
-            rel, dist = empty(e, 4, **f32), empty(e, **f32)
-            a.rel_out, a.dist_out = rel.data_ptr(), dist.data_ptr()
-        with _timed("edge_tail_bwd"):
-            rc = lib.egnn_edge_tail_bwd_f32(byref(a), _stream())
-        _abi.check(rc, "egnn_edge_tail_bwd_f32")
-        return gu, g_rel, sum_rows(part), rel, dist, gu_bits
-    g_hid = empty(e, 64, **f32)
-    a3 = empty(e, 64, **f32)
-    g_w = empty(e, **f32)
-    g_scale = empty(e, **f32) if scale is not None else None
     a = _abi.EdgeTailArgs()
     a.B, a.N, a.K, a.norm_coors = b, n, k, int(scale is not None)
     a.clamp = -1.0 if clamp is None else float(clamp)
@@ -1633,17 +1617,33 @@ def edge_tail_bwd(u16, coors, idx32, pair_mask, g_coors_out, g_msum16, w3p, b3p,
     a.u, a.coors, a.idx, a.pair_mask = u16.data_ptr(), coors.data_ptr(), _ptr(idx32), _ptr(pair_mask)
     a.g_coors_out, a.g_msum = g_coors_out.data_ptr(), g_msum16.data_ptr()
     a.W3, a.b3, a.W4, a.b4, a.scale = w3p.data_ptr(), b3p.data_ptr(), w4p.data_ptr(), b4.data_ptr(), _ptr(scale)
-    a.gU, a.g_rel, a.g_hid, a.a3, a.g_w, a.g_scale = gu.data_ptr(), g_rel.data_ptr(), g_hid.data_ptr(), a3.data_ptr(), g_w.data_ptr(), _ptr(g_scale)
-    g_gate = None
+    a.gU, a.g_rel = gu.data_ptr(), g_rel.data_ptr()
     if gate is not None:
-        g_gate = empty(e, **f32)
-        a.gate_w, a.gate_b, a.g_gate = gate[0].data_ptr(), gate[1].data_ptr(), g_gate.data_ptr()
+        a.gate_w, a.gate_b = gate[0].data_ptr(), gate[1].data_ptr()
+    if reduce:
+        pf = lib.egnn_edge_tail_part_floats()
+        assert pf == TAIL_PART_FLOATS, pf
+        part = empty((e + 255) // 256 * 4, pf, **f32)           # one row per wave of 64 edges
+        gu_bits = torch.empty(1, dtype=torch.int32, device=dev)
+        a.part, a.amax_gu = part.data_ptr(), gu_bits.data_ptr()
+        if drop is not None:                                  # training-mode dropout in coors_mlp: the forward's hash mask (p, seed), edges numbered from eid0
+            from . import _dropout
+            a.drop_thr, a.drop_seed, a.drop_inv_keep, a.drop_eid0 = _dropout.threshold(drop[0]), int(drop[1]), _dropout.inv_keep(drop[0]), int(eid0)
+        rel = dist = None
+        if want_rel:
+            rel, dist = empty(e, 4, **f32), empty(e, **f32)
+            a.rel_out, a.dist_out = rel.data_ptr(), dist.data_ptr()
+    else:
+        g_hid, a3, g_w = empty(e, 64, **f32), empty(e, 64, **f32), empty(e, **f32)
+        g_scale = empty(e, **f32) if scale is not None else None
+        g_gate = empty(e, **f32) if gate is not None else None
+        a.g_hid, a.a3, a.g_w, a.g_scale, a.g_gate = g_hid.data_ptr(), a3.data_ptr(), g_w.data_ptr(), _ptr(g_scale), _ptr(g_gate)
     with _timed("edge_tail_bwd"):
-        rc = _abi.load().egnn_edge_tail_bwd_f32(byref(a), _stream())
+        rc = lib.egnn_edge_tail_bwd_f32(byref(a), _stream())
     _abi.check(rc, "egnn_edge_tail_bwd_f32")
-    if gate is not None:
-        return gu, g_rel, g_hid, a3, g_w, g_scale, g_gate
-    return gu, g_rel, g_hid, a3, g_w, g_scale
+    if reduce:
+        return gu, g_rel, sum_rows(part), rel, dist, gu_bits
+    return (gu, g_rel, g_hid, a3, g_w, g_scale) + (() if gate is None else (g_gate,))
 
 
 # rounds (of 128 entries) one workgroup of egnn_edge_bwd_pass_f32 streams through its column chunk: short enough that the

@@ -9,10 +9,13 @@ Backward, three paths:
   `_backward_native` -- fp32 (half / bfloat16 modules through an fp32 shadow), every shape the fused forward kernels cover (m_dim <= 64,
            coordinate dimension 1 .. 8, up to 16 per-edge scalars, with or without training-mode dropout):
              * behind u: node_norm / node_mlp on the split-f16 GEMMs (`_node_mlp_backward`), the per-edge chain (second SiLU, gate, masks,
-               coors_mlp, CoorsNorm, clamp, coordinate update, pooling) in closed form -- egnn_edge_tail_bwd_f32 (csrc/edge_tail.hip, matrix
-               cores) for m_dim <= 16 and 3-D coordinates, egnn_edge_tail_exact_bwd_f32 (csrc/edge_exact_bwd.hip, one thread per edge) for
-               wider heads / other coordinate dimensions; `tail_edge_backward` is their specification (autograd on E x m tensors,
-               `layer_tail`, only on the CPU and behind EGNN_TAIL_GENERIC=0)  ->  gU, d/d (x_i - x_j) and those parameters' gradients;
+               coors_mlp, CoorsNorm, clamp, coordinate update, pooling) on the route `_behind_u_route` names -- `_behind_u_standard`:
+               egnn_edge_tail_bwd_f32 (csrc/edge_tail.hip, matrix cores) for m_dim <= 16 and 3-D coordinates; `_behind_u_closed`:
+               egnn_edge_tail_exact_bwd_f32 (csrc/edge_exact_bwd.hip, one thread per edge) for wider heads / other coordinate
+               dimensions; `tail_edge_backward` is their specification; `_behind_u_autograd`: autograd on E x m tensors (`layer_tail`),
+               host tensors only  ->  gU, d/d (x_i - x_j) and those parameters' gradients.  `_backward_exact` takes the same routes
+               (closed, or autograd beyond 64 channels).  The switches EGNN_BWD_TAIL_KERNEL, EGNN_BWD_TAIL_REDUCE, EGNN_TAIL_GENERIC and
+               EGNN_BWD_DROP_NATIVE are retired (DESIGN.md section 10);
              * the E x H work -- z = P_i + P_j + W_s s, a = SiLU(z), dz = (W2^T gU) SiLU'(z) and their contractions -- on
                egnn_edge_bwd_pass_f32 (csrc/edge_bwd.hip; `_edge_contract_fused`): one pass over the edges grouped by source node
                (d/d P_i, d/d W_s, d/d scalars) and one over the edges sorted by destination (d/d P_j, d/d W_2), everything recomputed
@@ -20,8 +23,8 @@ Backward, three paths:
              * the node-level products -- d/d feats, d/d edge_mlp.0, node_mlp -- on the forward's split-f16 GEMM (`_ops.grad_nn / grad_tn`).
   `_backward_exact` (round 5) -- the layers whose forward runs on the plain kernels (csrc/edge_exact.hip): float64 modules (the reference's
            own training recipe, denoise_sparse.py:11, 23-32), calls answered by the wide-range path (values beyond the split-fp16 range),
-           more than 16 per-edge scalars / 8 coordinates / 64 message channels.  The per-edge tail through autograd on E x m tensors,
-           the E x H work on egnn_edge_exact_bwd_f32 / _f64 + egnn_edge_exact_node_sums_* (csrc/edge_exact_bwd.hip), every contraction on
+           more than 16 per-edge scalars / 8 coordinates / 64 message channels.  The per-edge tail in closed form (through autograd on
+           E x m tensors beyond 64 channels), the E x H work on egnn_edge_exact_bwd_f32 / _f64 + egnn_edge_exact_node_sums_* (csrc/edge_exact_bwd.hip), every contraction on
            the exact GEMMs (egnn_linear_f32 / egnn_linear_f64), in the arithmetic of the forward.
   `_backward_recompute` -- what is left: more per-edge scalars than the exact backward keeps in LDS (80 in fp32, 40 in float64), EGNN_NATIVE_BACKWARD=0 /
            EGNN_NATIVE_BACKWARD_EXACT=0, CPU tensors (the tests); also the native paths' reference in the tests.  The whole layer
@@ -38,6 +41,7 @@ either).  It is also what the CPU tests compare with the reference, independentl
 from __future__ import annotations
 
 import os
+from typing import Any, NamedTuple
 
 import torch
 from torch import nn
@@ -49,11 +53,8 @@ _NATIVE_MODE = os.environ.get("EGNN_NATIVE_BACKWARD", "1")
 _NATIVE = _NATIVE_MODE != "0"
 # which pass of the fused backward carries d/d W_2: "dest" (default), "both" = the by-source pass carries everything (tuning knob)
 _FUSED_SPLIT = os.environ.get("EGNN_BWD_SPLIT", "dest")
-_TAIL_KERNEL = os.environ.get("EGNN_BWD_TAIL_KERNEL", "1") != "0"      # 0: the per-edge chain behind u through autograd
 _GRAD_GEMM = os.environ.get("EGNN_BWD_GRAD_GEMM", "1") != "0"          # 0: the node-level gradient products as fp32 library GEMMs
-_TAIL_REDUCE = os.environ.get("EGNN_BWD_TAIL_REDUCE", "1") != "0"      # 0: the tail kernel writes its E x 64 factors out for library reductions
 _NATIVE_EXACT = os.environ.get("EGNN_NATIVE_BACKWARD_EXACT", "1") != "0"   # 0: float64 / wide-range / wide-shape layers on the recompute path
-_TAIL_GENERIC = os.environ.get("EGNN_TAIL_GENERIC", "1") != "0"        # 0: the per-edge chain of wide heads / other coordinate dimensions / the plain path through autograd
 _EXACT_BWD_BYTES = int(float(os.environ.get("EGNN_EXACT_BWD_GB", "2")) * (1 << 30))   # budget of the a^T / dz^T tables per chunk of graphs
 _KEEP_PROJ = os.environ.get("EGNN_BWD_KEEP_PROJ", "1") != "0"          # 0: the backward recomputes the P_i | P_j table (B N x 2 Hp fp32 less to keep)
 _FUSED_MAX_GRAPHS = 0                 # tests: force the chunking over graphs that very large batches need (0 = by size only)
@@ -686,9 +687,35 @@ def _dropout_native_ok(layer):
     tuning switches that take pieces of the native backward away send the masked layer to the recompute path."""
     # (round 6: layers without coors_mlp / node_mlp -- update_coors=False / update_feats=False -- take the generic tail kernel, which
     # skips the absent module and its mask site; odd `dim`: egnn_silu_bwd_drop_f32 steps its (row, column) pair per element)
-    return (_TAIL_KERNEL and _TAIL_REDUCE and _GRAD_GEMM and _FUSED_SPLIT == "dest" and _TAIL_GENERIC
-            and 2 * layer.fourier_features + 1 + layer.edge_dim <= 16 and layer.m_dim <= 64
-            and os.environ.get("EGNN_TAIL_SCALAR", "0") != "1" and os.environ.get("EGNN_BWD_DROP_NATIVE", "1") != "0")
+    # (behind u: one of the two kernel routes -- with the gradient GEMMs on, the rule does not depend on the coordinate dimension)
+    return (_GRAD_GEMM and _FUSED_SPLIT == "dest" and _behind_u_route(layer, layer.m_dim, 3, True, True) != ROUTE_AUTOGRAD
+            and 2 * layer.fourier_features + 1 + layer.edge_dim <= 16 and os.environ.get("EGNN_TAIL_SCALAR", "0") != "1")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Step 1 of `_backward_native` / `_backward_exact`, "behind u": everything downstream of edge_mlp's second Linear -- the pooled messages,
+# node_norm and node_mlp, and the per-edge chain (second SiLU, gate, pair mask, coors_mlp, CoorsNorm, clamp, coordinate update).
+# One rule says which of three routes a chunk of graphs takes (`_behind_u_route`), one function per route does it
+# (`_behind_u_standard` / `_behind_u_closed` / `_behind_u_autograd`) and hands a `_BehindU` record to steps 2 and 3.
+ROUTE_STANDARD = "standard"       # egnn_edge_tail_bwd_f32 (csrc/edge_tail.hip): pools, differentiates and sums its parameter gradients
+ROUTE_CLOSED = "closed"           # egnn_edge_tail_exact_bwd_* (csrc/edge_exact_bwd.hip), parameter gradients on the exact GEMMs
+ROUTE_AUTOGRAD = "autograd"       # `layer_tail` on E x m tensors, differentiated by autograd
+
+
+def _behind_u_route(layer, m, cdim, on_device, native):
+    """The route of step 1 for a layer of m message channels and cdim coordinates; on_device: the tensors are on the GPU; native:
+    `_backward_native` asks (else `_backward_exact`).
+      standard -- m <= 16, coors_mlp hidden width <= 64, 3-D coordinates, coors_mlp and node_mlp present; native only.  Also what host
+                  tensors take (the tests, with `_ops.edge_tail_bwd` emulated): there without the kernel's own reductions;
+      closed   -- m <= 64; on the native path only for device tensors (node_mlp runs on the split-f16 gradient GEMMs there, so the
+                  knob that takes those away, EGNN_BWD_GRAD_GEMM=0, takes this route with them);
+      autograd -- what is left: wider heads, host tensors."""
+    cm = layer.coors_mlp
+    if native and cm is not None and layer.node_mlp is not None and m <= 16 and cm[0].weight.shape[0] <= 64 and cdim == 3:
+        return ROUTE_STANDARD
+    if m <= 64 and (not native or (on_device and _GRAD_GEMM)):
+        return ROUTE_CLOSED
+    return ROUTE_AUTOGRAD
 
 
 def _ops_mod():
@@ -961,16 +988,23 @@ def _pooled_messages(layer, u, m0, i64, r0, valid_radius):
         gl = layer.edge_gate[0]
         mm = mm * torch.sigmoid(mm @ gl.weight.detach().to(u.dtype)[0] + gl.bias.detach().to(u.dtype))[..., None]
     m_sum = (mm if pm is None else mm.masked_fill(~pm[..., None], 0.0)).sum(dim=2)
-    cnt = None
-    if layer.m_pool_method == "mean":
-        if pm is not None:
-            cnt = pm.sum(dim=-1, keepdim=True).to(m_sum.dtype)
-            m_i = (m_sum / cnt.clamp(min=1e-8)).masked_fill(cnt == 0, 0.0)
-        else:
-            m_i = m_sum / k
-    else:
-        m_i = m_sum
+    m_i, cnt = _pooled(layer, m_sum, pm, k)
     return m_i, pm, cnt
+
+
+def _mean_pool(x, cnt, k):
+    """x over the number of pairs the masks keep per node, 0 where they keep none (safe_div: egnn_pytorch.py:13-16, :326-328); cnt
+    None: all k pairs count.  Linear and diagonal, so its own adjoint: the summed messages forward, d loss / d m_i backward."""
+    return (x / cnt.clamp(min=1e-8)).masked_fill(cnt == 0, 0.0) if cnt is not None else x / k
+
+
+def _pooled(layer, m_sum, pm, k):
+    """(m_i, cnt) from the per-node sums of the messages: m_pool_method "sum" or "mean" (cnt: the kept pairs per node (B,N,1), None
+    without a mask or with "sum")"""
+    if layer.m_pool_method != "mean":
+        return m_sum, None
+    cnt = None if pm is None else pm.sum(dim=-1, keepdim=True).to(m_sum.dtype)
+    return _mean_pool(m_sum, cnt, k), cnt
 
 
 def _node_mlp_backward_exact(layer, f2d, m_i, g_out, grads, drop=None, row0=0):
@@ -1053,12 +1087,259 @@ def _tail_closed_form(layer, u2d, c0, i32, pm, g_coors_chunk, g_msum, grads, dl,
     return out["gU"], (src - dst).view(b, n, -1)
 
 
+class _Chunk:
+    """Graphs [lo, hi) of one backward: the saved inputs (contiguous), the incoming cotangents, and the rows of d loss / d feats and
+    d loss / d coors that the steps add their shares to."""
+
+    def __init__(self, lo, hi, k, feats, coors, edges, mask, idx32, rank, g_node, g_coors, g_feats, g_coors_in):
+        self.lo, self.hi, self.bc, self.n, self.k = lo, hi, hi - lo, feats.shape[1], k
+        self.bn, self.ec = self.bc * self.n, self.bc * self.n * k
+        self.f0, self.c0 = feats[lo:hi].contiguous(), coors[lo:hi].contiguous()
+        self.e0 = None if edges is None else edges[lo:hi].contiguous()
+        self.m0 = None if mask is None else mask[lo:hi]
+        self.i32 = None if idx32 is None else idx32[lo:hi].contiguous()
+        self.i64 = None if self.i32 is None else self.i32.long()
+        self.r0 = None if rank is None else rank[lo:hi]
+        self.g_node, self.g_coors = g_node[lo:hi], g_coors[lo:hi]
+        self.g_feats, self.g_coors_in = g_feats[lo:hi], g_coors_in[lo:hi]
+
+
+class _BehindU(NamedTuple):
+    """What step 1 leaves for steps 2 and 3 (its shares of d/d feats, d/d coors and its parameter gradients are already added)."""
+    g_u: torch.Tensor                   # d loss / d u, (E, m) -- or (E, pad_to)
+    scal: torch.Tensor                  # the per-edge scalars (B,N,K,S): over the leaves c, e below unless closed_dist
+    c: torch.Tensor                     # leaf copy of the chunk's coordinates ...
+    e: Any                              # ... and of its edge features (None without), which `scal` is a graph over
+    rel: Any = None                     # x_i - x_j per edge
+    g_rel: Any = None                   # d loss / d (x_i - x_j) (E, 4) where the caller still has to take it to the coordinates
+    closed_dist: bool = False           # the distance is the only scalar: the caller differentiates it in closed form, onto g_rel
+    bias2: Any = None                   # column sums of gU (= d/d edge_mlp's last bias) where the kernel summed them
+    gu_bits: Any = None                 # HostRead of the bits of max |gU| where the kernel found it
+    pm: Any = None                      # the pair mask (B,N,K) bool (None: no mask, or not asked for)
+
+
+def _scalars_graph(layer, ch, by_k, want_ge):
+    """(c, e, rel, scal): the chunk's per-edge scalars as a small graph of their own over leaf copies of its coordinates and edge
+    features -- d loss / d scalars goes back through it in the last step."""
+    with torch.enable_grad():
+        c = ch.c0.detach().requires_grad_(True)
+        e = None if ch.e0 is None else ch.e0.detach().requires_grad_(want_ge)
+        rel, scal = edge_scalars(layer, c, e, ch.i64, by_k)
+    return c, e, rel, scal
+
+
+def _self_pairs(ch):
+    """(bc, N, K) bool: the pairs whose neighbour is the node itself (dense: the diagonal)"""
+    me = torch.arange(ch.n, device=ch.c0.device)
+    if ch.i64 is None:
+        return (me[:, None] == me[None, :])[None].expand(ch.bc, ch.n, ch.n)
+    return ch.i64 == me[None, :, None]
+
+
+def _gu_rows(g_u, ec, m, pad_to):
+    """gU as (E, m) rows; pad_to: as (E, pad_to) with zero pad channels (the fused passes take whole blocks of 16 channels)"""
+    if pad_to is None:
+        return g_u.reshape(ec, m).contiguous()
+    out = torch.zeros(ec, pad_to, dtype=g_u.dtype, device=g_u.device)
+    out[:, :m] = g_u.reshape(ec, m)
+    return out
+
+
+def _pad_cached(pads, name, shape, src):
+    """the parameter (view) `src` zero padded to `shape` in fp32, made once per set of packed weights (`bwd_pads`: rebuilt whenever a
+    parameter changes, so once per optimizer step)"""
+    if name not in pads:
+        t = torch.zeros(shape, dtype=torch.float32, device=pads["device"])
+        t[tuple(slice(0, s) for s in src.shape)] = src
+        pads[name] = t
+    return pads[name]
+
+
+def _behind_u_standard(layer, w, ch, u_all, grads, early, drop, valid_radius, by_k, want_ge):
+    """Route "standard" (native only): the node-level modules from the pooled messages (egnn_edge_pool_f32; node_mlp on the split-f16
+    GEMMs, `_node_mlp_backward`), the per-edge chain in closed form on egnn_edge_tail_bwd_f32, which also sums its parameter gradients
+    -- `tail_edge_backward` is its specification.  Host tensors (the tests, `_ops.edge_tail_bwd` emulated): pooling, node_mlp and the
+    sums over edges in ATen.  early: queues the launches that depend on the saved inputs only."""
+    from . import _ops
+    pads = w["bwd_pads"]
+    bc, n, k, ec, m, s_in = ch.bc, ch.n, ch.k, ch.ec, layer.m_dim, w["S"]
+    f0, c0 = ch.f0, ch.c0
+    dev = f0.device
+    reduce = f0.is_cuda                  # (the kernels pool the messages and sum the parameter gradients' terms themselves)
+    with torch.no_grad():
+        u16 = u_all[ch.lo:ch.hi].contiguous()
+        pm = _pair_mask(ch.m0, ch.i64, ch.r0, valid_radius)
+        pm8 = None if pm is None else pm.contiguous().view(torch.uint8)
+        gate, mm_pre, mm = None, None, None
+        if layer.edge_gate is not None:                                              # soft_edges (:289-290)
+            gate = (_pad_cached(pads, "gw16", (16,), layer.edge_gate[0].weight.detach()[0]), layer.edge_gate[0].bias.detach().contiguous())
+        if reduce:
+            m_sum = _ops.edge_pool(u16, gate, pm8, bc, n, k)
+        else:
+            mm = torch.nn.functional.silu(u16)                                       # (bc, n, k, 16), columns >= m are 0
+            if gate is not None:
+                mm_pre = mm
+                mm = mm_pre * torch.sigmoid(mm_pre @ gate[0] + gate[1])[..., None]
+            m_sum = (mm if pm is None else mm.masked_fill(~pm[..., None], 0.0)).sum(dim=2)
+        m_i, cnt = _pooled(layer, m_sum, pm, k)
+        del m_sum
+    with torch.enable_grad():
+        f = f0.detach().requires_grad_(True)
+        c = c0.detach().requires_grad_(True)
+        e = None if ch.e0 is None else ch.e0.detach().requires_grad_(want_ge)
+        closed_dist = s_in == 1                       # the distance is the only per-edge scalar: its backward in closed form (caller)
+        rel = scal = None
+        if closed_dist:
+            if not reduce:                            # (reduce: x_i - x_j and the distance are by-products of the tail kernel)
+                with torch.no_grad():
+                    rel, scal = edge_scalars(layer, c0, None, ch.i64)
+        else:
+            rel, scal = edge_scalars(layer, c, e, ch.i64, by_k)                      # (only the scalars' graph is used by the caller)
+    if f0.is_cuda and _GRAD_GEMM:
+        g_f, g_mi = _node_mlp_backward(layer, w, f, m_i[..., :m], ch.g_node, grads, drop, ch.lo * n, overlap=early)
+        ch.g_feats += g_f
+    else:
+        with torch.enable_grad():
+            mi = m_i[..., :m].detach().requires_grad_(True)
+            out_n = _per_edge(layer.node_mlp, torch.cat((layer.node_norm(f), mi), dim=-1)) + f      # (split-K weight gradients)
+            # (only what requires grad may be differentiated: a frozen parameter in the list makes autograd.grad raise)
+            node_params = [p for p in list(layer.node_norm.parameters()) + list(layer.node_mlp.parameters()) if p.requires_grad]
+            tg = torch.autograd.grad([out_n], [f, mi] + node_params, [ch.g_node], allow_unused=True)
+        if tg[0] is not None:
+            ch.g_feats += tg[0]
+        for p, g in zip(node_params, tg[2:]):
+            if g is not None:
+                grads[id(p)] += g
+        g_mi = tg[1]
+    with torch.no_grad():
+        g_msum = torch.zeros(bc, n, 16, dtype=torch.float32, device=dev)
+        if g_mi is not None:
+            if layer.m_pool_method == "mean":
+                g_mi = _mean_pool(g_mi, cnt, k)
+            g_msum[..., :m] = g_mi
+        lin_a, lin_b = layer.coors_mlp[0], layer.coors_mlp[3]
+        hid3 = lin_a.weight.shape[0]
+        w3p = _pad_cached(pads, "w3p", (64, 16), lin_a.weight.detach())
+        b3p = _pad_cached(pads, "b3p", (64,), lin_a.bias.detach())
+        w4p = _pad_cached(pads, "w4p", (64,), lin_b.weight.detach()[0])
+        norm = layer.norm_coors
+        tail_args = (u16, c0, ch.i32, pm8, ch.g_coors.contiguous(), g_msum, w3p, b3p, w4p, lin_b.bias.detach().contiguous(),
+                     layer.coors_norm.scale.detach() if norm else None, layer.coors_norm.eps if norm else 0.0,
+                     layer.coor_weights_clamp_value, bc, n, k)
+        bias2 = gu_bits = None
+        if reduce:
+            gu16, g_rel, sums, rel4, dist, gu_bits = _ops.edge_tail_bwd(*tail_args, gate=gate, reduce=True, want_rel=closed_dist,
+                                                                       drop=drop, eid0=ch.lo * n * k)
+            gu_bits = _ops.HostRead(gu_bits)                              # (read in step 2, behind the small launches below)
+            at = _ops.TAIL_SUMS
+            grads[id(lin_a.weight)] += sums[at["W3"]].view(64, 16)[:hid3, :m]
+            grads[id(lin_a.bias)] += sums[at["b3"]][:hid3]
+            grads[id(lin_b.weight)] += sums[at["W4"]][:hid3][None, :]
+            grads[id(lin_b.bias)] += sums[at["b4"]]
+            if norm:
+                grads[id(layer.coors_norm.scale)] += sums[at["scale"]]
+            if gate is not None:
+                grads[id(layer.edge_gate[0].weight)] += sums[at["gate_w"]][:m][None, :]
+                grads[id(layer.edge_gate[0].bias)] += sums[at["gate_b"]]
+            bias2 = sums[at["gU"]][:m]                                    # column sums of gU = d loss / d edge_mlp's last bias
+            if closed_dist:
+                rel, scal = rel4, dist.view(bc, n, k, 1)
+        else:
+            tail_out = _ops.edge_tail_bwd(*tail_args, gate=gate)
+            gu16, g_rel, g_hid, a3, g_w, g_sc = tail_out[:6]
+            if gate is not None:
+                g_gate = tail_out[6]
+                grads[id(layer.edge_gate[0].weight)] += _tn(g_gate[:, None], mm_pre.view(ec, 16))[:, :m]
+                grads[id(layer.edge_gate[0].bias)] += g_gate.sum()[None]
+            grads[id(lin_a.weight)] += _tn(g_hid, mm.view(ec, 16))[:hid3, :m]
+            grads[id(lin_a.bias)] += g_hid.sum(dim=0)[:hid3]
+            grads[id(lin_b.weight)] += _tn(g_w[:, None], a3)[:, :hid3]
+            grads[id(lin_b.bias)] += g_w.sum()[None]
+            if norm:
+                grads[id(layer.coors_norm.scale)] += g_sc.sum()[None]
+        ch.g_coors_in += ch.g_coors                                       # (the residual; g_rel reaches the coordinates in the caller)
+        early()
+    return _BehindU(gu16, scal, c, e, rel=rel, g_rel=g_rel, closed_dist=closed_dist, bias2=bias2, gu_bits=gu_bits, pm=pm)
+
+
+def _behind_u_closed(layer, ch, u_all, grads, node_bwd, early, drop, valid_radius, by_k, want_ge, pad_to):
+    """Route "closed": the pooled messages on E x m tensors, node_norm / node_mlp on node_bwd(ch, m_i, overlap) -> (d/d feats (bc, n,
+    dim), d/d m_i (bc, n, m)), the per-edge chain in closed form on egnn_edge_tail_exact_bwd_* (one thread per edge; `_tail_closed_form`)
+    with its parameter gradients on the exact GEMMs.  early() -> the chunk's destination lists, queueing them if the caller has not."""
+    m, k = layer.m_dim, ch.k
+    c, e, rel, scal = _scalars_graph(layer, ch, by_k, want_ge)
+    with torch.no_grad():
+        u4 = u_all[ch.lo:ch.hi, :, :, :m]
+        m_i, pm, cnt = _pooled_messages(layer, u4, ch.m0, ch.i64, ch.r0, valid_radius)
+        g_msum = None
+        if layer.node_mlp is not None:
+            g_f, g_mi = node_bwd(ch, m_i, early)
+            ch.g_feats += g_f
+            if layer.m_pool_method == "mean":
+                g_mi = _mean_pool(g_mi, cnt, k)
+            g_msum = g_mi.reshape(ch.bn, m).contiguous()
+        else:
+            ch.g_feats += ch.g_node                                       # (update_feats=False: node_out is feats)
+        ch.g_coors_in += ch.g_coors                                       # the residual of the coordinate update
+        dl = early()
+        g_u, g_c = _tail_closed_form(layer, u4.reshape(ch.ec, m).contiguous(), ch.c0, ch.i32, pm, ch.g_coors, g_msum, grads, dl, ch.bc, ch.n,
+                                     k, drop, ch.lo * ch.n * k)
+        ch.g_coors_in += g_c
+        g_u = _gu_rows(g_u, ch.ec, m, pad_to)
+    return _BehindU(g_u, scal, c, e, rel=rel, pm=pm)
+
+
+def _behind_u_autograd(layer, ch, u_all, grads, tail_params, drop, valid_radius, by_k, want_ge, pad_to, want_pm):
+    """Route "autograd": `layer_tail` on E x m / node-level tensors, differentiated by autograd (heads wider than 64 channels; host
+    tensors).  tail_params: the layer's parameters behind u."""
+    m = layer.m_dim
+    c, e, rel, scal = _scalars_graph(layer, ch, by_k, want_ge)
+    with torch.enable_grad():
+        f = ch.f0.detach().requires_grad_(True)
+        u = u_all[ch.lo:ch.hi, :, :, :m].detach().requires_grad_(True)
+        pm = _pair_mask(ch.m0, ch.i64, ch.r0, valid_radius) if want_pm else None
+        rel_tail = rel
+        if layer.norm_coors and layer.coors_mlp is not None:
+            # A self pair (j == i) has rel = x_i - x_i: what CoorsNorm sends back through it reaches x_i once with each sign and cancels
+            # identically, but each copy is scale / eps = 1e8 times the coordinate weight, and autograd's two sums left rounding noise of
+            # that size in d/d coors (2.7e-2 of its maximum in fp32).  Taken out of the graph, as the closed-form kernels write it as zero.
+            rel_tail = torch.where(_self_pairs(ch)[..., None], rel.detach(), rel)
+        out_n, out_c = layer_tail(layer, f, c, u, rel_tail, ch.m0, ch.i64, ch.r0, valid_radius, drop=drop, graph_offset=ch.lo)
+        outs, gouts = [], []
+        for o, g in ((out_n, ch.g_node), (out_c, ch.g_coors)):
+            if o.requires_grad:
+                outs.append(o)
+                gouts.append(g)
+        live_tail = [p for p in tail_params if p.requires_grad]
+        tg = torch.autograd.grad(outs, [u, f, c] + live_tail, gouts, allow_unused=True, retain_graph=True)
+    if tg[1] is not None:
+        ch.g_feats += tg[1]
+    if tg[2] is not None:
+        ch.g_coors_in += tg[2]
+    for p, g in zip(live_tail, tg[3:]):
+        if g is not None:
+            grads[id(p)] += g
+    return _BehindU(_gu_rows(tg[0] if tg[0] is not None else torch.zeros_like(u), ch.ec, m, pad_to), scal, c, e, rel=rel, pm=pm)
+
+
+def _returned_gradients(ctx, layer, orig_params, grads, g_feats, g_coors_in, g_edges, lk, in_dtypes):
+    """The tuple a backward path returns, in the layout (layer, order_hint, mask, adj, feats, coors, edges, *params): every gradient
+    in its owner's dtype, None where nobody asked or no output depends on the parameter (`_unused_params`)."""
+    need = _need(ctx)
+    unused = _unused_params(layer, ctx)
+    out_params = [grads[id(p)].to(op.dtype) if (need[7 + i] and id(p) not in unused) else None
+                  for i, (p, op) in enumerate(zip(layer.parameters(), orig_params))]
+    return (None, None, None, None, g_feats.to(in_dtypes[0]) if need[4] else None, g_coors_in.to(in_dtypes[1]) if need[5] else None,
+            lk.outputs() if lk is not None else (g_edges.to(in_dtypes[2]) if g_edges is not None else None), *out_params)
+
+
 def _backward_exact(ctx, g_node, g_coors):
     """The backward of the layers that run on the plain kernels -- float64 modules (the reference's own training recipe,
     denoise_sparse.py:11, 23-32), calls answered by the wide-range path, shapes beyond the fused kernels' limits -- in the arithmetic of
     their forward (float64 / plain fp32), per chunk of graphs:
-      1. behind u (saved by the forward kernel): the small per-edge tail and the node-level modules through autograd on E x m / node-level
-         tensors (`layer_tail`)  ->  gU = d loss / d u, their parameters' gradients, the tail's share of d/d feats, d/d coors;
+      1. behind u (saved by the forward kernel): the per-edge tail and the node-level modules, by `_behind_u_route` in closed form
+         (`_behind_u_closed`, m_dim <= 64) or through autograd on E x m / node-level tensors (`_behind_u_autograd`)
+         ->  gU = d loss / d u, their parameters' gradients, the tail's share of d/d feats, d/d coors;
       2. the E x H work on egnn_edge_exact_bwd_* (csrc/edge_exact_bwd.hip): z, a recomputed, dz = (W2^T gU) SiLU'(z); a^T, dz^T (H, E) and
          d/d scalars; the per-node sums of dz over outgoing / incoming edges on egnn_edge_exact_node_sums_* (fixed order);
       3. every contraction a C = X W^T product of egnn_linear_f32 / _f64 (exact v_mfma_f32 / v_mfma_f64): d/d W2 = gU^T a and
@@ -1102,63 +1383,23 @@ def _backward_exact(ctx, g_node, g_coors):
     w2 = lin3.weight.detach().to(dtype).contiguous()                      # (m, H)
     w_it, w_jt = w1[:, :dim].t().contiguous(), w1[:, dim:2 * dim].t().contiguous()       # (dim, H): B operands of d/d feats
     step = max(1, min(b, int(_EXACT_BWD_BYTES // max(1, 2 * n * k * h * esz))))
+    route = _behind_u_route(layer, m, cdim, feats.is_cuda, False)
+
+    def node_bwd(ch, m_i, overlap):                                       # (node_mlp on the exact GEMMs, node-level rows)
+        g_f, g_mi = _node_mlp_backward_exact(layer, ch.f0.view(ch.bn, dim), m_i.reshape(ch.bn, m), ch.g_node.reshape(ch.bn, dim), grads, drop,
+                                             ch.lo * n)
+        return g_f.view(ch.bc, n, dim), g_mi.view(ch.bc, n, m)
     for lo in range(0, b, step):
         hi_ = min(b, lo + step)
-        bc = hi_ - lo
-        ec, bn = bc * n * k, bc * n
-        f0, c0 = feats[lo:hi_].contiguous(), coors[lo:hi_].contiguous()
-        e0 = None if edges is None else edges[lo:hi_].contiguous()
-        m0 = None if mask is None else mask[lo:hi_]
-        i32 = None if idx32 is None else idx32[lo:hi_].contiguous()
-        i64 = None if i32 is None else i32.long()
-        r0 = None if rank is None else rank[lo:hi_]
+        ch = _Chunk(lo, hi_, k, feats, coors, edges, mask, idx32, rank, g_node, g_coors, g_feats, g_coors_in)
+        bc, ec, bn, f0, c0, e0, i32 = ch.bc, ch.ec, ch.bn, ch.f0, ch.c0, ch.e0, ch.i32
         dl = _ops.dest_lists(i32, bc, n, k, dev)
-        with torch.enable_grad():
-            c = c0.detach().requires_grad_(True)
-            e = None if e0 is None else e0.detach().requires_grad_(want_ge)
-            rel, scal = edge_scalars(layer, c, e, i64, by_k)                      # (the scalars' own graph: step 4)
-        if m <= 64 and _TAIL_GENERIC:
-            # ---- 1. behind u, in closed form: the pooled messages (E x m element-wise), node_norm / node_mlp on the exact GEMMs, the
-            # per-edge chain on egnn_edge_tail_exact_bwd_* with its parameter gradients contracted on the exact GEMMs
-            with torch.no_grad():
-                u4 = u_all[lo:hi_]
-                m_i, pm, cnt = _pooled_messages(layer, u4, m0, i64, r0, ctx.valid_radius)
-                g_msum = None
-                if layer.node_mlp is not None:
-                    g_f, g_mi = _node_mlp_backward_exact(layer, f0.view(bn, dim), m_i.reshape(bn, m), g_node[lo:hi_].reshape(bn, dim), grads,
-                                                         drop, lo * n)
-                    g_feats[lo:hi_] += g_f.view(bc, n, dim)
-                    g_mi = g_mi.view(bc, n, m)
-                    if layer.m_pool_method == "mean":
-                        g_mi = (g_mi / cnt.clamp(min=1e-8)).masked_fill(cnt == 0, 0.0) if cnt is not None else g_mi / k
-                    g_msum = g_mi.reshape(bn, m).contiguous()
-                else:
-                    g_feats[lo:hi_] += g_node[lo:hi_]                                # (update_feats=False: node_out is feats)
-                g_coors_in[lo:hi_] += g_coors[lo:hi_]                                # the residual of the coordinate update
-                g_u, g_c = _tail_closed_form(layer, u4.reshape(ec, m).contiguous(), c0, i32, pm, g_coors[lo:hi_], g_msum, grads, dl, bc, n, k,
-                                             drop, lo * n * k)
-                g_coors_in[lo:hi_] += g_c
+        # ---- 1. behind u: in closed form (m_dim <= 64), else through autograd
+        if route == ROUTE_CLOSED:
+            tail = _behind_u_closed(layer, ch, u_all, grads, node_bwd, lambda: dl, drop, ctx.valid_radius, by_k, want_ge, None)
         else:
-            # ---- 1. the small tail, through autograd (E x m, node-level): heads wider than 64 channels
-            with torch.enable_grad():
-                f = f0.detach().requires_grad_(True)
-                u = u_all[lo:hi_].detach().requires_grad_(True)
-                out_n, out_c = layer_tail(layer, f, c, u, rel, m0, i64, r0, ctx.valid_radius, drop=drop, graph_offset=lo)
-                outs, gouts = [], []
-                for o, g in ((out_n, g_node[lo:hi_]), (out_c, g_coors[lo:hi_])):
-                    if o.requires_grad:
-                        outs.append(o)
-                        gouts.append(g)
-                live_tail = [p for p in tail_params if p.requires_grad]
-                tg = torch.autograd.grad(outs, [u, f, c] + live_tail, gouts, allow_unused=True, retain_graph=True)
-            g_u = (tg[0] if tg[0] is not None else torch.zeros_like(u)).reshape(ec, m).contiguous()
-            if tg[1] is not None:
-                g_feats[lo:hi_] += tg[1]
-            if tg[2] is not None:
-                g_coors_in[lo:hi_] += tg[2]
-            for p, g in zip(live_tail, tg[3:]):
-                if g is not None:
-                    grads[id(p)] += g
+            tail = _behind_u_autograd(layer, ch, u_all, grads, tail_params, drop, ctx.valid_radius, by_k, want_ge, None, False)
+        g_u, scal, c, e = tail.g_u, tail.scal, tail.c, tail.e
         with torch.no_grad():
             # ---- 2. the E x H work
             a_t = _ops.empty(h, ec, dtype=dtype, device=dev)
@@ -1199,11 +1440,7 @@ def _backward_exact(ctx, g_node, g_coors):
             g_coors_in[lo:hi_] += sg[0]
         if want_ge and sg[1] is not None:
             g_edges[lo:hi_] += sg[1]
-    unused = _unused_params(layer, ctx)
-    out_params = [grads[id(p)].to(op.dtype) if (need[7 + i] and id(p) not in unused) else None
-                  for i, (p, op) in enumerate(zip(params, orig_params))]
-    return (None, None, None, None, g_feats.to(in_dtypes[0]) if need[4] else None, g_coors_in.to(in_dtypes[1]) if need[5] else None,
-            lk.outputs() if lk is not None else (g_edges.to(in_dtypes[2]) if (want_ge and need[6]) else None)) + tuple(out_params)
+    return _returned_gradients(ctx, layer, orig_params, grads, g_feats, g_coors_in, g_edges, lk, in_dtypes)
 
 
 def _unused_params(layer, ctx=None):
@@ -1463,9 +1700,11 @@ def check_fused_training_shape(layer, b, n, k):
 
 def _backward_native(ctx, g_node, g_coors):
     """The backward on the HIP kernels (module docstring), per chunk of graphs:
-       1. behind u = ctx.u_pre (edge_mlp's second Linear, written by the forward kernel): the pooled messages (egnn_edge_pool_f32), node_mlp
-          on the split-f16 GEMMs (`_node_mlp_backward`; node_norm through autograd); the per-edge chain in closed form on
-          egnn_edge_tail_bwd_f32, which also sums its parameter gradients (on the CPU, in the tests: through autograd, `layer_tail`)  ->  gU = d loss / d u, d loss / d (x_i - x_j), those modules' parameter gradients;
+       1. behind u = ctx.u_pre (edge_mlp's second Linear, written by the forward kernel), on the route `_behind_u_route` names:
+          `_behind_u_standard` (the pooled messages on egnn_edge_pool_f32, node_mlp on the split-f16 GEMMs, the per-edge chain in closed
+          form on egnn_edge_tail_bwd_f32, which also sums its parameter gradients), `_behind_u_closed` (wider heads, other coordinate
+          dimensions: egnn_edge_tail_exact_bwd_f32) or `_behind_u_autograd` (`layer_tail`: host tensors)
+          ->  gU = d loss / d u, d loss / d (x_i - x_j), those modules' parameter gradients;
        2. the E x H work on egnn_edge_bwd_pass_f32 (`_edge_contract_fused`: by source and by destination, everything recomputed
           and contracted in registers)
           ->  d/d P_i, d/d P_j per node, d/d W_s, d/d scalars, d/d W_2;
@@ -1510,7 +1749,6 @@ def _backward_native(ctx, g_node, g_coors):
     mp = 16 * _weights.m_blocks(m)                       # u rows: whole 16-channel blocks, pad channels 0
     u_all = ctx.saved_tensors[6].view(b, n, k, mp)
     drop = getattr(ctx, "drop", None)                    # (p, seed) of a training-mode forward (_dropout_native_ok), else None
-    reduce = False
     # (egnn_edge_bwd_pass_f32: up to 16 per-edge scalars -- beyond five with the all-edge contractions split over the two passes)
     fused = (s_in <= 5 or (s_in <= 16 and _FUSED_SPLIT == "dest" and "WsTh" in w))
     if not fused:
@@ -1533,33 +1771,23 @@ def _backward_native(ctx, g_node, g_coors):
     pads = w.get("bwd_pads")
     if pads is None or pads["device"] != feats.device:
         pads = w["bwd_pads"] = {"device": feats.device}
-        w_s = torch.zeros(hp, lin0.weight.shape[1] - 2 * dim, dtype=torch.float32, device=feats.device)
-        w_s[:h] = lin0.weight.detach()[:, 2 * dim:]
-        pads["w_s"] = w_s
-    w_s = pads["w_s"]
+    w_s = _pad_cached(pads, "w_s", (hp, lin0.weight.shape[1] - 2 * dim), lin0.weight.detach()[:, 2 * dim:])
     w_i = w_j = None
     if not (feats.is_cuda and _GRAD_GEMM):               # (host tensors -- the CPU tests: plain matmuls instead of the split-f16 GEMM)
         w1p = torch.zeros(hp, lin0.weight.shape[1], dtype=torch.float32, device=feats.device)
         w1p[:h] = lin0.weight.detach()
         w_i, w_j = w1p[:, :dim].contiguous(), w1p[:, dim:2 * dim].contiguous()
     pi_split = k >= 6
-    # the per-edge chain behind u in closed form on the device (egnn_edge_tail_bwd_f32) where it applies (m_dim <= 16, coors_mlp
-    # hidden width <= 64); otherwise that part goes through autograd as well
-    tail_kernel = (_TAIL_KERNEL and layer.coors_mlp is not None and layer.node_mlp is not None
-                   and m <= 16 and layer.coors_mlp[0].weight.shape[0] <= 64 and coors.shape[-1] == 3)
+    route = _behind_u_route(layer, m, coors.shape[-1], feats.is_cuda, True)
+
+    def node_bwd(ch, m_i, overlap):                          # (node_mlp on the split-f16 GEMMs, `overlap` queued behind its SiLU pass)
+        return _node_mlp_backward(layer, w, ch.f0.detach().requires_grad_(True), m_i, ch.g_node, grads_by_id, drop, ch.lo * n, overlap=overlap)
     w2_finite = ctx.w2_finite = []
     for lo in range(0, b, step):
         hi_ = min(b, lo + step)
-        bc = hi_ - lo
-        f0, c0 = feats[lo:hi_].contiguous(), coors[lo:hi_].contiguous()
-        e0 = None if edges is None else edges[lo:hi_].contiguous()
-        m0 = None if mask is None else mask[lo:hi_]
-        i32 = None if idx32 is None else idx32[lo:hi_].contiguous()
-        i64 = None if i32 is None else i32.long()
-        r0 = None if rank is None else rank[lo:hi_]
-        ec = bc * n * k
+        ch = _Chunk(lo, hi_, k, feats, coors, edges, mask, idx32, rank, g_node, g_coors, g_feats, g_coors_in)
+        bc, ec, f0, c0, e0, i32, i64 = ch.bc, ch.ec, ch.f0, ch.c0, ch.e0, ch.i32, ch.i64
         dest_lists = None
-        pm = None                                            # (bc, n, k) bool: the pairs that pass the masks (None: all of them)
         hr_f = _ops.absmax_async(f0.view(bc * n, dim)) if (f0.is_cuda and _GRAD_GEMM) else None      # (read in step 3)
 
         def early():
@@ -1569,182 +1797,17 @@ def _backward_native(ctx, g_node, g_coors):
             if proj_all is not None and ctx.proj_words:
                 _ops.unsplit_words_(proj_all, hp)
                 ctx.proj_words = False
-            if dest_lists is None and (i32 is not None or not tail_kernel):
+            if dest_lists is None and (i32 is not None or route != ROUTE_STANDARD):
                 dest_lists = _ops.dest_lists(i32, bc, n, k, feats.device)                     # (shared by the tail and the E x H passes)
-        if tail_kernel:
-            # ---- 1. behind u: the node-level modules through autograd (node_norm, node_mlp, residual: from the pooled messages),
-            # the per-edge chain (second SiLU, masks, coors_mlp, CoorsNorm, clamp, coordinate update, pooling) in closed form on
-            # egnn_edge_tail_bwd_f32 -- `tail_edge_backward` is its specification
-            with torch.no_grad():
-                u16 = u_all[lo:hi_].contiguous()
-                pm = _pair_mask(m0, i64, r0, ctx.valid_radius)
-                reduce = f0.is_cuda and _TAIL_REDUCE       # (the kernels pool the messages and sum the parameter gradients' terms themselves)
-                pm8 = None if pm is None else pm.contiguous().view(torch.uint8)
-                gate, mm_pre, mm = None, None, None
-                if layer.edge_gate is not None:                                              # soft_edges (:289-290)
-                    if "gw16" not in pads:
-                        gw16 = torch.zeros(16, dtype=torch.float32, device=feats.device)
-                        gw16[:m] = layer.edge_gate[0].weight.detach()[0]
-                        pads["gw16"] = gw16
-                    gate = (pads["gw16"], layer.edge_gate[0].bias.detach().contiguous())
-                if reduce:
-                    m_sum = _ops.edge_pool(u16, gate, pm8, bc, n, k)
-                else:
-                    mm = torch.nn.functional.silu(u16)                                       # (bc, n, k, 16), columns >= m are 0
-                    if gate is not None:
-                        mm_pre = mm
-                        mm = mm_pre * torch.sigmoid(mm_pre @ gate[0] + gate[1])[..., None]
-                    m_sum = (mm if pm is None else mm.masked_fill(~pm[..., None], 0.0)).sum(dim=2)
-                cnt = None
-                if layer.m_pool_method == "mean":
-                    if pm is not None:
-                        cnt = pm.sum(dim=-1, keepdim=True).to(m_sum.dtype)
-                        m_i = (m_sum / cnt.clamp(min=1e-8)).masked_fill(cnt == 0, 0.0)
-                    else:
-                        m_i = m_sum / k
-                else:
-                    m_i = m_sum
-                del m_sum
-            with torch.enable_grad():
-                f = f0.detach().requires_grad_(True)
-                c = c0.detach().requires_grad_(True)
-                e = None if e0 is None else e0.detach().requires_grad_(want_ge)
-                closed_dist = s_in == 1                       # the distance is the only per-edge scalar: its backward in closed form below
-                if closed_dist:
-                    if not reduce:                            # (reduce: x_i - x_j and the distance are by-products of the tail kernel)
-                        with torch.no_grad():
-                            rel, scal = edge_scalars(layer, c0, None, i64)
-                else:
-                    rel, scal = edge_scalars(layer, c, e, i64, by_k)                         # (only the scalars' graph is used below)
-            if f0.is_cuda and _GRAD_GEMM:
-                g_f, g_mi = _node_mlp_backward(layer, w, f, m_i[..., :m], g_node[lo:hi_], grads_by_id, drop, lo * n, overlap=early)
-                g_feats[lo:hi_] += g_f
-            else:
-                with torch.enable_grad():
-                    mi = m_i[..., :m].detach().requires_grad_(True)
-                    out_n = _per_edge(layer.node_mlp, torch.cat((layer.node_norm(f), mi), dim=-1)) + f      # (split-K weight gradients)
-                    # (only what requires grad may be differentiated: a frozen parameter in the list makes autograd.grad raise)
-                    node_params = [p for p in list(layer.node_norm.parameters()) + list(layer.node_mlp.parameters()) if p.requires_grad]
-                    tg = torch.autograd.grad([out_n], [f, mi] + node_params, [g_node[lo:hi_]], allow_unused=True)
-                if tg[0] is not None:
-                    g_feats[lo:hi_] += tg[0]
-                for p, g in zip(node_params, tg[2:]):
-                    if g is not None:
-                        grads_by_id[id(p)] += g
-                g_mi = tg[1]
-            with torch.no_grad():
-                g_msum = torch.zeros(bc, n, 16, dtype=torch.float32, device=feats.device)
-                if g_mi is not None:
-                    if layer.m_pool_method == "mean":
-                        g_mi = (g_mi / cnt.clamp(min=1e-8)).masked_fill(cnt == 0, 0.0) if cnt is not None else g_mi / k
-                    g_msum[..., :m] = g_mi
-                lin_a, lin_b = layer.coors_mlp[0], layer.coors_mlp[3]
-                hid3 = lin_a.weight.shape[0]
-                if "w3p" not in pads:
-                    w3p = torch.zeros(64, 16, dtype=torch.float32, device=feats.device)
-                    w3p[:hid3, :m] = lin_a.weight.detach()
-                    b3p = torch.zeros(64, dtype=torch.float32, device=feats.device)
-                    b3p[:hid3] = lin_a.bias.detach()
-                    w4p = torch.zeros(64, dtype=torch.float32, device=feats.device)
-                    w4p[:hid3] = lin_b.weight.detach()[0]
-                    pads["w3p"], pads["b3p"], pads["w4p"] = w3p, b3p, w4p
-                w3p, b3p, w4p = pads["w3p"], pads["b3p"], pads["w4p"]
-                norm = layer.norm_coors
-                tail_args = (u16, c0, i32, pm8, g_coors[lo:hi_].contiguous(), g_msum, w3p, b3p, w4p, lin_b.bias.detach().contiguous(),
-                             layer.coors_norm.scale.detach() if norm else None, layer.coors_norm.eps if norm else 0.0,
-                             layer.coor_weights_clamp_value, bc, n, k)
-                bias2 = gu_bits = None
-                if reduce:
-                    gu16, g_rel, sums, rel4, dist, gu_bits = _ops.edge_tail_bwd(*tail_args, gate=gate, reduce=True, want_rel=closed_dist,
-                                                                               drop=drop, eid0=lo * n * k)
-                    gu_bits = _ops.HostRead(gu_bits)                              # (read in step 2, behind the small launches below)
-                    grads_by_id[id(lin_a.weight)] += sums[:1024].view(64, 16)[:hid3, :m]
-                    grads_by_id[id(lin_a.bias)] += sums[1024:1024 + hid3]
-                    grads_by_id[id(lin_b.weight)] += sums[1088:1088 + hid3][None, :]
-                    grads_by_id[id(lin_b.bias)] += sums[1184:1185]
-                    if norm:
-                        grads_by_id[id(layer.coors_norm.scale)] += sums[1185:1186]
-                    if gate is not None:
-                        grads_by_id[id(layer.edge_gate[0].weight)] += sums[1168:1168 + m][None, :]
-                        grads_by_id[id(layer.edge_gate[0].bias)] += sums[1186:1187]
-                    bias2 = sums[1152:1152 + m]                                  # column sums of gU = d loss / d edge_mlp's last bias
-                    if closed_dist:
-                        rel, scal = rel4, dist.view(bc, n, k, 1)
-                else:
-                    tail_out = _ops.edge_tail_bwd(*tail_args, gate=gate)
-                    gu16, g_rel, g_hid, a3, g_w, g_sc = tail_out[:6]
-                    if gate is not None:
-                        g_gate = tail_out[6]
-                        grads_by_id[id(layer.edge_gate[0].weight)] += _tn(g_gate[:, None], mm_pre.view(ec, 16))[:, :m]
-                        grads_by_id[id(layer.edge_gate[0].bias)] += g_gate.sum()[None]
-                        del mm_pre, g_gate
-                    grads_by_id[id(lin_a.weight)] += _tn(g_hid, mm.view(ec, 16))[:hid3, :m]
-                    grads_by_id[id(lin_a.bias)] += g_hid.sum(dim=0)[:hid3]
-                    grads_by_id[id(lin_b.weight)] += _tn(g_w[:, None], a3)[:, :hid3]
-                    grads_by_id[id(lin_b.bias)] += g_w.sum()[None]
-                    if norm:
-                        grads_by_id[id(layer.coors_norm.scale)] += g_sc.sum()[None]
-                    del g_hid, a3, mm
-                g_coors_in[lo:hi_] += g_coors[lo:hi_]                              # (the residual; g_rel reaches the coordinates below)
-                early()
-        elif f0.is_cuda and _TAIL_GENERIC and _GRAD_GEMM and m <= 64:
-            # ---- 1. behind u for the heads of 17 .. 64 channels and the other coordinate dimensions (round 5): the pooled messages on
-            # E x m tensors, node_mlp on the split-f16 GEMMs, the per-edge chain in closed form on egnn_edge_tail_exact_bwd_f32 (one
-            # thread per edge; csrc/edge_exact_bwd.hip) with its parameter gradients on the exact-fp32 GEMM
-            closed_dist, g_rel, bias2, gu_bits = False, None, None, None
-            with torch.enable_grad():
-                c = c0.detach().requires_grad_(True)
-                e = None if e0 is None else e0.detach().requires_grad_(want_ge)
-                rel, scal = edge_scalars(layer, c, e, i64, by_k)                  # (only the scalars' graph is used below)
-            with torch.no_grad():
-                u4 = u_all[lo:hi_, :, :, :m]
-                m_i, pm, cnt = _pooled_messages(layer, u4, m0, i64, r0, ctx.valid_radius)
-                g_msum = None
-                if layer.node_mlp is not None:
-                    f = f0.detach().requires_grad_(True)
-                    g_f, g_mi = _node_mlp_backward(layer, w, f, m_i, g_node[lo:hi_], grads_by_id, drop, lo * n, overlap=early)
-                    g_feats[lo:hi_] += g_f
-                    if layer.m_pool_method == "mean":
-                        g_mi = (g_mi / cnt.clamp(min=1e-8)).masked_fill(cnt == 0, 0.0) if cnt is not None else g_mi / k
-                    g_msum = g_mi.reshape(bc * n, m).contiguous()
-                else:
-                    g_feats[lo:hi_] += g_node[lo:hi_]
-                g_coors_in[lo:hi_] += g_coors[lo:hi_]
-                early()
-                g_u, g_c = _tail_closed_form(layer, u4.reshape(ec, m).contiguous(), c0, i32, pm, g_coors[lo:hi_], g_msum, grads_by_id,
-                                             dest_lists, bc, n, k, drop, lo * n * k)
-                g_coors_in[lo:hi_] += g_c
-                gu16 = torch.zeros(ec, mp, dtype=torch.float32, device=feats.device)
-                gu16[:, :m] = g_u
+            return dest_lists
+        # ---- 1. behind u: gU = d loss / d u, d loss / d (x_i - x_j) or its share of d/d coors, the parameter gradients of that part
+        if route == ROUTE_STANDARD:
+            tail = _behind_u_standard(layer, w, ch, u_all, grads_by_id, early, drop, ctx.valid_radius, by_k, want_ge)
+        elif route == ROUTE_CLOSED:
+            tail = _behind_u_closed(layer, ch, u_all, grads_by_id, node_bwd, early, drop, ctx.valid_radius, by_k, want_ge, mp)
         else:
-            closed_dist, g_rel, bias2, gu_bits = False, None, None, None
-            # ---- 1. the small tail, through autograd
-            with torch.enable_grad():
-                f = f0.detach().requires_grad_(True)
-                c = c0.detach().requires_grad_(True)
-                e = None if e0 is None else e0.detach().requires_grad_(want_ge)
-                u = u_all[lo:hi_, :, :, :m].detach().requires_grad_(True)
-                rel, scal = edge_scalars(layer, c, e, i64, by_k)
-                pm = _pair_mask(m0, i64, r0, ctx.valid_radius)
-                out_n, out_c = layer_tail(layer, f, c, u, rel, m0, i64, r0, ctx.valid_radius)
-                outs, gouts = [], []
-                for o, g in ((out_n, g_node[lo:hi_]), (out_c, g_coors[lo:hi_])):
-                    if o.requires_grad:
-                        outs.append(o)
-                        gouts.append(g)
-                live_tail = [p for p in tail_params if p.requires_grad]
-                wrt = [u, f, c] + live_tail
-                tg = torch.autograd.grad(outs, wrt, gouts, allow_unused=True, retain_graph=True)
-            g_u = tg[0] if tg[0] is not None else torch.zeros_like(u)
-            if tg[1] is not None:
-                g_feats[lo:hi_] += tg[1]
-            if tg[2] is not None:
-                g_coors_in[lo:hi_] += tg[2]
-            for p, g in zip(live_tail, tg[3:]):
-                if g is not None:
-                    grads_by_id[id(p)] += g
-            gu16 = torch.zeros(ec, mp, dtype=torch.float32, device=feats.device)
-            gu16[:, :m] = g_u.reshape(ec, m)
+            tail = _behind_u_autograd(layer, ch, u_all, grads_by_id, tail_params, drop, ctx.valid_radius, by_k, want_ge, mp, True)
+        gu16, scal, c, e, rel, g_rel, closed_dist, bias2, gu_bits, pm = tail
         # ---- 2. the E x H work: d/d P_i, d/d P_j (per node), d/d W_s, d/d scalars, d/d W_2
         early()
         amax = _ops.bits_to_floats(gu_bits)[0] if gu_bits is not None else _ops.absmax(gu16)
@@ -1845,11 +1908,7 @@ def _backward_native(ctx, g_node, g_coors):
                     g_coors_in[lo:hi_] -= g_rel.view(bc, n, n, 4).sum(dim=1)[..., :3]
                 else:
                     g_coors_in[lo:hi_] -= _ops.rows_gather_sum(g_rel, dest_lists.order, dest_lists.seg, bc * n).view(bc, n, 4)[..., :3]
-    unused = _unused_params(layer, ctx)
-    out_params = [grads_by_id[id(p)].to(op.dtype) if (need[7 + i] and id(p) not in unused) else None
-                  for i, (p, op) in enumerate(zip(params, orig_params))]
-    return (None, None, None, None, g_feats.to(in_dtypes[0]) if need[4] else None, g_coors_in.to(in_dtypes[1]) if need[5] else None,
-            lk.outputs() if lk is not None else (g_edges.to(in_dtypes[2]) if want_ge else None), *out_params)
+    return _returned_gradients(ctx, layer, orig_params, grads_by_id, g_feats, g_coors_in, g_edges, lk, in_dtypes)
 
 
 def _lookup_rows(lookup, idx, b, n, k, pos=None):

@@ -29,6 +29,116 @@ constexpr int SLD = 36;      // floats per row of the store staging (144 B: the 
 constexpr int RLD = 20;      // REDUCE: floats per row of a 16-column block of g_hid / a3
 constexpr int QLD = 40;      // REDUCE: floats per row of the per-edge scalar terms
 constexpr int PART = 1192;   // REDUCE: partial sums per wave: d/d W3 (64 x 16) | d/d b3 (64) | d/d W4 (64) | 40 scalar-term sums (EGNN_TAIL_PART_FLOATS)
+// ... and where each sum sits in a wave's row of `part` (egnn_pytorch_amd/_ops.py::TAIL_SUMS names the same columns of the summed row)
+constexpr int PART_W3 = 0;                     // d/d W3 (64 x 16)
+constexpr int PART_B3 = PART_W3 + TH * TM;     // d/d b3 (64)
+constexpr int PART_W4 = PART_B3 + TH;          // d/d W4 (64)
+constexpr int PART_Q = PART_W4 + TH;           // the QLD per-edge scalar terms: column sums of gU (16) ...
+constexpr int PART_GATE_W = PART_Q + TM;       // ... d/d gate weight (16) ...
+constexpr int PART_B4 = PART_GATE_W + TM;      // ... d/d b4 ...
+constexpr int PART_SCALE = PART_B4 + 1;        // ... d/d CoorsNorm.scale ...
+constexpr int PART_GATE_B = PART_SCALE + 1;    // ... d/d gate bias ...
+constexpr int PART_ZERO = PART_GATE_B + 1;     // ... and zeros up to PART
+static_assert(PART_Q + QLD == PART && PART_ZERO <= PART, "the part row is the three weight blocks and QLD scalar terms");
+
+// ---- what the two kernels below share: one edge's ends, its scalar section, the gate, SiLU'
+struct TailEdge {
+    bool live;          // not behind the last edge (a lane behind it computes a copy of the last edge with every gradient zero, and stores nothing)
+    int64_t e, ig, jg;  // edge, global source node (b N + i), global neighbour
+    bool pm;            // live and kept by the pair mask
+};
+
+__device__ __forceinline__ TailEdge tail_edge(const egnn_edge_tail_args& p, int64_t e_raw, int64_t E)
+{
+    TailEdge o;
+    o.live = e_raw < E;
+    o.e = o.live ? e_raw : E - 1;
+    const int K = p.K, N = p.N;
+    o.ig = o.e / K;
+    o.jg = p.idx ? (o.ig / N) * N + p.idx[o.e] : (o.ig / N) * N + (o.e - o.ig * K);
+    o.pm = o.live && (p.pair_mask ? p.pair_mask[o.e] != 0 : true);
+    return o;
+}
+
+// SiLU'(x) from x and sg = sigmoid(x)
+__device__ __forceinline__ float tail_dsilu(float x, float sg) { return sg * (1.0f + x * (1.0f - sg)); }
+
+// edge gate (soft_edges, :289-290): m_ij = m0 * gt, gt = sigmoid(s), s = gate_w . m0 + gate_b; 1 - gt as sigmoid(-s): no cancellation
+// where the gate saturates
+__device__ __forceinline__ void tail_gate(float s, float& gt, float& gtc) { gt = egnn_sigmoid(s); gtc = egnn_sigmoid(-s); }
+
+// through the gate: m = m0 gt  =>  d/d m0 = gm gt + gs gate_w with gs = (gm . m0) gt (1 - gt) = d/d (gate pre-activation); NC of the
+// edge's channels, gw their gate weights
+template <int NC, class V>
+__device__ __forceinline__ void tail_gate_bwd(V& gm, const float* gw, float gs, float gt)
+{
+#pragma unroll
+    for (int c = 0; c < NC; ++c) gm[c] = __builtin_fmaf(gs, gw[c], gm[c] * gt);
+}
+
+// The per-edge scalar section: rel = x_i - x_j, CoorsNorm, pair mask and clamp of the coordinate weight w (cscale = CoorsNorm.scale or 1)
+//     g_w = mask(clamp'(g_coors_out[i] . rel')),   g_rel = CoorsNorm'(w_c g_coors_out[i]),   gsc = this edge's term of d/d CoorsNorm.scale
+struct TailCoors {
+    float rel[3];
+    float g_w, gsc;
+    f32x4 g_rel;
+};
+
+__device__ __forceinline__ TailCoors tail_coors(const egnn_edge_tail_args& p, const TailEdge& ed, float w, float cscale)
+{
+    TailCoors o;
+    float relp[3], g[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        o.rel[d] = p.coors[ed.ig * 3 + d] - p.coors[ed.jg * 3 + d];
+        g[d] = p.g_coors_out[ed.ig * 3 + d];
+    }
+    const float* rel = o.rel;
+    float rn = 0.f, den = 1.f;
+    if (p.norm_coors) {
+        rn = sqrtf(rel[0] * rel[0] + rel[1] * rel[1] + rel[2] * rel[2]);
+        den = fmaxf(rn, p.eps);
+#pragma unroll
+        for (int d = 0; d < 3; ++d) relp[d] = rel[d] / den * cscale;
+    } else {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) relp[d] = rel[d];
+    }
+    const float wm = ed.pm ? w : 0.f;
+    const bool clamped = p.clamp >= 0.f && !(wm >= -p.clamp && wm <= p.clamp);
+    const float wc = p.clamp >= 0.f ? fminf(fmaxf(wm, -p.clamp), p.clamp) : wm;
+    const float g_wc = g[0] * relp[0] + g[1] * relp[1] + g[2] * relp[2];
+    o.g_w = (ed.pm && !clamped) ? g_wc : 0.f;
+    float g_relp[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) g_relp[d] = wc * g[d];
+    o.gsc = 0.f;
+    if (p.norm_coors) {
+        const float dot = g_relp[0] * rel[0] + g_relp[1] * rel[1] + g_relp[2] * rel[2];
+        o.gsc = dot / den;
+        const float k1 = cscale / den;
+        const float k2 = rn >= p.eps ? dot * cscale / (den * den * fmaxf(rn, 1e-30f)) : 0.f;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) o.g_rel[d] = g_relp[d] * k1 - k2 * rel[d];
+    } else {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) o.g_rel[d] = g_relp[d];
+    }
+    o.g_rel[3] = 0.f;
+    // A self pair (j == i: only_sparse_neighbors with the diagonal in the adjacency, dense all-pairs) has rel = x_i - x_i: its
+    // gradient reaches x_i once with each sign and cancels identically.  Written out as zero -- the two copies would otherwise
+    // travel through two different sums (per source, per neighbour) and, under CoorsNorm (|rel| < eps: a factor 1 / eps = 1e8),
+    // leave rounding noise of order one behind.
+    if (ed.jg == ed.ig) o.g_rel = f32x4{0.f, 0.f, 0.f, 0.f};
+    return o;
+}
+
+// x_i - x_j and |x_i - x_j|^2 of edge e, for the caller's closed-form backward of the distance
+__device__ __forceinline__ void tail_store_rel(const egnn_edge_tail_args& p, int64_t e, const float* rel)
+{
+    *reinterpret_cast<f32x4*>(p.rel_out + e * 4) = f32x4{rel[0], rel[1], rel[2], 0.f};
+    p.dist_out[e] = (rel[0] * rel[0] + rel[1] * rel[1]) + rel[2] * rel[2];
+}
 
 template <bool REDUCE>
 __global__ __launch_bounds__(256) void edge_tail_bwd_kernel(const egnn_edge_tail_args p)
@@ -51,13 +161,9 @@ __global__ __launch_bounds__(256) void edge_tail_bwd_kernel(const egnn_edge_tail
     float* sblk = sm + 64 * TM;                                                                // [64][RLD] g_hid block | [64][RLD] a3 block; later [64][QLD]
     float* sgwe = sblk + 64 * QLD;                                                             // [64] g_w per edge
     const int64_t E = (int64_t)p.B * p.N * p.K;
-    const int64_t e_raw = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool live = e_raw < E;                                               // (lanes behind the last edge compute a copy of it with every gradient zero, and store nothing)
-    const int64_t e = live ? e_raw : E - 1;
-    const int K = p.K, N = p.N;
-    const int64_t ig = e / K;                                                  // global node (b N + i)
-    const int64_t jg = p.idx ? (ig / N) * N + p.idx[e] : (ig / N) * N + (e - ig * K);
-    const bool pm = live && (p.pair_mask ? p.pair_mask[e] != 0 : true);
+    const TailEdge ed = tail_edge(p, (int64_t)blockIdx.x * 256 + threadIdx.x, E);
+    const bool live = ed.live, pm = ed.pm;
+    const int64_t e = ed.e, ig = ed.ig;
     float* wpart = REDUCE ? p.part + ((size_t)blockIdx.x * 4 + wave) * PART : nullptr;      // this wave's row of partial sums
 
     float u[TM], sgu[TM], m[TM];
@@ -75,14 +181,13 @@ __global__ __launch_bounds__(256) void edge_tail_bwd_kernel(const egnn_edge_tail
         sgu[c] = egnn_sigmoid(u[c]);
         m[c] = u[c] * sgu[c];
     }
-    // edge gate (soft_edges, :289-290): m_ij = m0 * gt, gt = sigmoid(gate_w . m0 + gate_b); m0 is rebuilt from u in the backward
-    float gt = 1.f, gtc = 0.f;                    // gate and 1 - gate (as sigmoid(-s): no cancellation where the gate saturates)
+    // edge gate (`tail_gate`); m0 is rebuilt from u in the backward
+    float gt = 1.f, gtc = 0.f;                    // gate and 1 - gate
     if (p.gate_w) {
         float sgate = p.gate_b[0];
 #pragma unroll
         for (int c = 0; c < TM; ++c) sgate = __builtin_fmaf(sgw[c], m[c], sgate);
-        gt = egnn_sigmoid(sgate);
-        gtc = egnn_sigmoid(-sgate);
+        tail_gate(sgate, gt, gtc);
 #pragma unroll
         for (int c = 0; c < TM; ++c) m[c] *= gt;
     }
@@ -96,58 +201,13 @@ __global__ __launch_bounds__(256) void edge_tail_bwd_kernel(const egnn_edge_tail
         for (int c = 0; c < TM; ++c) h = __builtin_fmaf(sW3[t * TM + c], m[c], h);
         w = __builtin_fmaf(sW4[t], egnn_silu(h), w);
     }
-    // relative coordinate, CoorsNorm
-    float rel[3], relp[3], g[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        rel[d] = p.coors[ig * 3 + d] - p.coors[jg * 3 + d];
-        g[d] = p.g_coors_out[ig * 3 + d];
-    }
-    float rn = 0.f, den = 1.f, scale = 1.f;
-    if (p.norm_coors) {
-        rn = sqrtf(rel[0] * rel[0] + rel[1] * rel[1] + rel[2] * rel[2]);
-        den = fmaxf(rn, p.eps);
-        scale = p.scale[0];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) relp[d] = rel[d] / den * scale;
-    } else {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) relp[d] = rel[d];
-    }
-    const float wm = pm ? w : 0.f;
-    const bool clamped = p.clamp >= 0.f && !(wm >= -p.clamp && wm <= p.clamp);
-    const float wc = p.clamp >= 0.f ? fminf(fmaxf(wm, -p.clamp), p.clamp) : wm;
-    const float g_wc = g[0] * relp[0] + g[1] * relp[1] + g[2] * relp[2];
-    const float g_w = (pm && !clamped) ? g_wc : 0.f;
-    float g_relp[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) g_relp[d] = wc * g[d];
-    f32x4 grel;
-    float gsc_e = 0.f;                                                         // this edge's term of d/d CoorsNorm.scale
-    if (p.rel_out && live) {
-        *reinterpret_cast<f32x4*>(p.rel_out + e * 4) = f32x4{rel[0], rel[1], rel[2], 0.f};
-        p.dist_out[e] = (rel[0] * rel[0] + rel[1] * rel[1]) + rel[2] * rel[2];
-    }
-    if (p.norm_coors) {
-        const float dot = g_relp[0] * rel[0] + g_relp[1] * rel[1] + g_relp[2] * rel[2];
-        gsc_e = dot / den;
-        if (!REDUCE && p.g_scale && live) p.g_scale[e] = gsc_e;
-        const float k1 = scale / den;
-        const float k2 = rn >= p.eps ? dot * scale / (den * den * fmaxf(rn, 1e-30f)) : 0.f;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) grel[d] = g_relp[d] * k1 - k2 * rel[d];
-    } else {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) grel[d] = g_relp[d];
-    }
-    grel[3] = 0.f;
-    // A self pair (j == i: only_sparse_neighbors with the diagonal in the adjacency, dense all-pairs) has rel = x_i - x_i: its
-    // gradient reaches x_i once with each sign and cancels identically.  Written out as zero -- the two copies would otherwise
-    // travel through two different sums (per source, per neighbour) and, under CoorsNorm (|rel| < eps: a factor 1 / eps = 1e8),
-    // leave rounding noise of order one behind.
-    if (jg == ig) grel = f32x4{0.f, 0.f, 0.f, 0.f};
+    // the edge's scalar section
+    const TailCoors tc = tail_coors(p, ed, w, p.norm_coors ? p.scale[0] : 1.f);
+    const float g_w = tc.g_w, gsc_e = tc.gsc;
     if (live) {
-        *reinterpret_cast<f32x4*>(p.g_rel + e * 4) = grel;
+        if (p.rel_out) tail_store_rel(p, e, tc.rel);
+        if (!REDUCE && p.norm_coors && p.g_scale) p.g_scale[e] = gsc_e;
+        *reinterpret_cast<f32x4*>(p.g_rel + e * 4) = tc.g_rel;
         if (!REDUCE) p.g_w[e] = g_w;
     }
     if constexpr (REDUCE) {
@@ -172,7 +232,7 @@ __global__ __launch_bounds__(256) void edge_tail_bwd_kernel(const egnn_edge_tail
             for (int c = 0; c < TM; ++c) h = __builtin_fmaf(sW3[t * TM + c], m[c], h);
             const float sg = egnn_sigmoid(h);
             a3v[q] = h * sg;
-            const float gh = g_w * sW4[t] * (sg * (1.0f + h * (1.0f - sg)));
+            const float gh = g_w * sW4[t] * tail_dsilu(h, sg);
             ghv[q] = gh;
 #pragma unroll
             for (int c = 0; c < TM; ++c) gm[c] = __builtin_fmaf(sW3[t * TM + c], gh, gm[c]);
@@ -197,9 +257,9 @@ __global__ __launch_bounds__(256) void edge_tail_bwd_kernel(const egnn_edge_tail
                     accb += gh;
                     accw = __builtin_fmaf(sgwe[ee], a3, accw);
                 }
-                *reinterpret_cast<f32x4*>(wpart + (16 * tb + tt) * TM + 4 * cg) = acc;
-                if (cg == 0) wpart[TH * TM + 16 * tb + tt] = accb;
-                if (cg == 1) wpart[TH * TM + TH + 16 * tb + tt] = accw;
+                *reinterpret_cast<f32x4*>(wpart + PART_W3 + (16 * tb + tt) * TM + 4 * cg) = acc;
+                if (cg == 0) wpart[PART_B3 + 16 * tb + tt] = accb;
+                if (cg == 1) wpart[PART_W4 + 16 * tb + tt] = accw;
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_wave_barrier();
             }
@@ -227,13 +287,11 @@ __global__ __launch_bounds__(256) void edge_tail_bwd_kernel(const egnn_edge_tail
     }
     float gs = 0.f;
     if (p.gate_w) {
-        // through the gate: m = m0 gt  =>  d/d m0 = gm gt + (gm . m0) gt (1 - gt) gate_w,   d/d (gate pre-activation) = (gm . m0) gt (1 - gt)
-        float dot = 0.f;
+        float dot = 0.f;                                                           // gm . m0
 #pragma unroll
         for (int c = 0; c < TM; ++c) dot = __builtin_fmaf(gm[c], u[c] * sgu[c], dot);
         gs = dot * gt * gtc;
-#pragma unroll
-        for (int c = 0; c < TM; ++c) gm[c] = __builtin_fmaf(gs, sgw[c], gm[c] * gt);
+        tail_gate_bwd<TM>(gm, sgw, gs, gt);
         if (!REDUCE && live) p.g_gate[e] = gs;
     }
     f32x4* gup = reinterpret_cast<f32x4*>(p.gU + e * TM);
@@ -244,14 +302,14 @@ __global__ __launch_bounds__(256) void edge_tail_bwd_kernel(const egnn_edge_tail
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const int cc = 4 * q + c;
-            v[c] = gm[cc] * (sgu[cc] * (1.0f + u[cc] * (1.0f - sgu[cc])));
+            v[c] = gm[cc] * tail_dsilu(u[cc], sgu[cc]);
         }
         if (live) gup[q] = v;
 #pragma unroll
         for (int c = 0; c < 4; ++c) { const uint32_t tb = egnn_abs_bits(v[c]); gu_max = gu_max > tb ? gu_max : tb; }
         if constexpr (REDUCE) {
-            // per-edge scalar terms, summed over the wave's edges below: [0, 16) d loss / d u (-> edge_mlp's last bias),
-            // [16, 32) gate term x SiLU(u) (-> d/d gate weight), 32 g_w (-> d/d b4), 33 CoorsNorm.scale term, 34 gate term (-> d/d gate bias)
+            // per-edge scalar terms, summed over the wave's edges below, in the order of PART_Q .. PART: [0, 16) d loss / d u (-> edge_mlp's
+            // last bias), [16, 32) gate term x SiLU(u) (-> d/d gate weight), 32 g_w (-> d/d b4), 33 CoorsNorm.scale term, 34 gate term (-> d/d gate bias)
             *reinterpret_cast<f32x4*>(sblk + lane * QLD + 4 * q) = v;
             *reinterpret_cast<f32x4*>(sblk + lane * QLD + 16 + 4 * q) =
                 f32x4{gs * (u[4 * q] * sgu[4 * q]), gs * (u[4 * q + 1] * sgu[4 * q + 1]), gs * (u[4 * q + 2] * sgu[4 * q + 2]), gs * (u[4 * q + 3] * sgu[4 * q + 3])};
@@ -266,7 +324,7 @@ __global__ __launch_bounds__(256) void edge_tail_bwd_kernel(const egnn_edge_tail
             float acc = 0.f;
 #pragma unroll 8
             for (int ee = 0; ee < 64; ++ee) acc += sblk[ee * QLD + lane];
-            wpart[TH * TM + 2 * TH + lane] = acc;
+            wpart[PART_Q + lane] = acc;
         }
     }
     if (p.amax_gu) {
@@ -367,7 +425,6 @@ __global__ __launch_bounds__(256) void edge_tail_mfma_kernel(const egnn_edge_tai
     float* smm = sa3 + 16 * GLD;                                              // [16 e][16]  post-gate messages
     float* sgwe = smm + 16 * TM;                                              // [16] g_w
     const int64_t E = (int64_t)p.B * p.N * p.K;
-    const int K = p.K, N = p.N;
     float* wpart = p.part + ((size_t)blockIdx.x * 4 + wave) * PART;
     const float gb = p.gate_w ? p.gate_b[0] : 0.f;
     const float b4 = p.b4[0];
@@ -383,12 +440,9 @@ __global__ __launch_bounds__(256) void edge_tail_mfma_kernel(const egnn_edge_tai
 
 #pragma unroll 1
     for (int tt = 0; tt < 4; ++tt) {
-        const int64_t e_raw = (int64_t)blockIdx.x * 256 + wave * 64 + 16 * tt + ee;
-        const bool live = e_raw < E;
-        const int64_t e = live ? e_raw : E - 1;
-        const int64_t ig = e / K;
-        const int64_t jg = p.idx ? (ig / N) * N + p.idx[e] : (ig / N) * N + (e - ig * K);
-        const bool pm = live && (p.pair_mask ? p.pair_mask[e] != 0 : true);
+        const TailEdge ed = tail_edge(p, (int64_t)blockIdx.x * 256 + wave * 64 + 16 * tt + ee, E);
+        const bool live = ed.live, pm = ed.pm;
+        const int64_t e = ed.e, ig = ed.ig;
         const f32x4 u4 = *reinterpret_cast<const f32x4*>(p.u + e * TM + 4 * g);
         f32x4 sgu, m0, m4;
 #pragma unroll
@@ -399,9 +453,7 @@ __global__ __launch_bounds__(256) void edge_tail_mfma_kernel(const egnn_edge_tai
             float ps = 0.f;
 #pragma unroll
             for (int r = 0; r < 4; ++r) ps = __builtin_fmaf(sgw[4 * g + r], m0[r], ps);
-            const float sgate = egnn_column_sum4_reg(ps) + gb;
-            gt = egnn_sigmoid(sgate);
-            gtc = egnn_sigmoid(-sgate);
+            tail_gate(egnn_column_sum4_reg(ps) + gb, gt, gtc);
             m4 = m0 * gt;
         }
         h16x4 mh, ml;
@@ -438,51 +490,11 @@ __global__ __launch_bounds__(256) void edge_tail_mfma_kernel(const egnn_edge_tai
         }
         const float w = egnn_column_sum4_reg(wpartial) + b4;
         // ---- the edge's scalar section (every lane group computes its edge's copy)
-        float rel[3], relp[3], gco[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            rel[d] = p.coors[ig * 3 + d] - p.coors[jg * 3 + d];
-            gco[d] = p.g_coors_out[ig * 3 + d];
-        }
-        float rn = 0.f, den = 1.f;
-        if (p.norm_coors) {
-            rn = sqrtf(rel[0] * rel[0] + rel[1] * rel[1] + rel[2] * rel[2]);
-            den = fmaxf(rn, p.eps);
-#pragma unroll
-            for (int d = 0; d < 3; ++d) relp[d] = rel[d] / den * cscale;
-        } else {
-#pragma unroll
-            for (int d = 0; d < 3; ++d) relp[d] = rel[d];
-        }
-        const float wm = pm ? w : 0.f;
-        const bool clamped = p.clamp >= 0.f && !(wm >= -p.clamp && wm <= p.clamp);
-        const float wc = p.clamp >= 0.f ? fminf(fmaxf(wm, -p.clamp), p.clamp) : wm;
-        const float g_wc = gco[0] * relp[0] + gco[1] * relp[1] + gco[2] * relp[2];
-        const float g_w = (pm && !clamped) ? g_wc : 0.f;
-        float g_relp[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) g_relp[d] = wc * gco[d];
-        f32x4 grel;
-        float gsc_e = 0.f;
-        if (p.norm_coors) {
-            const float dot = g_relp[0] * rel[0] + g_relp[1] * rel[1] + g_relp[2] * rel[2];
-            gsc_e = dot / den;
-            const float k1 = cscale / den;
-            const float k2 = rn >= p.eps ? dot * cscale / (den * den * fmaxf(rn, 1e-30f)) : 0.f;
-#pragma unroll
-            for (int d = 0; d < 3; ++d) grel[d] = g_relp[d] * k1 - k2 * rel[d];
-        } else {
-#pragma unroll
-            for (int d = 0; d < 3; ++d) grel[d] = g_relp[d];
-        }
-        grel[3] = 0.f;
-        if (jg == ig) grel = f32x4{0.f, 0.f, 0.f, 0.f};                          // (self pair: see edge_tail_bwd_kernel)
+        const TailCoors tc = tail_coors(p, ed, w, cscale);
+        const float g_w = tc.g_w, gsc_e = tc.gsc;
         if (live && g == 0) {
-            *reinterpret_cast<f32x4*>(p.g_rel + e * 4) = grel;
-            if (p.rel_out) {
-                *reinterpret_cast<f32x4*>(p.rel_out + e * 4) = f32x4{rel[0], rel[1], rel[2], 0.f};
-                p.dist_out[e] = (rel[0] * rel[0] + rel[1] * rel[1]) + rel[2] * rel[2];
-            }
+            *reinterpret_cast<f32x4*>(p.g_rel + e * 4) = tc.g_rel;
+            if (p.rel_out) tail_store_rel(p, e, tc.rel);
         }
         // ---- coors_mlp backward: gm^T = g_w W3^T q^T; the tile's g_hid / a3 / m / g_w go to LDS for the sums over edges
         f32x4 gmacc = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -492,7 +504,7 @@ __global__ __launch_bounds__(256) void edge_tail_mfma_kernel(const egnn_edge_tai
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float h = hid[tb][r], sg = sgh4[tb][r];
-                q[r] = sW4[16 * tb + 4 * g + r] * (sg * (1.0f + h * (1.0f - sg)));
+                q[r] = sW4[16 * tb + 4 * g + r] * tail_dsilu(h, sg);
                 if constexpr (DROP) q[r] = ((kbits >> (4 * tb + r)) & 1u) ? q[r] * p.drop_inv_keep : 0.f;       // d (dropped hid) / d hid
                 ghv[r] = g_w * q[r];
                 a3v[r] = h * sg;
@@ -518,13 +530,12 @@ __global__ __launch_bounds__(256) void edge_tail_mfma_kernel(const egnn_edge_tai
 #pragma unroll
             for (int r = 0; r < 4; ++r) dp = __builtin_fmaf(gm[r], m0[r], dp);
             gs = egnn_column_sum4_reg(dp) * gt * gtc;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) gm[r] = __builtin_fmaf(gs, sgw[4 * g + r], gm[r] * gt);
+            tail_gate_bwd<4>(gm, sgw + 4 * g, gs, gt);
         }
         f32x4 gu;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            gu[r] = gm[r] * (sgu[r] * (1.0f + u4[r] * (1.0f - sgu[r])));
+            gu[r] = gm[r] * tail_dsilu(u4[r], sgu[r]);
             const uint32_t tbits = egnn_abs_bits(gu[r]);
             gu_max = gu_max > tbits ? gu_max : tbits;
         }
@@ -553,20 +564,20 @@ __global__ __launch_bounds__(256) void edge_tail_mfma_kernel(const egnn_edge_tai
     // ---- this wave's row of partial sums
 #pragma unroll
     for (int c4 = 0; c4 < 4; ++c4)
-        *reinterpret_cast<f32x4*>(wpart + lane * TM + 4 * c4) = f32x4{acc3[4 * c4], acc3[4 * c4 + 1], acc3[4 * c4 + 2], acc3[4 * c4 + 3]};
-    wpart[TH * TM + lane] = accb;
-    wpart[TH * TM + TH + lane] = accw;
+        *reinterpret_cast<f32x4*>(wpart + PART_W3 + lane * TM + 4 * c4) = f32x4{acc3[4 * c4], acc3[4 * c4 + 1], acc3[4 * c4 + 2], acc3[4 * c4 + 3]};
+    wpart[PART_B3 + lane] = accb;
+    wpart[PART_W4 + lane] = accw;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const float a = egnn_row16_sum(s_gu[r]), b = egnn_row16_sum(s_gate[r]);
-        if (ee == 0) { wpart[TH * TM + 2 * TH + 4 * g + r] = a; wpart[TH * TM + 2 * TH + 16 + 4 * g + r] = b; }
+        if (ee == 0) { wpart[PART_Q + 4 * g + r] = a; wpart[PART_GATE_W + 4 * g + r] = b; }
     }
     {
         const float a = egnn_row16_sum(s_gw), b = egnn_row16_sum(s_sc), c = egnn_row16_sum(s_gs);
         if (lane == 0) {
-            wpart[TH * TM + 2 * TH + 32] = a; wpart[TH * TM + 2 * TH + 33] = b; wpart[TH * TM + 2 * TH + 34] = c;
+            wpart[PART_B4] = a; wpart[PART_SCALE] = b; wpart[PART_GATE_B] = c;
 #pragma unroll
-            for (int o = 35; o < 40; ++o) wpart[TH * TM + 2 * TH + o] = 0.f;
+            for (int o = PART_ZERO; o < PART; ++o) wpart[o] = 0.f;
         }
     }
     if (p.amax_gu) {

@@ -95,7 +95,7 @@ def family(inst):
 
 
 def default_split_reaches(inst):
-    """`autograd._edge_contract_fused` under EGNN_BWD_SPLIT=dest (autograd.py:1308-1327): by source with ws_nat (row_pairs where
+    """`autograd._edge_contract_fused` under EGNN_BWD_SPLIT=dest (its two `_ops.edge_bwd_pass` calls): by source with ws_nat (row_pairs where
     16 < K <= 32), by destination with want_w2 -- never a pass without a contraction, never one with both."""
     return family(inst) in ("w2", "ss", "pair")
 

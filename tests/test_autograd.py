@@ -1037,6 +1037,38 @@ def test_native_backward_host_logic_with_emulated_kernels(kw, use_mask, max_grap
         assert float((a.double() - r).abs().max()) <= 2e-4 * scale, (pos, float((a.double() - r).abs().max()), scale)
 
 
+def test_autograd_route_keeps_the_self_pair_out_of_coors_norm():
+    """`_behind_u_autograd` under CoorsNorm (host tensors, m_dim 20): a self pair's x_i - x_i sends +- scale / eps = 1e8-sized terms to x_i
+    that cancel identically; left in the graph they put rounding noise of 9e-3 of its maximum into fp32 d/d coors.  With the self pair's
+    rel detached -- the closed-form kernels write its term as zero -- every gradient is within the host-logic test's 2e-4."""
+    import copy
+    from egnn_pytorch_amd import EGNN, autograd as A
+    kw = dict(dim=8, num_nearest_neighbors=7, m_dim=20, norm_coors=True, soft_edges=True)
+    torch.manual_seed(5)
+    layer = EGNN(**kw)
+    for mod in layer.modules():
+        if isinstance(mod, torch.nn.Linear):
+            torch.nn.init.xavier_normal_(mod.weight)
+    assert A._behind_u_route(layer, 20, 3, False, True) == "autograd"
+    b, n, k = 3, 24, 7
+    g = torch.Generator().manual_seed(6)
+    feats, coors = torch.randn(b, n, 8, generator=g), torch.randn(b, n, 3, generator=g)
+    idx = torch.randint(0, n, (b, n, k), generator=g).to(torch.int32)
+    idx[:, :, 0] = torch.arange(n)[None, :]                                          # the self pair, as the selection always has it
+    rank = torch.rand(b, n, k, generator=g)
+    mask = torch.arange(n)[None] < torch.tensor([n, n - 5, n // 2])[:, None]
+    gn, gc = torch.randn(b, n, 8, generator=g), torch.randn(b, n, 3, generator=g)
+    got = _emulated_backward(layer, feats, coors, mask, idx, rank, 0.8, gn, gc)
+    l64 = copy.deepcopy(layer).double()
+    f, c = feats.double().requires_grad_(True), coors.double().requires_grad_(True)
+    node, co = A.layer_given_neighbors(l64, f, c, None, mask, idx.long(), rank.double(), 0.8)
+    want = torch.autograd.grad([node, co], [f, c] + list(l64.parameters()), [gn.double(), gc.double()], allow_unused=True)
+    for pos, (a, r) in enumerate(zip(got, want)):
+        scale = float(r.abs().max())
+        assert scale > 0, pos
+        assert float((a.double() - r).abs().max()) <= 2e-4 * scale, (pos, float((a.double() - r).abs().max()), scale)
+
+
 def _emulated_case(kw, dtype=torch.float32, frozen=()):
     from egnn_pytorch_amd import EGNN
     torch.manual_seed(5)

@@ -531,3 +531,55 @@ def test_c_layer_forward_refuses_a_graph_beyond_the_edge_kernels_offsets():
                                           ws_bytes, None, None)
     assert call(258112, 1 << 50) == -3 and call(258112, 0) == -3          # EGNN_E_UNSUPPORTED
     assert call(258111, 0) == -2                                          # EGNN_E_SHAPE: the workspace check, behind the guard
+
+
+def _route_cases():
+    """(constructor arguments, coordinate dimension) -> the route of step 1 for (native device, native host, exact): written down from the
+    rule -- standard: m_dim <= 16, coors_mlp hidden <= 64, C = 3, coors_mlp and node_mlp present, native only; closed: m_dim <= 64, on the
+    native path only for device tensors; else autograd."""
+    s, c, a = "standard", "closed", "autograd"
+    rows = []
+    for m in (16, 17, 64, 65):
+        for cdim in (3, 5):
+            wide = m > 64
+            nat_dev = a if wide else (s if (m <= 16 and cdim == 3) else c)
+            rows.append((dict(m_dim=m), cdim, (nat_dev, s if nat_dev == s else a, a if wide else c)))
+    rows.append((dict(m_dim=16, update_coors=False), 3, (c, a, c)))
+    rows.append((dict(m_dim=16, update_feats=False), 3, (c, a, c)))
+    return rows
+
+
+@pytest.mark.parametrize("kw,cdim,want", _route_cases())
+def test_behind_u_route_table(kw, cdim, want):
+    """autograd._behind_u_route: one rule for `_backward_native`, `_backward_exact` and `_dropout_native_ok`."""
+    from egnn_pytorch_amd import EGNN, autograd as A
+    layer = EGNN(dim=8, **kw)
+    m = layer.m_dim
+    if layer.coors_mlp is not None:
+        assert layer.coors_mlp[0].weight.shape[0] == 4 * m           # (the hidden width the rule's "<= 64" is about)
+    got = (A._behind_u_route(layer, m, cdim, True, True), A._behind_u_route(layer, m, cdim, False, True),
+           A._behind_u_route(layer, m, cdim, True, False))
+    assert got == want
+    assert A._behind_u_route(layer, m, cdim, False, False) == want[2]                # (the exact path: the device does not enter)
+    assert {A.ROUTE_STANDARD, A.ROUTE_CLOSED, A.ROUTE_AUTOGRAD} == {"standard", "closed", "autograd"}
+    assert A._dropout_native_ok(layer) == (m <= 64)
+
+
+def test_behind_u_route_wide_coors_mlp():
+    """m_dim <= 16 with a coors_mlp hidden layer beyond the standard tail kernel's 64 columns: not the standard route"""
+    from egnn_pytorch_amd import EGNN, autograd as A
+    layer = EGNN(dim=8, m_dim=16)
+    layer.coors_mlp[0], layer.coors_mlp[3] = torch.nn.Linear(16, 80), torch.nn.Linear(80, 1)
+    assert A._behind_u_route(layer, 16, 3, True, True) == "closed" and A._behind_u_route(layer, 16, 3, False, True) == "autograd"
+
+
+def test_tail_sums_layout():
+    """_ops.TAIL_SUMS, the named columns of the tail kernel's summed `part` row: disjoint, ascending, inside EGNN_TAIL_PART_FLOATS"""
+    from egnn_pytorch_amd import _abi, _ops
+    spans = list(_ops.TAIL_SUMS.values())
+    assert list(_ops.TAIL_SUMS) == ["W3", "b3", "W4", "gU", "gate_w", "b4", "scale", "gate_b"]
+    assert spans[0].start == 0 and all(s.step is None and s.start < s.stop for s in spans)
+    assert all(a.stop <= b.start for a, b in zip(spans, spans[1:]))
+    assert [(s.start, s.stop) for s in spans] == [(0, 1024), (1024, 1088), (1088, 1152), (1152, 1168), (1168, 1184), (1184, 1185),
+                                                  (1185, 1186), (1186, 1187)]
+    assert spans[-1].stop == 1187 <= 1192 == _ops.TAIL_PART_FLOATS == _abi.load().egnn_edge_tail_part_floats()
