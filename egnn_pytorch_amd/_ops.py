@@ -1648,15 +1648,16 @@ def edge_tail_bwd(u16, coors, idx32, pair_mask, g_coors_out, g_msum16, w3p, b3p,
 
 # rounds (of 128 entries) one workgroup of egnn_edge_bwd_pass_f32 streams through its column chunk: short enough that the
 # workgroups of one graph and one chunk (they share the gathered rows) are many and run side by side on an XCD
-ROUNDS_PER_SLAB = int(os.environ.get("EGNN_BWD_ROUNDS_PER_SLAB", "8"))
+ROUNDS_PER_SLAB = 8
 
 
 def edge_bwd_pass(w, proj, idx32, gu16, gu_scale, scal, ent, b, n, k, by_dest, ws_nat=None, want_w2=False, n_slabs=None, row_pairs=False,
-                  drop=None, eid0=0, want_amax=False):
+                  drop=None, eid0=0, want_amax=False, block=0):
     """One pass of egnn_edge_bwd_pass_f32 (include/egnn_hip.h) over the entry list ent (autograd.entry_list).  proj = (B*N, 2 Hp)
     fp32 P_i | P_j rows.  Returns a dict: rows (L / 16, Hp) partial rows, one per tile; with want_w2: w2 = d/d W_2 (16, Hp); with ws_nat (the
     natural-units scalar weights (Hp, S)): ws = d/d W_s (Hp, S) and scal = d/d scalars (E, S) -- the partial arrays of the
-    kernel already summed (fixed order).  row_pairs (by source, 16 < K <= 32, with ws_nat): rows = one row per node (L / 32, Hp)."""
+    kernel already summed (fixed order).  row_pairs (by source, 16 < K <= 32, with ws_nat): rows = one row per node (L / 32, Hp).
+    block: the block of 16 message channels gu16 holds (m_dim > 16: the pass is linear in gU, one call per block) -- its rows of W_2."""
     lib = _abi.load()
     hp, s_in = w["Hp"], w["S"]
     dev = proj.device
@@ -1674,7 +1675,7 @@ def edge_bwd_pass(w, proj, idx32, gu16, gu_scale, scal, ent, b, n, k, by_dest, w
     a.Pi, a.Pj, a.ldp = proj.data_ptr(), proj.data_ptr() + 4 * hp, proj.stride(0)
     a.Wst, a.ws_inv_scale = w["Wst"].data_ptr(), w["ws_inv_scale"]
     a.idx = _ptr(idx32)
-    a.W2Th, a.gU, a.gu_scale = w["W2Th"].data_ptr(), gu16.data_ptr(), gu_scale
+    a.W2Th, a.gU, a.gu_scale = w["W2Th_blocks"][block].data_ptr(), gu16.data_ptr(), gu_scale
     a.inv_scale = 1.0 / (gu_scale * w["w2t_scale"])
     a.scal = scal.data_ptr()
     a.part_rows, a.ld_rows = rows.data_ptr(), hp

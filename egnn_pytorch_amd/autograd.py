@@ -19,8 +19,15 @@ Backward, three paths:
              * the E x H work -- z = P_i + P_j + W_s s, a = SiLU(z), dz = (W2^T gU) SiLU'(z) and their contractions -- on
                egnn_edge_bwd_pass_f32 (csrc/edge_bwd.hip; `_edge_contract_fused`): one pass over the edges grouped by source node
                (d/d P_i, d/d W_s, d/d scalars) and one over the edges sorted by destination (d/d P_j, d/d W_2), everything recomputed
-               and contracted in registers; heads wider than 16 channels: once per block of 16 channels (linear in gU);
-             * the node-level products -- d/d feats, d/d edge_mlp.0, node_mlp -- on the forward's split-f16 GEMM (`_ops.grad_nn / grad_tn`).
+               and contracted in registers; heads wider than 16 channels: once per block of 16 channels (linear in gU;
+               `_edge_contract_blocks`, the block an argument of `_ops.edge_bwd_pass`);
+             * the node-level products -- d/d feats, d/d edge_mlp.0 (`_edge_mlp0_backward`), node_mlp -- on the forward's split-f16 GEMM
+               (`_ops.grad_nn / grad_tn`); host tensors (the CPU tests) on matmuls;
+             * d/d scalars -> coordinates and edge features (`_scalars_to_inputs`: the distance in closed form, else the scalars' own
+               small graph, `_scalars_graph_backward`, which `_backward_exact` shares).
+           Both native backwards start from one `_Start` record.  The four A/B switches of these steps (the distribution of the
+           contractions over the two passes, library GEMMs, a recomputed projection table, the rounds per slab) are retired like the
+           four above -- DESIGN.md section 10 names them: device or host is `is_cuda` alone.
   `_backward_exact` (round 5) -- the layers whose forward runs on the plain kernels (csrc/edge_exact.hip): float64 modules (the reference's
            own training recipe, denoise_sparse.py:11, 23-32), calls answered by the wide-range path (values beyond the split-fp16 range),
            more than 16 per-edge scalars / 8 coordinates / 64 message channels.  The per-edge tail in closed form (through autograd on
@@ -51,12 +58,8 @@ from .sparse_adj import SparseLabels
 # EGNN_NATIVE_BACKWARD=0: always the pure-ATen recompute (the reference implementation of the backward)
 _NATIVE_MODE = os.environ.get("EGNN_NATIVE_BACKWARD", "1")
 _NATIVE = _NATIVE_MODE != "0"
-# which pass of the fused backward carries d/d W_2: "dest" (default), "both" = the by-source pass carries everything (tuning knob)
-_FUSED_SPLIT = os.environ.get("EGNN_BWD_SPLIT", "dest")
-_GRAD_GEMM = os.environ.get("EGNN_BWD_GRAD_GEMM", "1") != "0"          # 0: the node-level gradient products as fp32 library GEMMs
 _NATIVE_EXACT = os.environ.get("EGNN_NATIVE_BACKWARD_EXACT", "1") != "0"   # 0: float64 / wide-range / wide-shape layers on the recompute path
 _EXACT_BWD_BYTES = int(float(os.environ.get("EGNN_EXACT_BWD_GB", "2")) * (1 << 30))   # budget of the a^T / dz^T tables per chunk of graphs
-_KEEP_PROJ = os.environ.get("EGNN_BWD_KEEP_PROJ", "1") != "0"          # 0: the backward recomputes the P_i | P_j table (B N x 2 Hp fp32 less to keep)
 _FUSED_MAX_GRAPHS = 0                 # tests: force the chunking over graphs that very large batches need (0 = by size only)
 
 # activations of the recompute per edge: a few E x H tensors (pre-activation, activation, gradients); 16 GB of the 288 GB
@@ -683,12 +686,12 @@ def _chunk_graphs(layer, n, k, batch):
 def _dropout_native_ok(layer):
     """Training-mode dropout on the native backward: the kernels that re-evaluate the forward's hash masks (egnn_edge_bwd_pass_f32 with
     drop_thr, the two tail kernels, egnn_silu_bwd_drop_f32) cover every shape of the fused forward kernels since round 5 -- heads up to 64
-    channels, coordinate dimensions up to 8 (the generic tail kernel re-evaluates coors_mlp's mask), up to 16 per-edge scalars; the
-    tuning switches that take pieces of the native backward away send the masked layer to the recompute path."""
+    channels, coordinate dimensions up to 8 (the generic tail kernel re-evaluates coors_mlp's mask), up to 16 per-edge scalars;
+    EGNN_TAIL_SCALAR=1 (the per-lane tail kernel, which does not re-evaluate masks) sends the masked layer to the recompute path."""
     # (round 6: layers without coors_mlp / node_mlp -- update_coors=False / update_feats=False -- take the generic tail kernel, which
     # skips the absent module and its mask site; odd `dim`: egnn_silu_bwd_drop_f32 steps its (row, column) pair per element)
-    # (behind u: one of the two kernel routes -- with the gradient GEMMs on, the rule does not depend on the coordinate dimension)
-    return (_GRAD_GEMM and _FUSED_SPLIT == "dest" and _behind_u_route(layer, layer.m_dim, 3, True, True) != ROUTE_AUTOGRAD
+    # (behind u: one of the two kernel routes -- on the device the rule does not depend on the coordinate dimension)
+    return (_behind_u_route(layer, layer.m_dim, 3, True, True) != ROUTE_AUTOGRAD
             and 2 * layer.fourier_features + 1 + layer.edge_dim <= 16 and os.environ.get("EGNN_TAIL_SCALAR", "0") != "1")
 
 
@@ -707,13 +710,12 @@ def _behind_u_route(layer, m, cdim, on_device, native):
     `_backward_native` asks (else `_backward_exact`).
       standard -- m <= 16, coors_mlp hidden width <= 64, 3-D coordinates, coors_mlp and node_mlp present; native only.  Also what host
                   tensors take (the tests, with `_ops.edge_tail_bwd` emulated): there without the kernel's own reductions;
-      closed   -- m <= 64; on the native path only for device tensors (node_mlp runs on the split-f16 gradient GEMMs there, so the
-                  knob that takes those away, EGNN_BWD_GRAD_GEMM=0, takes this route with them);
+      closed   -- m <= 64; on the native path only for device tensors (node_mlp runs on the split-f16 gradient GEMMs there);
       autograd -- what is left: wider heads, host tensors."""
     cm = layer.coors_mlp
     if native and cm is not None and layer.node_mlp is not None and m <= 16 and cm[0].weight.shape[0] <= 64 and cdim == 3:
         return ROUTE_STANDARD
-    if m <= 64 and (not native or (on_device and _GRAD_GEMM)):
+    if m <= 64 and (not native or on_device):
         return ROUTE_CLOSED
     return ROUTE_AUTOGRAD
 
@@ -856,7 +858,7 @@ class EGNNFunction(torch.autograd.Function):
         ctx.save_for_backward(feats, coors, edges if edges is not None else none, mask if mask is not None else none,
                               idx if idx is not None else none, rank if rank is not None else none,
                               u_pre if u_pre is not None else none,
-                              proj[0] if (proj is not None and (_KEEP_PROJ or exact_native)) else none)
+                              proj[0] if proj is not None else none)
         # the projection table as the forward's edge pass read it: P_i as (fp16 hi, fp16 lo) words when pi_split -- the backward turns
         # them into fp32 in place, once (a second backward over a retained graph finds them decoded)
         ctx.proj_words = bool(proj is not None and proj[1])
@@ -1128,6 +1130,16 @@ def _scalars_graph(layer, ch, by_k, want_ge):
     return c, e, rel, scal
 
 
+def _scalars_graph_backward(ch, tail, g_scal, want_ge, g_edges):
+    """Step 4 through `_scalars_graph`: d loss / d scalars (B,N,K,S) -> the chunk's rows of d/d coors (squared distance, fourier terms)
+    and of d/d edges."""
+    sg = torch.autograd.grad([tail.scal], [tail.c] + ([tail.e] if want_ge else []), [g_scal], allow_unused=True)
+    if sg[0] is not None:
+        ch.g_coors_in += sg[0]
+    if want_ge and sg[1] is not None:
+        g_edges[ch.lo:ch.hi] += sg[1]
+
+
 def _self_pairs(ch):
     """(bc, N, K) bool: the pairs whose neighbour is the node itself (dense: the diagonal)"""
     me = torch.arange(ch.n, device=ch.c0.device)
@@ -1165,7 +1177,8 @@ def _behind_u_standard(layer, w, ch, u_all, grads, early, drop, valid_radius, by
     bc, n, k, ec, m, s_in = ch.bc, ch.n, ch.k, ch.ec, layer.m_dim, w["S"]
     f0, c0 = ch.f0, ch.c0
     dev = f0.device
-    reduce = f0.is_cuda                  # (the kernels pool the messages and sum the parameter gradients' terms themselves)
+    on_device = f0.is_cuda               # (the kernels pool the messages and sum the parameter gradients' terms themselves; node_mlp on
+                                         #  the split-f16 GEMMs.  Host tensors: ATen)
     with torch.no_grad():
         u16 = u_all[ch.lo:ch.hi].contiguous()
         pm = _pair_mask(ch.m0, ch.i64, ch.r0, valid_radius)
@@ -1173,7 +1186,7 @@ def _behind_u_standard(layer, w, ch, u_all, grads, early, drop, valid_radius, by
         gate, mm_pre, mm = None, None, None
         if layer.edge_gate is not None:                                              # soft_edges (:289-290)
             gate = (_pad_cached(pads, "gw16", (16,), layer.edge_gate[0].weight.detach()[0]), layer.edge_gate[0].bias.detach().contiguous())
-        if reduce:
+        if on_device:
             m_sum = _ops.edge_pool(u16, gate, pm8, bc, n, k)
         else:
             mm = torch.nn.functional.silu(u16)                                       # (bc, n, k, 16), columns >= m are 0
@@ -1190,12 +1203,12 @@ def _behind_u_standard(layer, w, ch, u_all, grads, early, drop, valid_radius, by
         closed_dist = s_in == 1                       # the distance is the only per-edge scalar: its backward in closed form (caller)
         rel = scal = None
         if closed_dist:
-            if not reduce:                            # (reduce: x_i - x_j and the distance are by-products of the tail kernel)
+            if not on_device:                            # (on the device: x_i - x_j and the distance are by-products of the tail kernel)
                 with torch.no_grad():
                     rel, scal = edge_scalars(layer, c0, None, ch.i64)
         else:
             rel, scal = edge_scalars(layer, c, e, ch.i64, by_k)                      # (only the scalars' graph is used by the caller)
-    if f0.is_cuda and _GRAD_GEMM:
+    if on_device:
         g_f, g_mi = _node_mlp_backward(layer, w, f, m_i[..., :m], ch.g_node, grads, drop, ch.lo * n, overlap=early)
         ch.g_feats += g_f
     else:
@@ -1227,7 +1240,7 @@ def _behind_u_standard(layer, w, ch, u_all, grads, early, drop, valid_radius, by
                      layer.coors_norm.scale.detach() if norm else None, layer.coors_norm.eps if norm else 0.0,
                      layer.coor_weights_clamp_value, bc, n, k)
         bias2 = gu_bits = None
-        if reduce:
+        if on_device:
             gu16, g_rel, sums, rel4, dist, gu_bits = _ops.edge_tail_bwd(*tail_args, gate=gate, reduce=True, want_rel=closed_dist,
                                                                        drop=drop, eid0=ch.lo * n * k)
             gu_bits = _ops.HostRead(gu_bits)                              # (read in step 2, behind the small launches below)
@@ -1322,6 +1335,50 @@ def _behind_u_autograd(layer, ch, u_all, grads, tail_params, drop, valid_radius,
     return _BehindU(_gu_rows(tg[0] if tg[0] is not None else torch.zeros_like(u), ch.ec, m, pad_to), scal, c, e, rel=rel, pm=pm)
 
 
+class _Start:
+    """What `_backward_native` (dtype fp32) and `_backward_exact` (fp32 / float64) start from: the layer and the saved inputs in the
+    compute dtype, the cotangents (zeros for an output nobody used), the zeroed gradient accumulators; `finish` hands them back."""
+
+    def __init__(self, ctx, g_node, g_coors, dtype):
+        self.ctx = ctx
+        self.orig_params = list(ctx.layer.parameters())
+        self.layer = layer = ctx.layer if dtype == torch.float64 else _f32_shadow(ctx.layer)     # (fp32: the layer itself unless it is a half module)
+        feats, coors, edges, self.mask, self.idx32, rank = _unpack(ctx)
+        self.in_dtypes = (feats.dtype, coors.dtype, None if edges is None else edges.dtype)
+        self.feats, self.coors = feats, coors = feats.to(dtype), coors.to(dtype)
+        self.edges = edges = None if edges is None else edges.to(dtype)
+        self.rank = None if rank is None else rank.to(dtype)
+        g_node = None if g_node is None else g_node.to(dtype)
+        g_coors = None if g_coors is None else g_coors.to(dtype)
+        self.k = self.idx32.shape[-1] if self.idx32 is not None else feats.shape[1]
+        params = list(layer.parameters())
+        head = {id(p) for p in layer.edge_mlp.parameters()}
+        self.tail_params = [p for p in params if id(p) not in head]             # (the parameters behind u)
+        # (one zero fill for all parameter gradients: views of a flat buffer)
+        flat = torch.zeros(sum(p.numel() for p in params), dtype=dtype, device=feats.device)
+        self.grads, off = {}, 0
+        for p in params:
+            self.grads[id(p)] = flat[off:off + p.numel()].view(p.shape)
+            off += p.numel()
+        self.g_feats, self.g_coors_in = torch.zeros_like(feats), torch.zeros_like(coors)
+        self.by_k = getattr(ctx, "edges_by_k", False)
+        self.lk = _LookupGrads(ctx, feats.shape[0], feats.shape[1], feats.device) if self.by_k else None     # (edge look-up tables: their gradients per chunk)
+        # (the (B,N,N,edge_dim) input: its gradient only if somebody asked for it)
+        self.want_ge = edges is not None and _need(ctx)[6] and not self.by_k
+        self.g_edges = torch.zeros_like(edges) if self.want_ge else None
+        self.g_node = torch.zeros_like(feats) if g_node is None else g_node
+        self.g_coors = torch.zeros_like(coors) if g_coors is None else g_coors
+        self.drop = getattr(ctx, "drop", None)              # (p, seed) of a training-mode forward: the same hash masks re-evaluated
+
+    def chunk(self, lo, hi):
+        return _Chunk(lo, hi, self.k, self.feats, self.coors, self.edges, self.mask, self.idx32, self.rank, self.g_node, self.g_coors,
+                      self.g_feats, self.g_coors_in)
+
+    def finish(self):
+        return _returned_gradients(self.ctx, self.layer, self.orig_params, self.grads, self.g_feats, self.g_coors_in, self.g_edges, self.lk,
+                                   self.in_dtypes)
+
+
 def _returned_gradients(ctx, layer, orig_params, grads, g_feats, g_coors_in, g_edges, lk, in_dtypes):
     """The tuple a backward path returns, in the layout (layer, order_hint, mask, adj, feats, coors, edges, *params): every gradient
     in its owner's dtype, None where nobody asked or no output depends on the parameter (`_unused_params`)."""
@@ -1349,41 +1406,22 @@ def _backward_exact(ctx, g_node, g_coors):
     from . import _abi, _ops
     dtype = ctx.exact_dtype
     esz = 8 if dtype == torch.float64 else 4
-    orig_params = list(ctx.layer.parameters())
-    layer = ctx.layer if dtype == torch.float64 else _f32_shadow(ctx.layer)
-    feats, coors, edges, mask, idx32, rank = _unpack(ctx)
-    in_dtypes = (feats.dtype, coors.dtype, None if edges is None else edges.dtype)
-    feats, coors = feats.to(dtype), coors.to(dtype)
-    edges = None if edges is None else edges.to(dtype)
-    rank = None if rank is None else rank.to(dtype)
-    params = list(layer.parameters())
-    need = _need(ctx)
-    b, n, dim = feats.shape
-    dev = feats.device
-    k = idx32.shape[-1] if idx32 is not None else n
-    m, cdim = layer.m_dim, coors.shape[-1]
+    st = _Start(ctx, g_node, g_coors, dtype)
+    layer, grads, drop, by_k, want_ge, lk, g_feats = st.layer, st.grads, st.drop, st.by_k, st.want_ge, st.lk, st.g_feats
+    b, n, dim = st.feats.shape
+    dev = st.feats.device
+    k, m, cdim = st.k, layer.m_dim, st.coors.shape[-1]
     s_in = 2 * layer.fourier_features + 1 + layer.edge_dim
     lin0, lin3 = layer.edge_mlp[0], layer.edge_mlp[3]
     h = lin0.weight.shape[0]
-    head = {id(lin0.weight), id(lin0.bias), id(lin3.weight), id(lin3.bias)}
-    tail_params = [p for p in params if id(p) not in head]
-    grads = {id(p): torch.zeros_like(p, dtype=dtype) for p in params}
-    g_feats, g_coors_in = torch.zeros_like(feats), torch.zeros_like(coors)
-    by_k = getattr(ctx, "edges_by_k", False)
-    lk = _LookupGrads(ctx, b, n, dev) if by_k else None                  # (edge look-up tables: their gradients per chunk)
-    want_ge = edges is not None and need[6] and not by_k
-    g_edges = torch.zeros_like(edges) if want_ge else None
-    g_node = torch.zeros_like(feats) if g_node is None else g_node.to(dtype)
-    g_coors = torch.zeros_like(coors) if g_coors is None else g_coors.to(dtype)
     u_all = ctx.saved_tensors[6].view(b, n, k, m)
-    drop = getattr(ctx, "drop", None)                                     # (p, seed) of a training-mode forward: the same hash masks re-evaluated
     proj = ctx.saved_tensors[7]                                           # (B N, 2 hq): [P_i incl. bias | P_j], what the forward's edge pass read
     hq = proj.shape[1] // 2
     w1 = lin0.weight.detach().to(dtype).contiguous()                      # (H, Din): [W_i | W_j | scalar columns]
     w2 = lin3.weight.detach().to(dtype).contiguous()                      # (m, H)
     w_it, w_jt = w1[:, :dim].t().contiguous(), w1[:, dim:2 * dim].t().contiguous()       # (dim, H): B operands of d/d feats
     step = max(1, min(b, int(_EXACT_BWD_BYTES // max(1, 2 * n * k * h * esz))))
-    route = _behind_u_route(layer, m, cdim, feats.is_cuda, False)
+    route = _behind_u_route(layer, m, cdim, st.feats.is_cuda, False)
 
     def node_bwd(ch, m_i, overlap):                                       # (node_mlp on the exact GEMMs, node-level rows)
         g_f, g_mi = _node_mlp_backward_exact(layer, ch.f0.view(ch.bn, dim), m_i.reshape(ch.bn, m), ch.g_node.reshape(ch.bn, dim), grads, drop,
@@ -1391,15 +1429,15 @@ def _backward_exact(ctx, g_node, g_coors):
         return g_f.view(ch.bc, n, dim), g_mi.view(ch.bc, n, m)
     for lo in range(0, b, step):
         hi_ = min(b, lo + step)
-        ch = _Chunk(lo, hi_, k, feats, coors, edges, mask, idx32, rank, g_node, g_coors, g_feats, g_coors_in)
+        ch = st.chunk(lo, hi_)
         bc, ec, bn, f0, c0, e0, i32 = ch.bc, ch.ec, ch.bn, ch.f0, ch.c0, ch.e0, ch.i32
         dl = _ops.dest_lists(i32, bc, n, k, dev)
         # ---- 1. behind u: in closed form (m_dim <= 64), else through autograd
         if route == ROUTE_CLOSED:
             tail = _behind_u_closed(layer, ch, u_all, grads, node_bwd, lambda: dl, drop, ctx.valid_radius, by_k, want_ge, None)
         else:
-            tail = _behind_u_autograd(layer, ch, u_all, grads, tail_params, drop, ctx.valid_radius, by_k, want_ge, None, False)
-        g_u, scal, c, e = tail.g_u, tail.scal, tail.c, tail.e
+            tail = _behind_u_autograd(layer, ch, u_all, grads, st.tail_params, drop, ctx.valid_radius, by_k, want_ge, None, False)
+        g_u, scal = tail.g_u, tail.scal
         with torch.no_grad():
             # ---- 2. the E x H work
             a_t = _ops.empty(h, ec, dtype=dtype, device=dev)
@@ -1435,12 +1473,8 @@ def _backward_exact(ctx, g_node, g_coors):
             if lk is not None:                                            # the edge columns of d/d scalars -> the tables
                 lk.add(lo, hi_, i32, n, k, g_scal[:, s_in - layer.edge_dim:])
         # ---- 4. d loss / d scalars -> coordinates (squared distance, fourier terms) and edge features
-        sg = torch.autograd.grad([scal], [c] + ([e] if want_ge else []), [g_scal.view_as(scal)], allow_unused=True)
-        if sg[0] is not None:
-            g_coors_in[lo:hi_] += sg[0]
-        if want_ge and sg[1] is not None:
-            g_edges[lo:hi_] += sg[1]
-    return _returned_gradients(ctx, layer, orig_params, grads, g_feats, g_coors_in, g_edges, lk, in_dtypes)
+        _scalars_graph_backward(ch, tail, g_scal.view_as(scal), want_ge, st.g_edges)
+    return st.finish()
 
 
 def _unused_params(layer, ctx=None):
@@ -1530,49 +1564,44 @@ def entry_list(eids, keys, n_keys):
     return ent, seg
 
 
-def _edge_contract_fused(layer, w, f2d, c0, e0, sc2, i32, gu16, gu_scale, w_s, bc, n, k, pi_split, dest_lists=None, proj=None, drop=None, eid0=0):
-    """egnn_edge_bwd_pass_f32 (csrc/edge_bwd.hip) twice -- entries grouped by source node, then by neighbour: z, SiLU(z) and dz
-    are recomputed and contracted in registers, nothing of size E x H reaches memory.
+def _edge_contract_fused(layer, w, f2d, c0, e0, sc2, i32, gu16, gu_scale, w_s, bc, n, k, pi_split, dest_lists=None, proj=None, drop=None, eid0=0,
+                         block=0):
+    """Step 2: egnn_edge_bwd_pass_f32 (csrc/edge_bwd.hip) twice -- entries grouped by source node, then by neighbour: z, SiLU(z) and dz
+    are recomputed and contracted in registers, nothing of size E x H reaches memory.  The contractions over all edges ride along, each
+    pass keeping its accumulators in registers: d/d W_s and d/d scalars by source, d/d W_2 by destination.  gu16: the (E, 16) columns of
+    gU of message channels 16 block .. 16 block + 15.
     Returns d/d P_i (rows, Hp), d/d P_j (rows, Hp), d/d W_s (Hp, S), d/d scalars (E, S), d/d W_2 (16, Hp)."""
     from . import _ops
     dev = f2d.device
+    on_device = dev.type == "cuda"                            # (the max |.| by-products: the scales of step 3's GEMM operands)
     ec = bc * n * k
     if proj is None:
         proj = _edge_tables(layer, w, f2d, False)
+    # by source every node has ceil(K / 16) tiles: one IS the node's row, two (16 < K <= 32) are summed inside the kernel (row_pairs),
+    # more go through the gather-sum
     ent, seg = entry_list(torch.arange(ec, device=dev), None, bc * n)
-    # the contractions over all edges ride along: d/d W_s and d/d scalars with the first pass, d/d W_2 with the second (each keeps
-    # its accumulators in registers; one pass carrying both drops from 3 to 2 workgroups per CU)
-    s_first = _FUSED_SPLIT != "src"                          # ("src": d/d W_2 with the by-source pass, d/d W_s and d/d scalars with the other)
-    want_w2_first = _FUSED_SPLIT == "src" or (_FUSED_SPLIT == "both" and w["S"] == 1)
-    # by source every node has ceil(K / 16) tiles: two (16 < K <= 32) are summed inside the kernel, one IS the node's row -- no gather-sum
-    pairs = 16 < k <= 32 and s_first and not want_w2_first
-    o = _ops.edge_bwd_pass(w, proj, i32, gu16, gu_scale, sc2, ent, bc, n, k, by_dest=False, ws_nat=w_s if s_first else None,
-                           want_w2=want_w2_first, row_pairs=pairs, drop=drop, eid0=eid0, want_amax=(pairs or k <= 16) and dev.type == "cuda")
-    g_ws, g_scal, g_w2 = o.get("ws"), o.get("scal"), o.get("w2")
-    if pairs or k <= 16:
+    blk = dict(block=block) if block else {}                  # (the first block is the pass's default: one block, the call of a 16-channel head)
+    o = _ops.edge_bwd_pass(w, proj, i32, gu16, gu_scale, sc2, ent, bc, n, k, by_dest=False, ws_nat=w_s, want_w2=False, row_pairs=16 < k <= 32,
+                           drop=drop, eid0=eid0, want_amax=k <= 32 and on_device, **blk)
+    g_ws, g_scal = o["ws"], o["scal"]
+    if k <= 32:
         gz_i = o["rows"][:bc * n]
         if o.get("amax_bits") is not None:
             gz_i.amax_bits = _ops.HostRead(o["amax_bits"])   # (max |d/d P_i| as a by-product of the pass; read behind THIS pass)
     else:
-        ident = torch.arange(o["rows"].shape[0], device=dev)
-        gz_i = _ops.rows_gather_sum(o["rows"], ident, seg, bc * n)
-    del o
+        gz_i = _ops.rows_gather_sum(o["rows"], torch.arange(o["rows"].shape[0], device=dev), seg, bc * n)
+    del o, ent, seg                                           # (the by-source list is E words: not kept through the second pass)
     if dest_lists is None:
         dest_lists = _ops.dest_lists(i32, bc, n, k, dev)                 # (dense: destination = k)
-    ent, seg = dest_lists.ent, dest_lists.tile_seg
-    o = _ops.edge_bwd_pass(w, proj, i32, gu16, gu_scale, sc2, ent, bc, n, k, by_dest=True, ws_nat=None if s_first else w_s, want_w2=g_w2 is None,
-                           drop=drop, eid0=eid0)
-    if g_w2 is None:
-        g_w2 = o["w2"]
-    if not s_first:
-        g_ws, g_scal = o["ws"], o["scal"]
+    o = _ops.edge_bwd_pass(w, proj, i32, gu16, gu_scale, sc2, dest_lists.ent, bc, n, k, by_dest=True, ws_nat=None, want_w2=True,
+                           drop=drop, eid0=eid0, **blk)
     ident = torch.arange(o["rows"].shape[0], device=dev)
-    if dev.type == "cuda":
-        gz_j, bits = _ops.rows_gather_sum(o["rows"], ident, seg, bc * n, want_amax=True)
+    if on_device:
+        gz_j, bits = _ops.rows_gather_sum(o["rows"], ident, dest_lists.tile_seg, bc * n, want_amax=True)
         gz_j.amax_bits = _ops.HostRead(bits)                  # (max |d/d P_j| as a by-product: the scale of its gradient GEMM operands)
     else:
-        gz_j = _ops.rows_gather_sum(o["rows"], ident, seg, bc * n)
-    return gz_i, gz_j, g_ws, g_scal, g_w2
+        gz_j = _ops.rows_gather_sum(o["rows"], ident, dest_lists.tile_seg, bc * n)
+    return gz_i, gz_j, g_ws, g_scal, o["w2"]
 
 
 def _node_mlp_backward(layer, w, f, m_i, g_out, grads_by_id, drop=None, row0=0, overlap=None):
@@ -1698,6 +1727,105 @@ def check_fused_training_shape(layer, b, n, k):
         raise FusedBackwardLimit(_fused_limit_message(b, n, k, hp))
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# Steps 2 - 4 of `_backward_native`, "ahead of u": the E x H passes (`_edge_contract_blocks` over `_edge_contract_fused`), the node-level
+# products of edge_mlp's first Linear (`_edge_mlp0_backward`), d/d scalars -> coordinates / edge features (`_scalars_to_inputs`).
+def _edge_contract_blocks(layer, w, ch, tail, w_s, pi_split, dest_lists, proj, drop):
+    """Step 2 for a chunk: `_edge_contract_fused` once per block of 16 message channels that holds real ones -- dz = (W2^T gU) SiLU'(z)
+    and every contraction of it are linear in gU, so the blocks' results are added; d/d W_2 is per block anyway (m_dim 33 .. 48 has four
+    blocks in u -- the forward's NB = 4 -- but the fourth is all padding: two passes that would add exact zeros, its rows of d/d W_2 are 0).
+    Returns d/d P_i, d/d P_j (rows, Hp), d/d W_s (Hp, S), d/d scalars (E, S), d/d W_2 (blocks of u x 16, Hp)."""
+    from . import _ops, _weights
+    gu16, pm = tail.g_u, tail.pm
+    amax = _ops.bits_to_floats(tail.gu_bits)[0] if tail.gu_bits is not None else _ops.absmax(gu16)
+    gu_scale = _weights.pow2_scale(amax) if amax > 0 else 1.0
+    nblk = (layer.m_dim + 15) // 16
+    with torch.no_grad():
+        sc2 = tail.scal.detach().reshape(ch.ec, w["S"])
+        if pm is not None:
+            # Pairs the masks remove carry gU = 0, so whatever z they have they add exact zeros -- as long as SiLU(z) is finite where
+            # the pass holds it: as fp16 x 2^6 for d/d W_2, i.e. up to 1023.  A padded node's neighbours are the first K nodes wherever
+            # they are, so its |x_i - x_j|^2 (and with it z) is not bounded by the real pairs': 0 x inf was a NaN in d/d W_2.  Their
+            # scalars are read as 0 instead.
+            sc2 = sc2.masked_fill(~pm.reshape(ch.ec, 1), 0.0)
+        sc2 = sc2.contiguous()
+        parts = [_edge_contract_fused(layer, w, ch.f0.view(ch.bn, -1), ch.c0, ch.e0, sc2, ch.i32,
+                                      gu16 if nblk == 1 else gu16[:, 16 * blk:16 * blk + 16].contiguous(), gu_scale, w_s, ch.bc, ch.n, ch.k,
+                                      pi_split, dest_lists, proj, drop, ch.lo * ch.n * ch.k, blk) for blk in range(nblk)]
+        if nblk == 1:                                       # (the pass's own tensors, with their max |.| words)
+            return parts[0]
+        # (in this order: the sums' bits)
+        gz_i, gz_j, g_ws, g_scal = (sum(p[q] for p in parts[1:]) + parts[0][q] for q in range(4))
+        g_w2 = torch.cat([p[4] for p in parts] + [torch.zeros_like(parts[0][4])] * (gu16.shape[1] // 16 - nblk), dim=0)
+    return gz_i, gz_j, g_ws, g_scal, g_w2
+
+
+def _edge_mlp0_backward(layer, w, ch, gz_i, gz_j, g_ws, hr_f, grads):
+    """Step 3, the node-level products of edge_mlp's first Linear from the per-node sums d/d P_i, d/d P_j (rows, Hp) and feats:
+    d/d feats = dP_i W_i + dP_j W_j (added to the chunk's rows), d/d W_i = dP_i^T feats, d/d W_j = dP_j^T feats, d/d b_1 = column sums of
+    dP_i; d/d W_s (Hp, S) goes to its columns.  Everything works on the contiguous (rows, Hp) buffers the kernel wrote, the weights zero
+    padded to the kernel's hidden width Hp (slicing [:, :H] first would copy 17 GB per use at the north-star shape).  On the device:
+    the forward's split-f16 matrix-core GEMM (operands pre-scaled by powers of two, the weight gradients split-K over the B N nodes with
+    the parts summed in fixed order; hr_f: HostRead of max |feats|) -- the fp32 library GEMMs they replace ran at 60 - 130 TFLOP/s.  Host
+    tensors (the CPU tests): plain matmuls."""
+    from . import _ops
+    lin0 = layer.edge_mlp[0]
+    dim, h = ch.f0.shape[-1], w["H"]
+    f2d = ch.f0.view(ch.bn, dim)
+    gw1 = grads[id(lin0.weight)]
+    with torch.no_grad():
+        if f2d.is_cuda:
+            # (each matrix: one absmax, one read for its plain and transposed images; feats^T split once for both weight gradients)
+            # (launch order: everything of d/d P_i first -- its max |.| word was written by the by-source pass, long finished -- so that
+            # the device is busy with it while the host waits for the word of d/d P_j, which the last kernel queued above writes)
+            ib, jb = getattr(gz_i, "amax_bits", None), getattr(gz_j, "amax_bits", None)
+            op_i = _ops.GradOperand(gz_i, amax=None if ib is None else _ops.bits_to_floats(ib)[0], colsum=True)
+            gb1 = op_i.colsum
+            t = _ops.grad_nn(op_i, w["WiT_split"], dim, name="bwd_dfeats")
+            f_op = _ops.grad_tn_operand(f2d, None if hr_f is None else hr_f.floats()[0])
+            gw1[:, :dim] += _ops.grad_tn(op_i, f2d, name="bwd_dw1", x_operand=f_op)[:h]
+            del op_i
+            op_j = _ops.GradOperand(gz_j, amax=None if jb is None else _ops.bits_to_floats(jb)[0])
+            t = _ops.grad_nn(op_j, w["WjT_split"], dim, residual=t, name="bwd_dfeats")
+            ch.g_feats += t.view(ch.bc, ch.n, dim)
+            gw1[:, dim:2 * dim] += _ops.grad_tn(op_j, f2d, name="bwd_dw1", x_operand=f_op)[:h]
+        else:
+            pads, w1 = w["bwd_pads"], lin0.weight.detach()
+            w_i = _pad_cached(pads, "w_i", (w["Hp"], dim), w1[:, :dim])
+            w_j = _pad_cached(pads, "w_j", (w["Hp"], dim), w1[:, dim:2 * dim])
+            ch.g_feats += (gz_i @ w_i + gz_j @ w_j).view(ch.bc, ch.n, dim)
+            gw1[:, :dim] += _tn(gz_i, f2d)[:h]
+            gw1[:, dim:2 * dim] += _tn(gz_j, f2d)[:h]
+            gb1 = gz_i.sum(dim=0)
+        gw1[:, 2 * dim:] += g_ws[:h]
+        grads[id(lin0.bias)] += gb1[:h]
+
+
+def _scalars_to_inputs(ch, tail, g_scal, dest_lists, want_ge, g_edges):
+    """Step 4: d loss / d scalars (B,N,K,S) -> coordinates (through d = |x_i - x_j|^2 and the fourier terms) and edge features: onto
+    step 1's d loss / d (x_i - x_j) in closed form where the distance is the only scalar, else through the scalars' own small graph;
+    then d loss / d (x_i - x_j), where step 1 left it to the caller, to the coordinates at both ends."""
+    from . import _ops
+    g_rel, rel, bc, n, k = tail.g_rel, tail.rel, ch.bc, ch.n, ch.k
+    if tail.closed_dist:
+        with torch.no_grad():                                   # d = |rel|^2:  d loss / d rel += 2 g_d rel
+            if rel.shape[-1] == 4:                              # (the tail kernel's (E, 4) rows, 4th column 0)
+                g_rel.addcmul_(g_scal.reshape(ch.ec, 1), rel, value=2.0)
+            else:
+                g_rel[:, :3] += (2.0 * g_scal.reshape(ch.ec, 1)) * rel.reshape(ch.ec, 3)
+    else:
+        _scalars_graph_backward(ch, tail, g_scal, want_ge, g_edges)
+    if g_rel is not None:
+        # rel = x_i - x_j reaches the coordinates at the source (sum over a node's edges) and, negated, at the neighbour
+        # (fixed-order gather over the edges sorted by destination)
+        with torch.no_grad():
+            ch.g_coors_in += g_rel.view(bc, n, k, 4).sum(dim=2)[..., :3]
+            if ch.i64 is None:
+                ch.g_coors_in -= g_rel.view(bc, n, n, 4).sum(dim=1)[..., :3]
+            else:
+                ch.g_coors_in -= _ops.rows_gather_sum(g_rel, dest_lists.order, dest_lists.seg, bc * n).view(bc, n, 4)[..., :3]
+
+
 def _backward_native(ctx, g_node, g_coors):
     """The backward on the HIP kernels (module docstring), per chunk of graphs:
        1. behind u = ctx.u_pre (edge_mlp's second Linear, written by the forward kernel), on the route `_behind_u_route` names:
@@ -1705,56 +1833,27 @@ def _backward_native(ctx, g_node, g_coors):
           form on egnn_edge_tail_bwd_f32, which also sums its parameter gradients), `_behind_u_closed` (wider heads, other coordinate
           dimensions: egnn_edge_tail_exact_bwd_f32) or `_behind_u_autograd` (`layer_tail`: host tensors)
           ->  gU = d loss / d u, d loss / d (x_i - x_j), those modules' parameter gradients;
-       2. the E x H work on egnn_edge_bwd_pass_f32 (`_edge_contract_fused`: by source and by destination, everything recomputed
-          and contracted in registers)
+       2. the E x H work on egnn_edge_bwd_pass_f32 (`_edge_contract_blocks`: by source and by destination, everything recomputed and
+          contracted in registers, once per block of 16 message channels)
           ->  d/d P_i, d/d P_j per node, d/d W_s, d/d scalars, d/d W_2;
-       3. node-level products: d/d feats, d/d W_i, W_j, b_1 from the per-node sums and feats; d/d scalars -> coordinates (closed
-          form when the distance is the only scalar, the scalars' own small graph otherwise) and edge features.
+       3. the node-level products of edge_mlp's first Linear (`_edge_mlp0_backward`): d/d feats, d/d W_i, W_j, b_1 from the per-node sums
+          and feats;
+       4. d/d scalars -> coordinates (closed form when the distance is the only scalar, the scalars' own small graph otherwise) and edge
+          features (`_scalars_to_inputs`).
     Every sum over edges has a fixed order.  Chunks: the kernels' tables stay below 2 GB (signed 32-bit offsets): `_fused_graphs_per_chunk`."""
-    from . import _abi, _ops, _weights
+    from . import _ops, _weights
     w = ctx.layer.packed_weights()
-    orig_params = list(ctx.layer.parameters())
-    layer = _f32_shadow(ctx.layer)                       # (the layer itself unless it is a float64 / half module)
-    feats, coors, edges, mask, idx32, rank = _unpack(ctx)
-    in_dtypes = (feats.dtype, coors.dtype, None if edges is None else edges.dtype)
-    feats, coors = feats.float(), coors.float()
-    edges = None if edges is None else edges.float()
-    g_node = None if g_node is None else g_node.float()
-    g_coors = None if g_coors is None else g_coors.float()
-    params = list(layer.parameters())
-    need = _need(ctx)                                    # (layer, order_hint, mask, adj, feats, coors, edges, *params)
-    b, n, dim = feats.shape
-    k = idx32.shape[-1] if idx32 is not None else n
-    m = layer.m_dim
-    h, hp, s_in = w["H"], w["Hp"], w["S"]
+    st = _Start(ctx, g_node, g_coors, torch.float32)
+    layer, grads, drop, by_k, want_ge = st.layer, st.grads, st.drop, st.by_k, st.want_ge
+    b, n, dim = st.feats.shape
+    k, m, h, hp, s_in = st.k, layer.m_dim, w["H"], w["Hp"], w["S"]
+    dev = st.feats.device
+    on_device = dev.type == "cuda"                       # (host tensors -- the CPU tests -- take the ATen body of every step)
     lin0, lin3 = layer.edge_mlp[0], layer.edge_mlp[3]
-    head = {id(lin0.weight), id(lin0.bias), id(lin3.weight), id(lin3.bias)}
-    tail_params = [p for p in params if id(p) not in head]
-    # (one zero fill for all parameter gradients: views of a flat buffer)
-    flat = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=feats.device)
-    grads_by_id, off = {}, 0
-    for p in params:
-        grads_by_id[id(p)] = flat[off:off + p.numel()].view(p.shape)
-        off += p.numel()
-    g_feats = torch.zeros_like(feats)
-    g_coors_in = torch.zeros_like(coors)
-    by_k = getattr(ctx, "edges_by_k", False)
-    lk = _LookupGrads(ctx, b, n, feats.device) if by_k else None        # (edge look-up tables: their gradients per chunk)
-    want_ge = edges is not None and need[6] and not by_k    # (the (B,N,N,edge_dim) input: its gradient only if somebody asked for it)
-    g_edges = torch.zeros_like(edges) if want_ge else None
-    if g_node is None:
-        g_node = torch.zeros_like(feats)
-    if g_coors is None:
-        g_coors = torch.zeros_like(coors)
     mp = 16 * _weights.m_blocks(m)                       # u rows: whole 16-channel blocks, pad channels 0
     u_all = ctx.saved_tensors[6].view(b, n, k, mp)
-    drop = getattr(ctx, "drop", None)                    # (p, seed) of a training-mode forward (_dropout_native_ok), else None
-    # (egnn_edge_bwd_pass_f32: up to 16 per-edge scalars -- beyond five with the all-edge contractions split over the two passes)
-    fused = (s_in <= 5 or (s_in <= 16 and _FUSED_SPLIT == "dest" and "WsTh" in w))
-    if not fused:
-        raise NotImplementedError("the native backward carries more than five per-edge scalars only with EGNN_BWD_SPLIT=dest (the default)")
     proj_all = None
-    if len(ctx.saved_tensors) > 7 and ctx.saved_tensors[7].numel() and fused:
+    if len(ctx.saved_tensors) > 7 and ctx.saved_tensors[7].numel():
         proj_all = ctx.saved_tensors[7]                                   # (B N, 2 Hp): what the forward's edge pass read (P_i still as
                                                                           # (hi, lo) words when ctx.proj_words: decoded in `early` below)
     # nothing of size E x H: graphs are only chunked to keep the P table and the partial rows below 2 GB and E below 2^31
@@ -1764,31 +1863,22 @@ def _backward_native(ctx, g_node, g_coors):
         raise FusedBackwardLimit(_fused_limit_message(b, n, k, hp))
     if _FUSED_MAX_GRAPHS > 0:
         step = min(step, _FUSED_MAX_GRAPHS)
-    # the first Linear's blocks, zero padded to the kernel's hidden width Hp: everything below works on the contiguous
-    # (E, Hp) buffers the kernel wrote (slicing [:, :H] first would copy 17 GB per use at the north-star shape)
     # (padded copies of parameters are kept with the packed weights: `w` is rebuilt whenever a parameter changes, so once per
     # optimizer step instead of a dozen small launches per backward)
     pads = w.get("bwd_pads")
-    if pads is None or pads["device"] != feats.device:
-        pads = w["bwd_pads"] = {"device": feats.device}
+    if pads is None or pads["device"] != dev:
+        pads = w["bwd_pads"] = {"device": dev}
     w_s = _pad_cached(pads, "w_s", (hp, lin0.weight.shape[1] - 2 * dim), lin0.weight.detach()[:, 2 * dim:])
-    w_i = w_j = None
-    if not (feats.is_cuda and _GRAD_GEMM):               # (host tensors -- the CPU tests: plain matmuls instead of the split-f16 GEMM)
-        w1p = torch.zeros(hp, lin0.weight.shape[1], dtype=torch.float32, device=feats.device)
-        w1p[:h] = lin0.weight.detach()
-        w_i, w_j = w1p[:, :dim].contiguous(), w1p[:, dim:2 * dim].contiguous()
     pi_split = k >= 6
-    route = _behind_u_route(layer, m, coors.shape[-1], feats.is_cuda, True)
+    route = _behind_u_route(layer, m, st.coors.shape[-1], on_device, True)
 
     def node_bwd(ch, m_i, overlap):                          # (node_mlp on the split-f16 GEMMs, `overlap` queued behind its SiLU pass)
-        return _node_mlp_backward(layer, w, ch.f0.detach().requires_grad_(True), m_i, ch.g_node, grads_by_id, drop, ch.lo * n, overlap=overlap)
+        return _node_mlp_backward(layer, w, ch.f0.detach().requires_grad_(True), m_i, ch.g_node, grads, drop, ch.lo * n, overlap=overlap)
     w2_finite = ctx.w2_finite = []
     for lo in range(0, b, step):
-        hi_ = min(b, lo + step)
-        ch = _Chunk(lo, hi_, k, feats, coors, edges, mask, idx32, rank, g_node, g_coors, g_feats, g_coors_in)
-        bc, ec, f0, c0, e0, i32, i64 = ch.bc, ch.ec, ch.f0, ch.c0, ch.e0, ch.i32, ch.i64
+        ch = st.chunk(lo, min(b, lo + step))
         dest_lists = None
-        hr_f = _ops.absmax_async(f0.view(bc * n, dim)) if (f0.is_cuda and _GRAD_GEMM) else None      # (read in step 3)
+        hr_f = _ops.absmax_async(ch.f0.view(ch.bn, dim)) if on_device else None      # (read in step 3)
 
         def early():
             """Launches that depend on the saved inputs only -- P_i decoded in place (once), the edges sorted by destination: queued where
@@ -1797,118 +1887,34 @@ def _backward_native(ctx, g_node, g_coors):
             if proj_all is not None and ctx.proj_words:
                 _ops.unsplit_words_(proj_all, hp)
                 ctx.proj_words = False
-            if dest_lists is None and (i32 is not None or route != ROUTE_STANDARD):
-                dest_lists = _ops.dest_lists(i32, bc, n, k, feats.device)                     # (shared by the tail and the E x H passes)
+            if dest_lists is None and (ch.i32 is not None or route != ROUTE_STANDARD):
+                dest_lists = _ops.dest_lists(ch.i32, ch.bc, n, k, dev)                        # (shared by the tail and the E x H passes)
             return dest_lists
         # ---- 1. behind u: gU = d loss / d u, d loss / d (x_i - x_j) or its share of d/d coors, the parameter gradients of that part
         if route == ROUTE_STANDARD:
-            tail = _behind_u_standard(layer, w, ch, u_all, grads_by_id, early, drop, ctx.valid_radius, by_k, want_ge)
+            tail = _behind_u_standard(layer, w, ch, u_all, grads, early, drop, ctx.valid_radius, by_k, want_ge)
         elif route == ROUTE_CLOSED:
-            tail = _behind_u_closed(layer, ch, u_all, grads_by_id, node_bwd, early, drop, ctx.valid_radius, by_k, want_ge, mp)
+            tail = _behind_u_closed(layer, ch, u_all, grads, node_bwd, early, drop, ctx.valid_radius, by_k, want_ge, mp)
         else:
-            tail = _behind_u_autograd(layer, ch, u_all, grads_by_id, tail_params, drop, ctx.valid_radius, by_k, want_ge, mp, True)
-        gu16, scal, c, e, rel, g_rel, closed_dist, bias2, gu_bits, pm = tail
+            tail = _behind_u_autograd(layer, ch, u_all, grads, st.tail_params, drop, ctx.valid_radius, by_k, want_ge, mp, True)
         # ---- 2. the E x H work: d/d P_i, d/d P_j (per node), d/d W_s, d/d scalars, d/d W_2
         early()
-        amax = _ops.bits_to_floats(gu_bits)[0] if gu_bits is not None else _ops.absmax(gu16)
-        gu_scale = _weights.pow2_scale(amax) if amax > 0 else 1.0
+        gz_i, gz_j, g_ws, g_scal, g_w2 = _edge_contract_blocks(layer, w, ch, tail, w_s, pi_split, dest_lists,
+                                                               None if proj_all is None else proj_all[lo * n:ch.hi * n], drop)
         with torch.no_grad():
-            f2d = f0.view(bc * n, dim)
-            sc2 = scal.detach().reshape(ec, s_in)
-            if pm is not None:
-                # Pairs the masks remove carry gU = 0, so whatever z they have they add exact zeros -- as long as SiLU(z) is finite where
-                # the pass holds it: as fp16 x 2^6 for d/d W_2, i.e. up to 1023.  A padded node's neighbours are the first K nodes wherever
-                # they are, so its |x_i - x_j|^2 (and with it z) is not bounded by the real pairs': 0 x inf was a NaN in d/d W_2.  Their
-                # scalars are read as 0 instead.
-                sc2 = sc2.masked_fill(~pm.reshape(ec, 1), 0.0)
-            sc2 = sc2.contiguous()
-            contract = _edge_contract_fused
-            proj = None if proj_all is None else proj_all[lo * n:hi_ * n]
-            if drop is not None and mp == 16:
-                assert fused                                                           # (_dropout_native_ok)
-                gz_i, gz_j, g_ws, g_scal, g_w2 = contract(layer, w, f2d, c0, e0, sc2, i32, gu16, gu_scale, w_s, bc, n, k, pi_split, dest_lists, proj,
-                                                          drop, lo * n * k)
-            elif mp == 16:
-                gz_i, gz_j, g_ws, g_scal, g_w2 = contract(layer, w, f2d, c0, e0, sc2, i32, gu16, gu_scale, w_s, bc, n, k, pi_split, dest_lists, proj)
-            else:
-                # m_dim > 16: dz = (W2^T gU) SiLU'(z) and every contraction of it are linear in gU, so the passes run once per block of
-                # 16 message channels (its columns of gU, its rows of W2) and the results are added; d/d W_2 is per block anyway
-                if dest_lists is None and i32 is not None:
-                    dest_lists = _ops.dest_lists(i32, bc, n, k, feats.device)
-                parts = []
-                # (only blocks that hold real channels: m_dim 33 .. 48 has mp = 64 -- the forward's NB = 4 -- but its fourth block of gU
-                # and W2 is all padding, a by-source + by-destination pass that would add exact zeros)
-                nblk = (m + 15) // 16
-                try:
-                    for blk in range(nblk):
-                        w["W2Th"], w["w2_block"] = w["W2Th_blocks"][blk], blk   # (in place: what the passes cache in `w` -- bwd_pads -- survives;
-                                                                                #  w2_block: read by the CPU tests' kernel emulation)
-                        parts.append(contract(layer, w, f2d, c0, e0, sc2, i32, gu16[:, 16 * blk:16 * blk + 16].contiguous(), gu_scale, w_s, bc, n,
-                                              k, pi_split, dest_lists, proj, drop, lo * n * k))       # (the mask of z: the same for every block)
-                finally:
-                    w["W2Th"] = w["W2Th_blocks"][0]
-                    w.pop("w2_block", None)
-                gz_i, gz_j, g_ws, g_scal = (sum(p[q] for p in parts[1:]) + parts[0][q] for q in range(4))
-                g_w2 = torch.cat([p[4] for p in parts] + [torch.zeros_like(parts[0][4])] * (mp // 16 - nblk), dim=0)
-                del parts
-            # ---- 3. node-level products: d/d feats = dP_i W_i + dP_j W_j, d/d W_i = dP_i^T feats, d/d W_j = dP_j^T feats.  On the
-            # device: the forward's split-f16 matrix-core GEMM (operands pre-scaled by powers of two, the weight gradients split-K
-            # over the B N nodes with the parts summed in fixed order) -- the fp32 library GEMMs they replace ran at 60 - 130 TFLOP/s
-            if g_w2.is_cuda:                                        # (read by `_w2_in_range_or_recomputed`, behind everything below)
+            if on_device:                                           # (read by `_w2_in_range_or_recomputed`, behind everything below)
                 w2_finite.append(_ops.HostRead(torch.isfinite(g_w2).all().to(torch.int32).view(1)))
-            gw1 = grads_by_id[id(lin0.weight)]
-            if f2d.is_cuda and _GRAD_GEMM:
-                # (each matrix: one absmax, one read for its plain and transposed images; feats^T split once for both weight gradients)
-                # (launch order: everything of d/d P_i first -- its max |.| word was written by the by-source pass, long finished -- so that
-                # the device is busy with it while the host waits for the word of d/d P_j, which the last kernel queued above writes)
-                ib, jb = getattr(gz_i, "amax_bits", None), getattr(gz_j, "amax_bits", None)
-                op_i = _ops.GradOperand(gz_i, amax=None if ib is None else _ops.bits_to_floats(ib)[0], colsum=True)
-                gb1 = op_i.colsum
-                t = _ops.grad_nn(op_i, w["WiT_split"], dim, name="bwd_dfeats")
-                f_op = _ops.grad_tn_operand(f2d, None if hr_f is None else hr_f.floats()[0])
-                gw1[:, :dim] += _ops.grad_tn(op_i, f2d, name="bwd_dw1", x_operand=f_op)[:h]
-                del op_i
-                op_j = _ops.GradOperand(gz_j, amax=None if jb is None else _ops.bits_to_floats(jb)[0])
-                t = _ops.grad_nn(op_j, w["WjT_split"], dim, residual=t, name="bwd_dfeats")
-                g_feats[lo:hi_] += t.view(bc, n, dim)
-                gw1[:, dim:2 * dim] += _ops.grad_tn(op_j, f2d, name="bwd_dw1", x_operand=f_op)[:h]
-                del f_op, op_j
-            else:
-                g_feats[lo:hi_] += (gz_i @ w_i + gz_j @ w_j).view(bc, n, dim)
-                gw1[:, :dim] += _tn(gz_i, f2d)[:h]
-                gw1[:, dim:2 * dim] += _tn(gz_j, f2d)[:h]
-                gb1 = gz_i.sum(dim=0)
-            gw1[:, 2 * dim:] += g_ws[:h]
-            grads_by_id[id(lin0.bias)] += gb1[:h]
-            g_scal = g_scal.view_as(scal)
-            grads_by_id[id(lin3.weight)] += g_w2[:m, :h]
-            grads_by_id[id(lin3.bias)] += bias2 if bias2 is not None else gu16[:, :m].sum(dim=0)
+            # ---- 3. node-level products: d/d feats, d/d W_i, W_j, b_1 (and d/d W_s to its columns); edge_mlp's second Linear
+            _edge_mlp0_backward(layer, w, ch, gz_i, gz_j, g_ws, hr_f, grads)
             del gz_i, gz_j
-            if lk is not None:                                      # the edge columns of d/d scalars -> the tables
-                lk.add(lo, hi_, i32, n, k, g_scal.view(ec, s_in)[:, s_in - layer.edge_dim:])
-        # d loss / d scalars -> coordinates (through d = |x_i - x_j|^2 and the fourier terms) and edge features
-        if closed_dist:
-            with torch.no_grad():                                   # d = |rel|^2:  d loss / d rel += 2 g_d rel
-                if rel.shape[-1] == 4:                              # (the tail kernel's (E, 4) rows, 4th column 0)
-                    g_rel.addcmul_(g_scal.reshape(ec, 1), rel, value=2.0)
-                else:
-                    g_rel[:, :3] += (2.0 * g_scal.reshape(ec, 1)) * rel.reshape(ec, 3)
-        else:
-            sg = torch.autograd.grad([scal], [c] + ([e] if want_ge else []), [g_scal], allow_unused=True)
-            if sg[0] is not None:
-                g_coors_in[lo:hi_] += sg[0]
-            if want_ge and sg[1] is not None:
-                g_edges[lo:hi_] += sg[1]
-        if g_rel is not None:
-            # rel = x_i - x_j reaches the coordinates at the source (sum over a node's edges) and, negated, at the neighbour
-            # (fixed-order gather over the edges sorted by destination)
-            with torch.no_grad():
-                g_coors_in[lo:hi_] += g_rel.view(bc, n, k, 4).sum(dim=2)[..., :3]
-                if i64 is None:
-                    g_coors_in[lo:hi_] -= g_rel.view(bc, n, n, 4).sum(dim=1)[..., :3]
-                else:
-                    g_coors_in[lo:hi_] -= _ops.rows_gather_sum(g_rel, dest_lists.order, dest_lists.seg, bc * n).view(bc, n, 4)[..., :3]
-    return _returned_gradients(ctx, layer, orig_params, grads_by_id, g_feats, g_coors_in, g_edges, lk, in_dtypes)
+            g_scal = g_scal.view_as(tail.scal)
+            grads[id(lin3.weight)] += g_w2[:m, :h]
+            grads[id(lin3.bias)] += tail.bias2 if tail.bias2 is not None else tail.g_u[:, :m].sum(dim=0)
+            if st.lk is not None:                                   # the edge columns of d/d scalars -> the tables
+                st.lk.add(lo, ch.hi, ch.i32, n, k, g_scal.view(ch.ec, s_in)[:, s_in - layer.edge_dim:])
+        # ---- 4. d loss / d scalars -> coordinates and edge features
+        _scalars_to_inputs(ch, tail, g_scal, dest_lists, want_ge, st.g_edges)
+    return st.finish()
 
 
 def _lookup_rows(lookup, idx, b, n, k, pos=None):

@@ -38,7 +38,7 @@ from collections import namedtuple
 E_NULLPTR, E_SHAPE, E_UNSUPPORTED = -1, -2, -3                   # include/egnn_hip.h:34-36
 CH_S, CH_W2, GS = 8, 6, 32                                       # csrc/edge_bwd.hip:58-67, :68-71, :61-64
 BW_WAVES, XLD, DLD = 4, 36, 20                                   # csrc/edge_bwd.hip:66, :72, :248
-ROUNDS_PER_SLAB = 8                                              # _ops.py:1527
+ROUNDS_PER_SLAB = 8                                              # _ops.ROUNDS_PER_SLAB
 S_CLASSES = ((1,), (2, 4), (5,), (6, 8), (9, 16))                # egnn_edge_mfmas, csrc/edge_fused.hip:1196
 NM_ST = ((1, 1), (3, 4), (4, 5), (6, 2), (12, 2))                # csrc/edge_bwd.hip:878-882; launch_many's ST: :807-819
 FAMILIES = ("w2", "ss", "pair", "none", "both")
@@ -95,7 +95,7 @@ def family(inst):
 
 
 def default_split_reaches(inst):
-    """`autograd._edge_contract_fused` under EGNN_BWD_SPLIT=dest (its two `_ops.edge_bwd_pass` calls): by source with ws_nat (row_pairs where
+    """`autograd._edge_contract_fused`, the product's one distribution (its two `_ops.edge_bwd_pass` calls): by source with ws_nat (row_pairs where
     16 < K <= 32), by destination with want_w2 -- never a pass without a contraction, never one with both."""
     return family(inst) in ("w2", "ss", "pair")
 
@@ -123,7 +123,7 @@ def slabs(rounds, n_slabs):
 
 
 def n_slabs_of(rounds, r):
-    """_ops.edge_bwd_pass's rule (_ops.py:1541-1542) with r for ROUNDS_PER_SLAB"""
+    """_ops.edge_bwd_pass's rule (its `n_slabs is None` branch) with r for ROUNDS_PER_SLAB"""
     return max(1, (rounds + r - 1) // r)
 
 

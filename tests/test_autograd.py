@@ -912,10 +912,9 @@ def _emulated_backward(layer, feats, coors, mask, idx, rank, radius, g_node, g_c
         return (proj[src, :hp] + proj[dst, hp:] + scal @ w["Ws"]) / nl2e
 
     def bwd_pass(w_, proj, idx32, gu16, gu_scale, scal, ent, b_, n_, k_, by_dest, ws_nat=None, want_w2=False, n_slabs=None, row_pairs=False,
-                 drop=None, eid0=0, want_amax=False):
+                 drop=None, eid0=0, want_amax=False, block=0):
         assert drop is None
-        blk = w_.get("w2_block", 0)                                                 # (m_dim > 16: one call per block of 16 channels)
-        w2n = w2all[16 * blk:16 * blk + 16]
+        w2n = w2all[16 * block:16 * block + 16]                                     # (m_dim > 16: one call per block of 16 channels)
         z = z_of(proj, idx32, scal, b_, n_, k_)
         sg = torch.sigmoid(z)
         a = z * sg
@@ -985,21 +984,26 @@ def _emulated_backward(layer, feats, coors, mask, idx, rank, radius, g_node, g_c
     return [out[4], out[5]] + list(out[7:])
 
 
-_HOST_LOGIC = [(dict(dim=8, num_nearest_neighbors=5), False, 0),
-               (dict(dim=8, num_nearest_neighbors=6, norm_coors=True, coor_weights_clamp_value=0.6), True, 0),
-               (dict(dim=8, num_nearest_neighbors=20, m_pool_method="mean", norm_feats=True), True, 2),
-               (dict(dim=8, num_nearest_neighbors=7, soft_edges=True, m_dim=12), True, 0),
-               (dict(dim=8, num_nearest_neighbors=7, m_dim=20), True, 0),          # two blocks of 16 channels
-               (dict(dim=8, num_nearest_neighbors=9, m_dim=40, soft_edges=True), False, 2)]
+# (constructor arguments, prefix mask, chunks of that many graphs (0: whole), N)
+_HOST_LOGIC = [(dict(dim=8, num_nearest_neighbors=5), False, 0, 24),
+               (dict(dim=8, num_nearest_neighbors=6, norm_coors=True, coor_weights_clamp_value=0.6), True, 0, 24),
+               (dict(dim=8, num_nearest_neighbors=20, m_pool_method="mean", norm_feats=True), True, 2, 24),
+               (dict(dim=8, num_nearest_neighbors=7, soft_edges=True, m_dim=12), True, 0, 24),
+               (dict(dim=8, num_nearest_neighbors=7, m_dim=20), True, 0, 24),          # two blocks of 16 channels
+               (dict(dim=8, num_nearest_neighbors=9, m_dim=40, soft_edges=True), False, 2, 24),
+               # step 2's other arms: K > 32, the by-source rows through the gather-sum; three real blocks of 16 channels (and the padded
+               # fourth) on row pairs
+               (dict(dim=8, num_nearest_neighbors=34), False, 0, 36),
+               (dict(dim=8, num_nearest_neighbors=20, m_dim=40), False, 2, 24)]
 # the prefix-mask / no-mask cases under the ids they always had, then every masked configuration on every pattern of tests/_masks.py,
 # whole and in chunks of two graphs
-_HOST_LOGIC_CASES = [pytest.param(kw, um, mg, None, id=f"kw{i}-{um}-{mg}") for i, (kw, um, mg) in enumerate(_HOST_LOGIC)] + \
-                    [pytest.param(kw, True, mg, pat, id=f"kw{i}-{pat}-{mg}")
-                     for i, (kw, um, _) in enumerate(_HOST_LOGIC) if um for pat in PATTERNS for mg in (0, 2)]
+_HOST_LOGIC_CASES = [pytest.param(kw, um, mg, None, n, id=f"kw{i}-{um}-{mg}") for i, (kw, um, mg, n) in enumerate(_HOST_LOGIC)] + \
+                    [pytest.param(kw, True, mg, pat, n, id=f"kw{i}-{pat}-{mg}")
+                     for i, (kw, um, _, n) in enumerate(_HOST_LOGIC) if um for pat in PATTERNS for mg in (0, 2)]
 
 
-@pytest.mark.parametrize("kw,use_mask,max_graphs,pattern", _HOST_LOGIC_CASES)
-def test_native_backward_host_logic_with_emulated_kernels(kw, use_mask, max_graphs, pattern):
+@pytest.mark.parametrize("kw,use_mask,max_graphs,pattern,n", _HOST_LOGIC_CASES)
+def test_native_backward_host_logic_with_emulated_kernels(kw, use_mask, max_graphs, pattern, n):
     """autograd._backward_native on the CPU with its three kernels emulated in torch from their header contracts: what remains
     under test is the host side -- entry lists, partial rows, fixed-order sums, chunking over graphs, the node-level products,
     the parameter bookkeeping -- against autograd of the restated layer.  `pattern`: a mask of tests/_masks.py instead of the prefix
@@ -1011,7 +1015,7 @@ def test_native_backward_host_logic_with_emulated_kernels(kw, use_mask, max_grap
     with torch.no_grad():
         for p in layer.parameters():
             p.mul_(40.0)
-    b, n = (3, 24) if pattern is None else (4, 24)
+    b = 3 if pattern is None else 4
     k = kw["num_nearest_neighbors"]
     g = torch.Generator().manual_seed(6)
     feats, coors = torch.randn(b, n, kw["dim"], generator=g), torch.randn(b, n, 3, generator=g)

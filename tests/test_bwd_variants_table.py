@@ -12,8 +12,8 @@ from tests import _bwd_variants as V
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# Compiled into the product and launched neither by `autograd._edge_contract_fused` under the default split (EGNN_BWD_SPLIT=dest) nor by any
-# test before this table: the ten kernels that write the partial rows only and the two S = 1 kernels that carry everything.  Reachable
+# Compiled into the product and launched neither by `autograd._edge_contract_fused` (d/d W_s, d/d s by source, d/d W_2 by destination) nor
+# by any test before this table: the ten kernels that write the partial rows only and the two S = 1 kernels that carry everything.  Reachable
 # only by a direct call of `_ops.edge_bwd_pass` / egnn_edge_bwd_pass_f32.
 DIRECT_ONLY = sorted(
     [V.Instantiation(nm, st, False, False, 8, False, drop, False) for nm, st in V.NM_ST for drop in (False, True)]

@@ -238,6 +238,36 @@ def test_packed_weights_cache_tracks_replaced_submodules():
     assert layer.packed_weights() is c
 
 
+@pytest.mark.parametrize("m_dim", [16, 40])
+def test_backward_leaves_the_packed_weights_as_they_were(m_dim):
+    """A backward reads the layer's cached packed weights and writes nothing into them: the same keys and the same tensor objects before
+    and after, whole and with one call per block of 16 message channels (m_dim 40) -- the block is an argument of `_ops.edge_bwd_pass`.
+    The one exception is the cache of padded parameter copies the backward keeps there, `bwd_pads`."""
+    from tests.test_autograd import _emulated_backward, _emulated_case
+    layer, feats, coors, idx, rank, gn, gc = _emulated_case(dict(dim=8, num_nearest_neighbors=7, m_dim=m_dim))
+    written = []
+
+    class Recording(dict):                                                       # (a write that is undone afterwards counts too)
+        def __setitem__(self, key, value):
+            written.append(key)
+            dict.__setitem__(self, key, value)
+
+        def pop(self, key, *default):
+            written.append(key)
+            return dict.pop(self, key, *default)
+
+    w = layer._packed = Recording(layer.packed_weights())
+    before = {k: v for k, v in w.items() if k != "bwd_pads"}
+    blocks = list(w["W2Th_blocks"])
+    got = _emulated_backward(layer, feats, coors, None, idx, rank, 0.8, gn, gc)
+    assert all(g is not None and float(g.abs().max()) > 0 for g in got)         # (a backward did run)
+    assert layer.packed_weights() is w and set(written) <= {"bwd_pads"}, written
+    after = {k: v for k, v in w.items() if k != "bwd_pads"}
+    assert list(after) == list(before)
+    assert all(after[k] is before[k] for k in before)
+    assert len(w["W2Th_blocks"]) == len(blocks) and all(a is b for a, b in zip(w["W2Th_blocks"], blocks))
+
+
 def test_packed_tile_layout_matches_header_formula():
     """_weights.pack_tiles / unpack_tiles against the offset formula documented in include/egnn_hip.h."""
     from egnn_pytorch_amd import _weights
