@@ -210,6 +210,18 @@ SIGNATURES = {name: (restype, argtypes) for names, restype, argtypes in (
     ("egnn_segment_scatter_rows_f32 egnn_segment_scatter_rows_f64", c_int,
      (c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p)),
     ("egnn_segment_gather_rows_f32 egnn_segment_gather_rows_f64", c_int, (c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p)),
+    # per-graph softmax of a packed batch
+    ("egnn_segment_softmax_stats_f32 egnn_segment_softmax_stats_f64", c_int,
+     (c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p,
+      c_void_p, c_size_t, c_void_p)),
+    ("egnn_segment_softmax_apply_f32 egnn_segment_softmax_apply_f64", c_int,
+     (c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p)),
+    ("egnn_segment_pool_f32 egnn_segment_pool_f64", c_int,
+     (c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+      c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p)),
+    ("egnn_segment_pool_bwd_f32 egnn_segment_pool_bwd_f64", c_int,
+     (c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p,
+      c_void_p, c_void_p)),
     # adjacency: CSR expansion, degrees, dense expansion
     ("egnn_adj_csr_workspace_bytes egnn_adj_expand_workspace_bytes", c_size_t, (c_int, c_int)),
     ("egnn_adj_csr_square_count", c_int,

@@ -475,6 +475,17 @@ def _segment_args(x, segments, rows, what):
     return _dtype_suffix(x.dtype)
 
 
+def _segment_rows_in_place(x, d):
+    """x (T, d): rows read in place at their pitch; anything else (a transposed view) is copied first"""
+    return x if x.stride(1) == 1 and x.stride(0) >= d else x.contiguous()
+
+
+def _segment_workspace(lib, tab, g, t, d, like):
+    if not tab.n_multi:
+        return None
+    return empty(lib.egnn_segment_reduce_workspace_bytes(g, t, d, like.element_size()), dtype=torch.uint8, device=like.device)
+
+
 def segment_reduce(x, segments, op="sum"):
     """(T, D) node rows -> (G, D) graph rows -- egnn_segment_reduce_f32 / _f64 (csrc/segment_reduce.hip): op "sum" / "mean" return out,
     "max" / "min" return (out, rows int32 (G, D): the winning row of the packed batch per graph and column).  Fixed order, no atomics;
@@ -485,16 +496,13 @@ def segment_reduce(x, segments, op="sum"):
     if op not in SEGMENT_OPS:
         raise ValueError(f"segment_reduce: op = {op!r}: expected one of {tuple(SEGMENT_OPS)}")
     t, d = x.shape
-    if x.stride(1) != 1 or x.stride(0) < d:
-        x = x.contiguous()
+    x = _segment_rows_in_place(x, d)
     g = segments.num_graphs
     tab = segments._reduce_tables()
     out = empty(g, d, dtype=x.dtype, device=x.device)
     rows = empty(g, d, dtype=torch.int32, device=x.device) if SEGMENT_OPS[op] >= 2 else None
     lib = _abi.load()
-    ws = None
-    if tab.n_multi:
-        ws = empty(lib.egnn_segment_reduce_workspace_bytes(g, t, d, x.element_size()), dtype=torch.uint8, device=x.device)
+    ws = _segment_workspace(lib, tab, g, t, d, x)
     name = "egnn_segment_reduce" + sfx
     with _timed("segment_reduce"):
         rc = getattr(lib, name)(_ptr(x), x.stride(0), _ptr(segments.offsets), _ptr(tab.chunk_row), _ptr(tab.chunk_seg), _ptr(tab.chunk_slot),
@@ -549,6 +557,109 @@ def segment_gather_rows(x, rows, segments):
         rc = getattr(_abi.load(), name)(_ptr(x), _ptr(rows), segments.num_graphs, segments.num_nodes, x.shape[1], _ptr(out), _stream())
     _abi.check(rc, name)
     return out
+
+
+def _segment_stats_pair(m, l, like, shape, what):
+    for name, s in (("m", m), ("l", l)):
+        if s.dtype != like.dtype or s.device != like.device or tuple(s.shape) != tuple(shape) or not s.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous {like.dtype} {tuple(shape)} tensor on {like.device} "
+                             f"(got {s.dtype} {tuple(s.shape)} on {s.device})")
+
+
+def segment_softmax_stats(x, segments):
+    """(T, D) node rows -> (m, l), both (G, D): the maximum of every graph's column (a NaN wins) and l = sum exp(x - m), added in the
+    order of `segment_reduce`'s sum -- egnn_segment_softmax_stats_f32 / _f64 (csrc/segment_softmax.hip).  An empty graph: (-inf, 0).
+    Rows at any pitch are read in place (the same bits on the 16-byte and the scalar path); a transposed view is copied first."""
+    sfx = _segment_args(x, segments, segments.num_nodes, "segment_softmax_stats")
+    t, d = x.shape
+    x = _segment_rows_in_place(x, d)
+    g = segments.num_graphs
+    tab = segments._reduce_tables()
+    m, l = empty(g, d, dtype=x.dtype, device=x.device), empty(g, d, dtype=x.dtype, device=x.device)
+    lib = _abi.load()
+    ws = _segment_workspace(lib, tab, g, t, d, x)
+    name = "egnn_segment_softmax_stats" + sfx
+    with _timed("segment_softmax_stats"):
+        rc = getattr(lib, name)(_ptr(x), x.stride(0), _ptr(segments.offsets), _ptr(tab.chunk_row), _ptr(tab.chunk_seg), _ptr(tab.chunk_slot),
+                                tab.n_chunks, _ptr(tab.multi_seg), _ptr(tab.multi_slot), tab.n_multi, g, t, d, _ptr(m), _ptr(l), _ptr(ws),
+                                0 if ws is None else ws.numel(), _stream())
+    _abi.check(rc, name)
+    return m, l
+
+
+def segment_softmax_apply(x, m, l, segments):
+    """(T, D) node rows and the (G, D) statistics of `segment_softmax_stats` -> y (T, D) = exp(x - m[g]) / l[g] --
+    egnn_segment_softmax_apply_f32 / _f64"""
+    sfx = _segment_args(x, segments, segments.num_nodes, "segment_softmax_apply")
+    t, d = x.shape
+    _segment_stats_pair(m, l, x, (segments.num_graphs, d), "segment_softmax_apply")
+    x = _segment_rows_in_place(x, d)
+    y = empty(t, d, dtype=x.dtype, device=x.device)
+    name = "egnn_segment_softmax_apply" + sfx
+    with _timed("segment_softmax_apply"):
+        rc = getattr(_abi.load(), name)(_ptr(x), x.stride(0), _ptr(m), _ptr(l), _ptr(segments.segment_of), segments.num_graphs, t, d, _ptr(y),
+                                        _stream())
+    _abi.check(rc, name)
+    return y
+
+
+def _segment_pool_args(scores, values, m, l, segments, what):
+    """scores (T, H), values (T, H, Dv), m / l (G, H) -> (suffix, scores, values as rows at a pitch, H, Dv)"""
+    sfx = _segment_args(scores, segments, segments.num_nodes, what)
+    t, h = scores.shape
+    if values.dtype != scores.dtype:
+        raise TypeError(f"{what}: scores are {scores.dtype}, values {values.dtype}: expected one dtype")
+    if values.device != scores.device:
+        raise RuntimeError(f"Expected all tensors to be on the same device: scores are on {scores.device}, values on {values.device}")
+    if values.dim() != 3 or values.shape[:2] != (t, h) or values.shape[2] < 1:
+        raise ValueError(f"{what}: values shape {tuple(values.shape)}: expected ({t}, {h}, Dv) with Dv >= 1 for scores {tuple(scores.shape)}")
+    dv = values.shape[2]
+    _segment_stats_pair(m, l, scores, (segments.num_graphs, h), what)
+    scores = _segment_rows_in_place(scores, h)
+    if not (values.stride(2) == 1 and values.stride(1) == dv and values.stride(0) >= h * dv):
+        values = values.contiguous()
+    return sfx, scores, values, h, dv
+
+
+def segment_pool(scores, values, m, l, segments):
+    """scores (T, H), values (T, H, Dv) and the (G, H) statistics of the scores -> out (G, H, Dv) = sum_i softmax(scores)_i values_i over
+    the nodes of every graph -- egnn_segment_pool_f32 / _f64: one pass over `values`, the numerator in the order of `segment_reduce`'s
+    sum over the flattened (T, H Dv) matrix, one division by l; neither the weights nor the products are formed in memory."""
+    sfx, scores, values, h, dv = _segment_pool_args(scores, values, m, l, segments, "segment_pool")
+    g, t = segments.num_graphs, segments.num_nodes
+    tab = segments._reduce_tables()
+    out = empty(g, h, dv, dtype=values.dtype, device=values.device)
+    lib = _abi.load()
+    ws = _segment_workspace(lib, tab, g, t, h * dv, values)
+    name = "egnn_segment_pool" + sfx
+    with _timed("segment_pool"):
+        rc = getattr(lib, name)(_ptr(scores), scores.stride(0), _ptr(values), values.stride(0), _ptr(m), _ptr(l), _ptr(segments.offsets),
+                                _ptr(tab.chunk_row), _ptr(tab.chunk_seg), _ptr(tab.chunk_slot), tab.n_chunks, _ptr(tab.multi_seg),
+                                _ptr(tab.multi_slot), tab.n_multi, g, t, h, dv, _ptr(out), _ptr(ws), 0 if ws is None else ws.numel(),
+                                _stream())
+    _abi.check(rc, name)
+    return out
+
+
+def segment_pool_bwd(g, out, scores, values, m, l, segments):
+    """the first-order backward of `segment_pool`: the cotangent g and the forward's out, both (G, H, Dv) -> (d_scores (T, H),
+    d_values (T, H, Dv)) -- egnn_segment_pool_bwd_f32 / _f64: one pass over `values`"""
+    sfx, scores, values, h, dv = _segment_pool_args(scores, values, m, l, segments, "segment_pool_bwd")
+    shape = (segments.num_graphs, h, dv)
+    for name, s in (("g", g), ("out", out)):
+        if s.dtype != values.dtype or s.device != values.device or tuple(s.shape) != shape:
+            raise ValueError(f"segment_pool_bwd: {name} must be a {values.dtype} {shape} tensor on {values.device} "
+                             f"(got {s.dtype} {tuple(s.shape)} on {s.device})")
+    g, out = g.contiguous(), out.contiguous()
+    t = segments.num_nodes
+    d_scores = empty(t, h, dtype=values.dtype, device=values.device)
+    d_values = empty(t, h, dv, dtype=values.dtype, device=values.device)
+    name = "egnn_segment_pool_bwd" + sfx
+    with _timed("segment_pool_bwd"):
+        rc = getattr(_abi.load(), name)(_ptr(g), _ptr(out), _ptr(scores), scores.stride(0), _ptr(values), values.stride(0), _ptr(m), _ptr(l),
+                                        _ptr(segments.segment_of), segments.num_graphs, t, h, dv, _ptr(d_scores), _ptr(d_values), _stream())
+    _abi.check(rc, name)
+    return d_scores, d_values
 
 
 KNN_GRID_KMAX = 128           # the K limit of egnn_knn_select_grid_f32 / _f64 and _grid_csr_f32 / _f64 (csrc/knn_grid.hip: KG_KMAX)

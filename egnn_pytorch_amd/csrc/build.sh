@@ -9,7 +9,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-pass-failed -Wno-inline-a
 rm -rf "$HERE/obj"
 mkdir -p "$HERE/obj"
 pids=()
-for f in knn_select knn_rows knn_stream knn_grid knn_segments spatial_order adj_expand adj_csr linear_hl node_mlp_fused edge_fused edge_pw edge_exact edge_exact_bwd edge_hidden edge_bwd edge_tail node_ops layer_api segment_sum segment_reduce edge_csr entry_lists global_attn global_attn_bwd linear_f32 node_prep_f32 fp64 linear_split; do
+for f in knn_select knn_rows knn_stream knn_grid knn_segments spatial_order adj_expand adj_csr linear_hl node_mlp_fused edge_fused edge_pw edge_exact edge_exact_bwd edge_hidden edge_bwd edge_tail node_ops layer_api segment_sum segment_reduce segment_softmax edge_csr entry_lists global_attn global_attn_bwd linear_f32 node_prep_f32 fp64 linear_split; do
   EXTRA=""
   # the ranking kernel must reproduce the reference's un-fused ((dx*dx+dy*dy)+dz*dz) bit for bit
   [ "$f" = knn_select ] || [ "$f" = knn_rows ] || [ "$f" = knn_stream ] || [ "$f" = knn_grid ] || [ "$f" = knn_segments ] && EXTRA="-ffp-contract=off"

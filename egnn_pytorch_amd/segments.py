@@ -13,7 +13,9 @@ tensor code on whatever device the inputs live on, so they work on CPU tensors.
 Graph-level work stays packed: `reduce` takes (T, ...) node rows to (G, ...) graph rows (sum, mean, max, min), `broadcast` goes back and
 `center` removes every graph's mean.  On the device they run the ordered, atomic-free kernels of csrc/segment_reduce.hip -- the bits
 of a graph's result depend on its own rows only -- and are differentiable to any order; on CPU tensors, ordinary torch code with the
-same tie and empty-graph rules.
+same tie and empty-graph rules.  `softmax`, `logsumexp` and `attention_pool` normalise node scores over the nodes of each graph and pool
+node features with those weights (csrc/segment_softmax.hip: the same order, no atomics, one pass over the values), with torch's NaN and
+-inf rules on the rows of each graph.
 """
 from __future__ import annotations
 
@@ -309,6 +311,67 @@ class GraphSegments:
         """x - broadcast(reduce(x, "mean")): every graph moved to zero mean (coordinates: the zero-centre-of-mass projection)"""
         return x - self.broadcast(self.reduce(x, "mean"))
 
+    # ------------------------------------------------------------------ per-graph softmax: normalised node scores, learned readouts
+    def _graph_rows(self):
+        return zip(self._host, self._host[1:])
+
+    def softmax(self, x):
+        """(T, ...) -> (T, ...): the softmax over the nodes of every graph, per column -- torch.softmax(x[a:b], 0) on the rows [a, b) of
+        each graph.  A NaN makes its (graph, column) NaN and touches nothing else; a column that is all -inf gives NaN; -inf next to a
+        finite score gives exactly 0.  On the device: the ordered, atomic-free kernels of csrc/segment_softmax.hip (a graph's bits depend
+        on its own rows only); float16 / bfloat16 are computed in fp32.  Differentiable to any order; reads nothing back."""
+        x2 = self._readout_rows(x, self.num_nodes, "softmax", "node")
+        if x2.is_cuda and self.num_nodes > 0:
+            y = _SegmentSoftmax.apply(x2, self)
+        else:
+            y = torch.cat([torch.softmax(x2[a:b], 0) for a, b in self._graph_rows()])
+        return y.to(x.dtype).reshape(x.shape)
+
+    def logsumexp(self, x):
+        """(T, ...) -> (G, ...): torch.logsumexp(x[a:b], 0) on the rows of every graph, per column; an empty graph and a column that is
+        all -inf give -inf.  Device, dtypes and autograd as `softmax`."""
+        x2 = self._readout_rows(x, self.num_nodes, "logsumexp", "node")
+        if x2.is_cuda and self.num_nodes > 0:
+            out = _SegmentLogSumExp.apply(x2, self)
+        else:
+            out = torch.stack([torch.logsumexp(x2[a:b], 0) for a, b in self._graph_rows()])
+        return out.to(x.dtype).reshape(self.num_graphs, *x.shape[1:])
+
+    def attention_pool(self, scores, values):
+        """scores (T, H), values (T, H, Dv) -> (G, H, Dv): (torch.softmax(scores[a:b], 0)[..., None] * values[a:b]).sum(0) on the rows of
+        every graph -- a learned readout with H heads; the shorthand scores (T,), values (T, Dv) -> (G, Dv) is H = 1.  An empty graph gives
+        a row of zeros with zero gradient; NaN and -inf as `softmax`.  On the device one pass over `values` (csrc/segment_softmax.hip)
+        that forms neither the weights nor the products in memory; float16 / bfloat16 are computed in fp32.  Differentiable to any
+        order; reads nothing back."""
+        t = self.num_nodes
+        for what, v in (("scores", scores), ("values", values)):
+            if not torch.is_tensor(v):
+                raise TypeError(f"attention_pool: {what}: expected a tensor (got {type(v).__name__})")
+            if not v.dtype.is_floating_point:
+                raise TypeError(f"attention_pool takes floating-point {what} (got {v.dtype})")
+        if scores.dtype != values.dtype:
+            raise TypeError(f"attention_pool: scores are {scores.dtype}, values {values.dtype}: expected one dtype")
+        if scores.dim() not in (1, 2) or scores.shape[0] != t or (scores.dim() == 2 and scores.shape[1] < 1):
+            raise ValueError(f"attention_pool: scores shape {tuple(scores.shape)}: expected ({t}, H) with H >= 1, or ({t},): one row per node "
+                             f"of these segments")
+        want = (t, "Dv") if scores.dim() == 1 else (t, scores.shape[1], "Dv")
+        if values.dim() != scores.dim() + 1 or values.shape[:-1] != scores.shape or values.shape[-1] < 1:
+            raise ValueError(f"attention_pool: values shape {tuple(values.shape)}: expected ({', '.join(str(v) for v in want)}) with Dv >= 1 "
+                             f"for scores of shape {tuple(scores.shape)}")
+        for what, v in (("scores", scores), ("values", values)):
+            if v.device != self.device:
+                raise RuntimeError(f"Expected all tensors to be on the same device: {what} is on {v.device}, the segments on {self.device}")
+        h = 1 if scores.dim() == 1 else scores.shape[1]
+        s2, v3 = scores.reshape(t, h), values.reshape(t, h, values.shape[-1])
+        if s2.dtype in (torch.float16, torch.bfloat16):
+            s2, v3 = s2.float(), v3.float()                                              # computed in fp32, returned in the caller's dtype
+        if s2.is_cuda and t > 0:
+            out = _SegmentPool.apply(s2, v3, self)
+        else:
+            out = torch.stack([(torch.softmax(s2[a:b], 0)[..., None] * v3[a:b]).sum(0) if b > a else v3.new_zeros(v3.shape[1:])
+                               for a, b in self._graph_rows()])
+        return out.to(values.dtype).reshape(self.num_graphs, *values.shape[1:])
+
     # ------------------------------------------------------------------ chunks
     def split(self, max_nodes):
         """Yields (row_slice, GraphSegments) pieces cut at graph boundaries, each with at most `max_nodes` rows -- greedily, in order.
@@ -395,3 +458,72 @@ class _SegmentGather(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         return _SegmentScatter.apply(g, ctx.rows, ctx.seg), None, None
+
+
+# ---------------------------------------------------------------------- the per-graph softmax under autograd (device tensors)
+# softmax saves its OUTPUT, whose history is the Function itself, and its backward is made of differentiable pieces (products,
+# _SegmentSum, _SegmentBroadcast): recorded with create_graph=True it differentiates again.  logsumexp and the pool run their kernels
+# for the ordinary first-order step and, when the backward itself is being recorded, the same formula through the Functions.
+class _SegmentSoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, seg):
+        from . import _ops
+        m, l = _ops.segment_softmax_stats(x, seg)
+        y = _ops.segment_softmax_apply(x, m, l, seg)
+        ctx.seg = seg
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        y, = ctx.saved_tensors
+        return y * (g - _SegmentBroadcast.apply(_SegmentSum.apply(y * g, ctx.seg, False), ctx.seg)), None
+
+
+def _lse_of_stats(m, l):
+    """m + log(l); m itself where it is infinite (a column of -inf, an empty graph: -inf; a +inf score: +inf, as torch.logsumexp)"""
+    return torch.where(torch.isinf(m), m, m + torch.log(l))
+
+
+class _SegmentLogSumExp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, seg):
+        from . import _ops
+        m, l = _ops.segment_softmax_stats(x, seg)
+        ctx.seg, ctx.stats = seg, (m, l)
+        ctx.save_for_backward(x)
+        return _lse_of_stats(m, l)
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import _ops
+        x, = ctx.saved_tensors
+        y = _SegmentSoftmax.apply(x, ctx.seg) if torch.is_grad_enabled() else _ops.segment_softmax_apply(x, *ctx.stats, ctx.seg)
+        return _SegmentBroadcast.apply(g, ctx.seg) * y, None
+
+
+class _SegmentPool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, values, seg):
+        from . import _ops
+        m, l = _ops.segment_softmax_stats(scores, seg)
+        out = _ops.segment_pool(scores, values, m, l, seg)
+        ctx.seg, ctx.stats = seg, (m, l)
+        ctx.save_for_backward(scores, values, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import _ops
+        scores, values, out = ctx.saved_tensors
+        seg = ctx.seg
+        if not torch.is_grad_enabled():
+            d_scores, d_values = _ops.segment_pool_bwd(g, out, scores, values, *ctx.stats, seg)
+            return d_scores, d_values, None
+        # create_graph=True: d_values = w g, d_scores = w sum_c g (v - out), through the differentiable Functions (the saved `out`
+        # carries this Function as its history)
+        t, h, dv = values.shape
+        w = _SegmentSoftmax.apply(scores, seg)
+        gb = _SegmentBroadcast.apply(g.reshape(-1, h * dv), seg).reshape(t, h, dv)
+        ob = _SegmentBroadcast.apply(out.reshape(-1, h * dv), seg).reshape(t, h, dv)
+        return w * (gb * (values - ob)).sum(-1), w[..., None] * gb, None

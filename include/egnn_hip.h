@@ -225,6 +225,49 @@ int egnn_segment_scatter_rows_f64(const double* g, const int32_t* rows, const in
 int egnn_segment_gather_rows_f32(const float* x, const int32_t* rows, int G, int64_t T, int D, float* out, void* stream);
 int egnn_segment_gather_rows_f64(const double* x, const int32_t* rows, int G, int64_t T, int D, double* out, void* stream);
 
+/* Per-graph softmax of a packed batch (csrc/segment_softmax.hip), on the chunk tables and the workspace of egnn_segment_reduce
+ * (workspace: egnn_segment_reduce_workspace_bytes(G, T, columns walked, sizeof element), required when n_multi > 0).  No float atomics;
+ * every result of a graph is a function of its own rows, its size and the column count, the same on the 16-byte and
+ * the scalar access path; every output element is stored; table entries out of range are clamped into the arrays.
+ * egnn_segment_softmax_stats: x (T, D) at a pitch of ldx -> m, l (G, D) contiguous: the maximum of every graph's column (a NaN wins)
+ * and l = sum exp(x - m) in the order of egnn_segment_reduce's sum, the subtraction before the exponential; an empty graph: (-inf, 0).
+ * Two launches, four when n_multi > 0.
+ * egnn_segment_softmax_apply: y (T, D) contiguous = exp(x - m[g]) / l[g], g = segment_of[t].
+ * egnn_segment_pool: scores (T, H) at a pitch of lds, values (T, H, Dv) rows at a pitch of ldv, m, l (G, H) the statistics of the
+ * scores -> out (G, H, Dv) contiguous = (sum_i exp(s[i, h] - m[g, h]) v[i, h, :]) / l[g, h]: the numerator in the order of the sum over
+ * the flattened (T, H Dv) matrix, one division; an empty graph: 0.  One launch over `values`, two when n_multi > 0; neither the weights
+ * nor the products are formed in memory.
+ * egnn_segment_pool_bwd: g, out (G, H, Dv) contiguous: the cotangent and the forward's result -> d_scores (T, H), d_values (T, H, Dv)
+ * contiguous: with w = exp(s - m) / l, d_values = w g[seg] and d_scores = w sum_c g[seg, h, c] (v[t, h, c] - out[seg, h, c]), the sum
+ * in an order fixed by Dv.  One launch.
+ * Errors, all returned before any launch: EGNN_E_NULLPTR; EGNN_E_SHAPE (G, T, D, H, Dv <= 0, a pitch below its row, n_chunks < G,
+ * n_multi outside 0..n_chunks, a workspace that is too small); EGNN_E_UNSUPPORTED (T >= 2^31, H Dv >= 2^31, more than 65 535 column
+ * tiles); EGNN_E_ALIGN (workspace). */
+int egnn_segment_softmax_stats_f32(const float* x, int64_t ldx, const int64_t* offsets, const int32_t* chunk_row, const int32_t* chunk_seg,
+                                   const int32_t* chunk_slot, int n_chunks, const int32_t* multi_seg, const int32_t* multi_slot, int n_multi,
+                                   int G, int64_t T, int D, float* m, float* l, void* workspace, size_t workspace_bytes, void* stream);
+int egnn_segment_softmax_stats_f64(const double* x, int64_t ldx, const int64_t* offsets, const int32_t* chunk_row, const int32_t* chunk_seg,
+                                   const int32_t* chunk_slot, int n_chunks, const int32_t* multi_seg, const int32_t* multi_slot, int n_multi,
+                                   int G, int64_t T, int D, double* m, double* l, void* workspace, size_t workspace_bytes, void* stream);
+int egnn_segment_softmax_apply_f32(const float* x, int64_t ldx, const float* m, const float* l, const int32_t* segment_of, int G, int64_t T,
+                                   int D, float* y, void* stream);
+int egnn_segment_softmax_apply_f64(const double* x, int64_t ldx, const double* m, const double* l, const int32_t* segment_of, int G,
+                                   int64_t T, int D, double* y, void* stream);
+int egnn_segment_pool_f32(const float* scores, int64_t lds, const float* values, int64_t ldv, const float* m, const float* l,
+                          const int64_t* offsets, const int32_t* chunk_row, const int32_t* chunk_seg, const int32_t* chunk_slot, int n_chunks,
+                          const int32_t* multi_seg, const int32_t* multi_slot, int n_multi, int G, int64_t T, int H, int Dv, float* out,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int egnn_segment_pool_f64(const double* scores, int64_t lds, const double* values, int64_t ldv, const double* m, const double* l,
+                          const int64_t* offsets, const int32_t* chunk_row, const int32_t* chunk_seg, const int32_t* chunk_slot, int n_chunks,
+                          const int32_t* multi_seg, const int32_t* multi_slot, int n_multi, int G, int64_t T, int H, int Dv, double* out,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int egnn_segment_pool_bwd_f32(const float* g, const float* out, const float* scores, int64_t lds, const float* values, int64_t ldv,
+                              const float* m, const float* l, const int32_t* segment_of, int G, int64_t T, int H, int Dv, float* d_scores,
+                              float* d_values, void* stream);
+int egnn_segment_pool_bwd_f64(const double* g, const double* out, const double* scores, int64_t lds, const double* values, int64_t ldv,
+                              const double* m, const double* l, const int32_t* segment_of, int G, int64_t T, int H, int Dv, double* d_scores,
+                              double* d_values, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Sparse adjacency: the N-degree expansion of EGNN_Network (egnn_pytorch.py:414-427; egnn_adj_expand_u8 is its dense form) on CSR rows
  * (csrc/adj_csr.hip).  Row pointers are int64 (G, N + 1) ABSOLUTE offsets into a flat int32 column array, columns strictly ascending
