@@ -10,8 +10,10 @@
 //     wave and the per-node sums stay in registers (DPP butterfly over a tile's 16 edges) -- no cross-wave reduction, no LDS
 //     accumulators, no workgroup barrier outside the staging ring's one per chunk of 64 hidden units;
 //   * the setup is written for this shape only (the general kernel carries fourier / edge-feature / dense / ragged-K paths as
-//     run-time branches through every tile); a round's 32 slot records (512 B) arrive by LDS-DMA in a wave-private buffer -- the next
-//     round's while the current one computes -- and the epilogue re-reads x_i - x_j from the same LDS copy;
+//     run-time branches through every tile); a round's 32 slot records (512 B) arrive by LDS-DMA at the head of the wave's gather
+//     exchange rows -- requested behind the previous round's hidden loop, when the rows are idle, landing under its epilogue -- and
+//     the epilogue re-reads x_i - x_j from memory: no record buffers, 26 KB of LDS and at most 80 registers = six workgroups per CU
+//     (a 32-column ring reaches 26 KB too and loses more to its barrier per step than the sixth workgroup gives: DESIGN.md 4.5, 5);
 //   * kernel arguments are read per phase through a pointer the optimiser cannot see through (pw_args): nothing of the ~40 fields
 //     stays live -- or spilled -- across the hidden loop; per-lane addresses of the epilogue constants are not hoisted (pw_opaque);
 //     the staging ring's LDS-DMA uses a scalar base + 32-bit lane offset (no 64-bit vector address arithmetic per chunk);
@@ -21,8 +23,8 @@
 //   * the node's 16 message channels leave as one 8-byte store per packed image.
 // Scheduling: one workgroup (4 waves = 4 Morton-adjacent nodes) per node group, dispatched dynamically.  The kernel CAN walk several
 // groups per workgroup (EGNN_PW_GRID_MULT; ring and record prefetch continue across groups) and was first built fully persistent --
-// 5 workgroups per CU, equal static shares: 10 % SLOWER (1.54 vs 1.39 ms at the north-star shape, same box): with equal shares
-// fixed at launch the five workgroups of a CU stay in step, their latency-bound setups and epilogues coincide instead of hiding under
+// then 5 workgroups per CU, equal static shares: 10 % SLOWER (1.54 vs 1.39 ms at the north-star shape, same box): with equal shares
+// fixed at launch the workgroups of a CU stay in step, their latency-bound setups and epilogues coincide instead of hiding under
 // each other's hidden loops, and it is the dispatcher's staggered refill that de-phases them (egnn_edge_pw_launch below).
 // Round 5 (profiles/r05_experiments/edge_pw_ablations_and_pipelining.txt; code in the history at commit aaff455): software pipelining
 // of the step head without extra registers (tile 0 of the next step picked up at the end of the current one), the four SiLU chains of
@@ -48,7 +50,7 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
 
 #ifndef EGNN_PW_WGS
-#define EGNN_PW_WGS 5                        // workgroups per CU the register allocation must allow
+#define EGNN_PW_WGS 6                        // workgroups per CU the register allocation must allow (6: at most 80 VGPRs)
 #endif
 #ifndef EGNN_PW_SKIP_MASKED
 #define EGNN_PW_SKIP_MASKED 1                // a round none of whose 32 edges contributes (a padded node: mask_i = 0) skips its hidden loop
@@ -78,14 +80,15 @@ constexpr int PW_WAVES = 4;
 #endif
 constexpr int PW_HC = EGNN_PW_HC;            // hidden columns per slot of the staging ring (64: two steps of 32)
 constexpr int PW_XLD = 32;                   // floats per row of the gather exchange buffer (one 128-byte line, chunk-swizzled)
-// LDS (31 KB: five workgroups per CU):  W2 fragments, two ring slots | first-layer A fragments, two ring slots |
-// per-wave gather exchange rows (32 slots x 128 B) | per-wave slot records, two buffers of 32 x 16 B | per-wave 64-float scratch
+// LDS (26 KB: six workgroups per CU's 160 KB):  W2 fragments, two ring slots | first-layer A fragments, two ring slots |
+// per-wave gather exchange rows (32 slots x 128 B), which also take the next round's slot records and the epilogue's scratch
 constexpr int PW_W2S = 0;
 constexpr int PW_WST = PW_W2S + 2 * PW_HC * 64;
 constexpr int PW_XCH = PW_WST + 2 * PW_HC * 16;
-constexpr int PW_REC = PW_XCH + PW_WAVES * 32 * PW_XLD * 4;
-constexpr int PW_SCR = PW_REC + PW_WAVES * 2 * 512;
-constexpr int PW_LDS = PW_SCR + PW_WAVES * 256;
+constexpr int PW_LDS = PW_XCH + PW_WAVES * 32 * PW_XLD * 4;
+// Between a round's last pick-up and the next round's first gather a wave's exchange rows are dead: the next round's 32 slot records
+// (512 B) land in their first 512 bytes, and the epilogue's 64-float scratch sits behind them
+constexpr int PW_XCH_SCR = 512;
 
 __device__ __forceinline__ uint32_t pw_pack_h2(_Float16 a, _Float16 b)
 {
@@ -106,6 +109,14 @@ __device__ __forceinline__ T pw_opaque(T v)
 __device__ __forceinline__ uint32_t lds_addr_of(const void* p)
 {
     return __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) char*)(char*)p);
+}
+
+// gather_dma16 (egnn_lds_dma.h) with the LDS address as wave-uniform base + literal: the four exchange-row quarters of a step share
+// one scalar register instead of holding four precomputed addresses through the hidden loop
+__device__ __forceinline__ void pw_gather_dma16(u32x4s rsrc, uint32_t voff, uint32_t soff, uint32_t lds_base, int lds_imm)
+{
+    asm volatile("s_add_u32 m0, %3, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
+                 :: "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_base), "i"(lds_imm) : "memory", "m0", "scc");
 }
 
 // Kernel arguments read where they are used, through a pointer the optimiser cannot see through: as ordinary by-value arguments all
@@ -149,10 +160,9 @@ __global__ __launch_bounds__(PW_THREADS, EGNN_PW_WGS) void edge_pw_kernel(const 
     _Float16* const w2s = reinterpret_cast<_Float16*>(smem + PW_W2S);
     char* const wst = smem + PW_WST;
     float* const xch = reinterpret_cast<float*>(smem + PW_XCH) + wave * (32 * PW_XLD);
-    char* const recb = smem + PW_REC + wave * 1024;
-    float* const scr = reinterpret_cast<float*>(smem + PW_SCR) + wave * 64;
+    const char* const rb = reinterpret_cast<const char*>(xch);             // the round's records, until its first gather
+    float* const scr = xch + PW_XCH_SCR / 4;
     const uint32_t xch_lds = lds_addr_of(xch);
-    const uint32_t rec_lds = lds_addr_of(recb);
 
     const int Hp = p.Hp;
     const int nchunks = (Hp + PW_HC - 1) / PW_HC;
@@ -179,12 +189,13 @@ __global__ __launch_bounds__(PW_THREADS, EGNN_PW_WGS) void edge_pw_kernel(const 
                 if ((int)lane16 + o < tbytes) lds_dma16_s(wst_g + (size_t)c0s * 16 + o, lane16, wst + slot * (PW_HC * 16) + o);
         }
     };
-    // the 32 slot records of round r of node tau -> record buffer `buf` (lanes 0 .. 31: 512 bytes)
-    auto rec_dma = [&](int tau, int r, int buf) {
+    // the 32 slot records of round r of node tau -> the head of the wave's (idle) exchange rows (lanes 0 .. 31: 512 bytes)
+    // (lane_x: the caller's copy of the lane index -- the opaque one of its phase, so that the lane < 32 predicate is not hoisted)
+    auto rec_dma = [&](int tau, int r, int lane_x) {
         const pw_args_ptr a = pw_args();
         const u32x4s slot_words = make_rsrc_words(a->slots, (uint32_t)((size_t)a->B * a->N * a->K * 16));
         const uint32_t soff = ((uint32_t)tau * (uint32_t)a->K + 32u * (uint32_t)r) * 16u;
-        if (lane < 32) gather_dma16(slot_words, (uint32_t)lane * 16u, soff, rec_lds + (uint32_t)buf * 512u);
+        if (lane_x < 32) gather_dma16(slot_words, (uint32_t)lane_x * 16u, soff, xch_lds);
     };
     // node of this wave in the workgroup's kg-th group (a wave past the last node repeats the last one and stores nothing)
     auto node_of = [&](int kg) { return (gstart + wi + kg * nper) * PW_WAVES + wave; };
@@ -220,7 +231,7 @@ __global__ __launch_bounds__(PW_THREADS, EGNN_PW_WGS) void edge_pw_kernel(const 
     for (int u = 0; u < 4; ++u) neg_identity[u] = (e == 4 * g + u) ? (_Float16)-1.f : (_Float16)0.f;
 #endif
 #if defined(EGNN_PW_STAGGER) && EGNN_PW_STAGGER
-    // experiment: the five workgroups of a CU start together and run rounds of equal length -- are their latency-bound phases (epilogue,
+    // experiment: the EGNN_PW_WGS workgroups of a CU start together and run rounds of equal length -- are their latency-bound phases (epilogue,
     // setup) phase-locked?  Delay the workgroup by its (presumed) slot on the CU
     for (int q = 0; q < ((wi / 32) % EGNN_PW_WGS) * EGNN_PW_STAGGER; ++q) __builtin_amdgcn_s_sleep(127);
 #endif
@@ -229,7 +240,7 @@ __global__ __launch_bounds__(PW_THREADS, EGNN_PW_WGS) void edge_pw_kernel(const 
     int tau_next = node_of(0);
     bool live_next = tau_next < T;
     if (!live_next) tau_next = T - 1;
-    rec_dma(tau_next, 0, 0);
+    rec_dma(tau_next, 0, lane);
     int i_next_v = row_of(tau_next);
     int ring = 0;                                                          // chunks staged so far - 1 = index of the chunk the loop consumes next
 
@@ -241,56 +252,50 @@ __global__ __launch_bounds__(PW_THREADS, EGNN_PW_WGS) void edge_pw_kernel(const 
         // ------------------------------------------------------------------ round setup
         const pw_args_ptr pa = pw_args();                                   // setup arguments (scalar loads, this round only)
         const int64_t ldp = pa->ldp;
+        // the setup's own copy of the lane index (see pw_opaque): what it derives from it -- e, g, record and gather offsets, the
+        // lane < 32 predicate of the record DMA -- is recomputed every round instead of living through the hidden loop
+        const int lane_s = (lane + pw_opaque(0)) & 63;
+        const int e_s = lane_s & 15, g_s = lane_s >> 4;
         const int tau = tau_next;
         const bool live = live_next;
-        const int b = tau / N;
-        const size_t bN = (size_t)b * N;
+        const int Ns = pa->N;                                               // (re-read: the division's magic numbers do not outlive the setup)
+        const int b = tau / Ns;
+        const size_t bN = (size_t)b * Ns;
         const int i = __builtin_amdgcn_readfirstlane(i_next_v);
-        const uint32_t prow_bytes = (uint32_t)((size_t)N * ldp * 4);
+        const uint32_t prow_bytes = (uint32_t)((size_t)Ns * ldp * 4);
         const __amdgpu_buffer_rsrc_t pi_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pa->Pi + bN * ldp), 0, prow_bytes, 0x00020000);
         const u32x4s pj_words = make_rsrc_words(pa->Pj + bN * ldp, prow_bytes);
-        const int cur = rho & 1;
-        const char* const rb = recb + cur * 512;
 
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                    // this round's records have landed
         __builtin_amdgcn_wave_barrier();
         uint32_t goff[4];
 #pragma unroll
         for (int qq = 0; qq < 4; ++qq) {
-            const uint32_t j2 = *reinterpret_cast<const uint32_t*>(rb + (8 * qq + (lane >> 3)) * 16) & 0x3fffffffu;   // (bit 31: pair mask, bit 30: group flag)
+            const uint32_t j2 = *reinterpret_cast<const uint32_t*>(rb + (8 * qq + (lane_s >> 3)) * 16) & 0x3fffffffu;   // (bit 31: pair mask, bit 30: group flag)
             // the DMA drops lane l's 16 bytes at position l & 7 of row 8 qq + (l >> 3); the exchange rows' swizzle (chunk c at position
             // c ^ ((row >> 1) & 7)) moves to the global side: fetch the chunk that belongs at that position
-            const uint32_t gchunk = (uint32_t)(((lane & 7) ^ ((4 * qq + (lane >> 4)) & 7)) * 16);
+            const uint32_t gchunk = (uint32_t)(((lane_s & 7) ^ ((4 * qq + g_s) & 7)) * 16);
             goff[qq] = (uint32_t)((size_t)j2 * ldp * 4) + gchunk;
         }
         u32x4v rec[2];
 #pragma unroll
-        for (int t = 0; t < 2; ++t) rec[t] = *reinterpret_cast<const u32x4v*>(rb + (16 * t + e) * 16);
+        for (int t = 0; t < 2; ++t) rec[t] = *reinterpret_cast<const u32x4v*>(rb + (16 * t + e_s) * 16);
+        // the records are in registers before the first gathered lines may overwrite them
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
         // the first step's gathered lines and P_i words
 #pragma unroll
-        for (int qq = 0; qq < 4; ++qq) gather_dma16(pj_words, goff[qq], 0u, xch_lds + qq * 1024);
-        const uint32_t piw = (uint32_t)(((size_t)i * ldp + e) * 4);
+        for (int qq = 0; qq < 4; ++qq) pw_gather_dma16(pj_words, goff[qq], 0u, xch_lds, qq * 1024);
+        const uint32_t piw = (uint32_t)(((size_t)i * ldp + e_s) * 4);
         uint32_t piv[2];
         piv[0] = buf_load1(pi_rsrc, piw, 0);
         piv[1] = buf_load1(pi_rsrc, piw, 64);
-        // the records (and, for a new node, the feature row) of the round after this one
-        if (rho + 1 < total_rounds) {
-            if (r + 1 == R) {
-                tau_next = node_of(kg + 1);
-                live_next = tau_next < T;
-                if (!live_next) tau_next = T - 1;
-                i_next_v = row_of(tau_next);
-                rec_dma(tau_next, 0, cur ^ 1);
-            } else {
-                rec_dma(tau, r + 1, cur ^ 1);
-            }
-        }
 
         u32x2 bq[2];                                                        // B fragments of the first-layer MFMA
         bool fm[2];                                                         // edge contributes (unmasked)
         // lane-group masks, rebuilt every round (three registers that need not live through the hidden loop) and applied with bitwise
         // operations: as selects on g the compiler turns the split below into divergent branches
-        const int gq_ = g + pw_opaque(0);
+        const int gq_ = g_s;
         const uint32_t gm0 = gq_ == 0 ? 0xffffffffu : 0u, gm1 = gq_ == 1 ? 0xffffffffu : 0u, gm2 = gq_ == 2 ? 0xffffffffu : 0u;
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
@@ -324,7 +329,7 @@ __global__ __launch_bounds__(PW_THREADS, EGNN_PW_WGS) void edge_pw_kernel(const 
         // masked_f32), so that padding fills whole groups.
 #if EGNN_PW_SKIP_MASKED
         const bool skip_round = pa->U_out == nullptr && __builtin_amdgcn_ballot_w64(fm[0] || fm[1]) == 0ull;
-        const bool skip_group = skip_round && ((__builtin_amdgcn_readfirstlane(*reinterpret_cast<const int*>(rb)) >> 30) & 1) != 0;
+        const bool skip_group = skip_round && ((__builtin_amdgcn_readfirstlane((int)rec[0][0]) >> 30) & 1) != 0;   // (lane 0: record 0)
 #else
         constexpr bool skip_round = false, skip_group = false;
 #endif
@@ -393,7 +398,7 @@ __global__ __launch_bounds__(PW_THREADS, EGNN_PW_WGS) void edge_pw_kernel(const 
 #if !(EGNN_PW_ABL & 1)
             if (more) {
 #pragma unroll
-                for (int qq = 0; qq < 4; ++qq) gather_dma16(pj_words, goff[qq], (uint32_t)(hnext * 4), xch_lds + qq * 1024);
+                for (int qq = 0; qq < 4; ++qq) pw_gather_dma16(pj_words, goff[qq], (uint32_t)(hnext * 4), xch_lds, qq * 1024);
             }
 #endif
 
@@ -523,7 +528,25 @@ __global__ __launch_bounds__(PW_THREADS, EGNN_PW_WGS) void edge_pw_kernel(const 
 #endif
         // ------------------------------------------------------------------ per-edge epilogue (registers; channel of (lane group g, register u) = 4 g + u)
         const pw_args_ptr pe = pw_args();                                   // epilogue arguments (scalar loads, this round only)
+        // ... and the epilogue's own copy of the lane index (as lane_s above): its offsets and store predicates are rebuilt here
+        const int lane_e = (lane + pw_opaque(0)) & 63;
+        const int e_e = lane_e & 15, g_e = lane_e >> 4;
         const bool has_mask = pe->mask != nullptr;
+        const int Ke = pe->K;
+        // the records (and, for a new node, the feature row) of the round after this one: the exchange rows are idle from the last
+        // pick-up on (a round without hidden loop still has its first gathers in flight: they land first)
+        if (skip_round) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (rho + 1 < total_rounds) {
+            if (r + 1 == R) {
+                tau_next = node_of(kg + 1);
+                live_next = tau_next < T;
+                if (!live_next) tau_next = T - 1;
+                i_next_v = row_of(tau_next);
+                rec_dma(tau_next, 0, lane_e);
+            } else {
+                rec_dma(tau, r + 1, lane_e);
+            }
+        }
         int32_t* const status = pe->status;
         const float* const gate_w = pe->gate_w;
         const float* const coors_scale = pe->coors_scale;
@@ -535,9 +558,17 @@ __global__ __launch_bounds__(PW_THREADS, EGNN_PW_WGS) void edge_pw_kernel(const 
                 for (int c = 0; c < 4; ++c) ncs[c] = 0.f;
             }
         } else {
+        // this round's records once more, for x_i - x_j below (their LDS copy is gone under the gathered lines): from memory -- they
+        // came through the same caches a round ago --, requested here and used after coors_mlp
+        const __amdgpu_buffer_rsrc_t rec_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<void*>(static_cast<const void*>(pe->slots)), 0, (uint32_t)((size_t)pe->B * pe->N * Ke * 16), 0x00020000);
+        const uint32_t rec_soff = ((uint32_t)tau * (uint32_t)Ke + 32u * (uint32_t)r) * 16u;
+        f32x4 rcv[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) rcv[t] = buf_load4(rec_rsrc, (uint32_t)e_e * 16u, (int)(rec_soff + 256u * t));
         f32x4 b2r, gwr = f32x4{0.f, 0.f, 0.f, 0.f};
         float gb = 0.f;
-        const int g4 = pw_opaque(4) * g;                                     // (opaque: see pw_opaque)
+        const int g4 = 4 * g_e;
         b2r = *reinterpret_cast<const f32x4*>(pe->b2 + g4);
         if (gate_w) {
             gwr = *reinterpret_cast<const f32x4*>(gate_w + g4);
@@ -561,11 +592,11 @@ __global__ __launch_bounds__(PW_THREADS, EGNN_PW_WGS) void edge_pw_kernel(const 
                 m[u] = egnn_silu(uu[u]);
             }
             // forward under autograd: u = W2 SiLU(x) + b2, what the backward differentiates from (one 16-float row per edge (b, i, k))
-            if (u_out && live) *reinterpret_cast<f32x4*>(u_out + ((bN + i) * (size_t)K + 32 * r + 16 * t + e) * 16 + g4) = uu;
+            if (u_out && live) *reinterpret_cast<f32x4*>(u_out + ((bN + i) * (size_t)Ke + 32 * r + 16 * t + e_e) * 16 + g4) = uu;
             float part = gwr[0] * m[0] + gwr[1] * m[1] + gwr[2] * m[2] + gwr[3] * m[3];
             egnn_flag_range(status, bad && fm[t], EGNN_RANGE_HIDDEN);
             if (gate_w) {                                                      // soft_edges (:289-290)
-                part = egnn_column_sum4(part, scr, lane);
+                part = egnn_column_sum4(part, scr, lane_e);
                 const float gt = egnn_sigmoid(part + gb);
                 m *= gt;
             }
@@ -597,7 +628,7 @@ __global__ __launch_bounds__(PW_THREADS, EGNN_PW_WGS) void edge_pw_kernel(const 
                 }
             }
             constexpr int W3LD = 16, W3IMG = 64 * 16;
-            const int w3o = e * W3LD + g4;
+            const int w3o = e_e * W3LD + g4;
             const float* const b3p = pe->b3;
             const float* const w4p = pe->W4;
             const float w3_inv_scale = pe->w3_inv_scale;
@@ -621,7 +652,7 @@ __global__ __launch_bounds__(PW_THREADS, EGNN_PW_WGS) void edge_pw_kernel(const 
             const float b4 = pe->b4[0];
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                float s = egnn_column_sum4(part[t], scr, lane);
+                float s = egnn_column_sum4(part[t], scr, lane_e);
                 s += b4;
                 if (has_mask && !fm[t]) s = 0.f;                                 // :308-309
                 if (clampv >= 0.f) s = fminf(fmaxf(s, -clampv), clampv);         // :311-313
@@ -630,15 +661,11 @@ __global__ __launch_bounds__(PW_THREADS, EGNN_PW_WGS) void edge_pw_kernel(const 
             }
         }
 
-        // x_i - x_j again, from the wave's LDS copy of the records
+        // x_i - x_j again, from the records re-read above
         float rn[2][3], keep[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            const u32x4v rc = *reinterpret_cast<const u32x4v*>(rb + (16 * t + e) * 16);
-            const uint32_t rw[3] = {rc[1], rc[2], rc[3]};
-            float rel[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) rel[c] = __uint_as_float(rw[c]);
+            const float rel[3] = {rcv[t][1], rcv[t][2], rcv[t][3]};
             keep[t] = fm[t] ? 1.f : 0.f;
             float inv = 1.f;
             if (coors_scale) {                                                   // CoorsNorm, egnn_pytorch.py:67-77
@@ -685,11 +712,11 @@ __global__ __launch_bounds__(PW_THREADS, EGNN_PW_WGS) void edge_pw_kernel(const 
                 _Float16* const node_hi = static_cast<_Float16*>(pe->node_hi);
                 _Float16* const node_lo = static_cast<_Float16*>(pe->node_lo);
                 const int dim = pe->dim;
-                if (e == 0 && node_hi && !m_i && (dim & 3) == 0 && m_dim == 16) {
+                if (e_e == 0 && node_hi && !m_i && (dim & 3) == 0 && m_dim == 16) {
                     // the common case (the layer's own launch sequence, m_dim = 16, dim % 4 == 0): the lane's four channels are four
                     // consecutive halves of one 16-byte chunk of the packed images -- one 8-byte store per image instead of four
                     // per-channel rounds of offset arithmetic
-                    const int gch = pw_opaque(4) * g;
+                    const int gch = 4 * g_e;
                     const int pool_mean = pe->pool_mean, nkt = pe->node_kp / 16;
                     f32x4 val;
                     bool bad = false;
@@ -701,7 +728,7 @@ __global__ __launch_bounds__(PW_THREADS, EGNN_PW_WGS) void edge_pw_kernel(const 
                                 const float cnt = 0.f + ncs[3];
                                 v = (cnt == 0.f) ? 0.f : v / fmaxf(cnt, 1e-8f);
                             } else {
-                                v = v / (float)K;                                // :330
+                                v = v / (float)Ke;                               // :330
                             }
                         }
                         bad = bad || egnn_beyond_f16(v);
@@ -717,8 +744,8 @@ __global__ __launch_bounds__(PW_THREADS, EGNN_PW_WGS) void edge_pw_kernel(const 
                     const size_t off = egnn_pk_off((int64_t)row, dim + gch, nkt);
                     *reinterpret_cast<f16x4*>(node_hi + off) = h4;
                     *reinterpret_cast<f16x4*>(node_lo + off) = l4;
-                } else if (e == 0 && (m_i || node_hi)) {
-                    const int gch = pw_opaque(4) * g;                            // (opaque: the packed offsets below are not loop invariants)
+                } else if (e_e == 0 && (m_i || node_hi)) {
+                    const int gch = 4 * g_e;
                     const int pool_mean = pe->pool_mean, nkt = pe->node_kp / 16;
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
@@ -730,7 +757,7 @@ __global__ __launch_bounds__(PW_THREADS, EGNN_PW_WGS) void edge_pw_kernel(const 
                                     const float cnt = 0.f + ncs[3];
                                     val = (cnt == 0.f) ? 0.f : val / fmaxf(cnt, 1e-8f);
                                 } else {
-                                    val = val / (float)K;                        // :330
+                                    val = val / (float)Ke;                       // :330
                                 }
                             }
                             if (m_i) m_i[row * m_dim + ch] = val;
@@ -745,9 +772,9 @@ __global__ __launch_bounds__(PW_THREADS, EGNN_PW_WGS) void edge_pw_kernel(const 
                     }
                 }
                 float* const coors_out = pe->coors_out;
-                if (lane < 3 && coors_out) {
-                    const float val = 0.f + (lane == 0 ? ncs[0] : (lane == 1 ? ncs[1] : ncs[2]));
-                    coors_out[row * 3 + lane] = pe->coors[row * 3 + lane] + val;
+                if (lane_e < 3 && coors_out) {
+                    const float val = 0.f + (lane_e == 0 ? ncs[0] : (lane_e == 1 ? ncs[1] : ncs[2]));
+                    coors_out[row * 3 + lane_e] = pe->coors[row * 3 + lane_e] + val;
                 }
             }
             if (MULTI) {
@@ -791,10 +818,10 @@ int egnn_edge_pw_launch(const egnn_edge_args* args, void* stream)
         return (int)hipGetLastError();
     const int64_t T = (int64_t)a.B * a.N;
     const int64_t ngroups = (T + PW_WAVES - 1) / PW_WAVES;
-    // One workgroup per node group by default.  The kernel can walk several groups per workgroup (a grid of EGNN_PW_GRID_MULT x 5
+    // One workgroup per node group by default.  The kernel can walk several groups per workgroup (a grid of EGNN_PW_GRID_MULT x EGNN_PW_WGS
     // workgroups per CU; 1 = fully persistent) -- measured on the north-star shape / c3, same box: persistent 1.54 / 0.484 ms, two
     // workgroups per slot 1.45 / 0.463, four 1.40 / 0.446, one workgroup per group 1.39 / 0.443 (profiles/r04_experiments/): with equal
-    // shares fixed at launch the five workgroups of a CU stay in step -- their latency-bound setups and epilogues coincide instead of
+    // shares fixed at launch the workgroups of a CU (five then) stay in step -- their latency-bound setups and epilogues coincide instead of
     // hiding under each other's hidden loops -- and dynamic dispatch is what de-phases them.
 #if defined(EGNN_PW_GRID_MULT)
     int64_t grid = (int64_t)cus * EGNN_PW_WGS * EGNN_PW_GRID_MULT;
