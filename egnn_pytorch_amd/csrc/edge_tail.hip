@@ -386,12 +386,12 @@ __global__ __launch_bounds__(256) void edge_tail_mfma_kernel(const egnn_edge_tai
     __shared__ uint2 fragA[4][2][64];            // W3 rows: [t block][hi | lo][lane (g, m)] = W3[16 tb + m][4g .. 4g+3] x s3
     __shared__ uint2 fragB[4][2][64];            // W3^T:    [t block][hi | lo][lane (g, m)] = W3[16 tb + 4g .. +3][m] x s3
     __shared__ float sb3[TH], sW4[TH], sgw[TM];
-    __shared__ uint32_t w3max;
+    __shared__ uint32_t w3max, w4max;
     __shared__ __attribute__((aligned(16))) float stage_raw[4 * (2 * 16 * GLD + 16 * TM + 16)];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, ee = lane & 15;
     // ---- weights: power-of-two scale from max |W3| (hi / lo halves in fp16's normal range), fragments, biases
-    if (tid == 0) w3max = 0u;
+    if (tid == 0) { w3max = 0u; w4max = 0u; }
     __syncthreads();
     {
         uint32_t m = 0u;
@@ -399,11 +399,21 @@ __global__ __launch_bounds__(256) void edge_tail_mfma_kernel(const egnn_edge_tai
         if (m) atomicMax(&w3max, m);
     }
     if (tid < TM) sgw[tid] = p.gate_w ? p.gate_w[tid] : 0.f;
-    if (tid < TH) { sb3[tid] = p.b3[tid]; sW4[tid] = p.W4[tid]; }
+    if (tid < TH) {
+        sb3[tid] = p.b3[tid]; sW4[tid] = p.W4[tid];
+        const uint32_t t = egnn_abs_bits(sW4[tid]);
+        if (t) atomicMax(&w4max, t);
+    }
     __syncthreads();
     const uint32_t ebits = w3max & 0x7f800000u;                                 // exponent field of max |W3|
     const float s3 = (ebits && ebits < 0x7e800000u) ? __uint_as_float(0x7f000000u - ebits) : 1.0f;       // 2^-floor(log2 max): max |W3| s3 in [1, 2)
     const float inv_s3 = 1.0f / s3;
+    // q = W4 SiLU'(hid) is split into fp16 (hi, lo) too, and |SiLU'| <= 1.1: where max |W4| < 1 (the module's own N(0, 1e-3) draw: q ~ 5e-4, lo
+    // halves in the subnormals, 2^-24 absolute) the split takes q x s4, max |W4| s4 in [1, 2), and gk undoes it.  Upwards only: at
+    // max |W4| >= 1 the lo halves are normal as they are, and s4 = 1 keeps every bit
+    const uint32_t ebits4 = w4max & 0x7f800000u;
+    const float s4 = (ebits4 && ebits4 < 0x3f800000u) ? __uint_as_float(0x7f000000u - ebits4) : 1.0f;
+    const float inv_s34 = inv_s3 * (1.0f / s4);
     {
         const int tb = tid >> 6, l = tid & 63, lg = l >> 4, lm = l & 15;
         f32x4 a, b;
@@ -512,7 +522,7 @@ __global__ __launch_bounds__(256) void edge_tail_mfma_kernel(const egnn_edge_tai
             *reinterpret_cast<f32x4*>(sgh + ee * GLD + 16 * tb + 4 * g) = ghv;
             *reinterpret_cast<f32x4*>(sa3 + ee * GLD + 16 * tb + 4 * g) = a3v;
             h16x4 qh, ql;
-            tail_split4(q, qh, ql);
+            tail_split4(q * s4, qh, ql);
             const h16x4 bh = __builtin_bit_cast(h16x4, fragB[tb][0][lane]), bl = __builtin_bit_cast(h16x4, fragB[tb][1][lane]);
             gmacc = __builtin_amdgcn_mfma_f32_16x16x16f16(bh, qh, gmacc, 0, 0, 0);
             gmacc = __builtin_amdgcn_mfma_f32_16x16x16f16(bh, ql, gmacc, 0, 0, 0);
@@ -521,7 +531,7 @@ __global__ __launch_bounds__(256) void edge_tail_mfma_kernel(const egnn_edge_tai
         *reinterpret_cast<f32x4*>(smm + ee * TM + 4 * g) = m4;
         if (g == 0) sgwe[ee] = g_w;
         f32x4 gm;
-        const float gk = g_w * inv_s3;
+        const float gk = g_w * inv_s34;
 #pragma unroll
         for (int r = 0; r < 4; ++r) gm[r] = __builtin_fmaf(gmacc[r], gk, pm ? p.g_msum[ig * TM + 4 * g + r] : 0.f);
         float gs = 0.f;

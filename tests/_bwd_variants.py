@@ -29,7 +29,10 @@ The cells are not drawn, they follow a rule (`_build_cells`):
              never leaves a slab empty; two extra cells with r = 1 and at least 35 rounds: two slab groups, the second partial
     weights  xavier-normal (tests/test_gpu_kernels.py::test_edge_bwd_pass_contractions_match_float64: with the default N(0, 1e-3) init
              SiLU' is nearly constant);  gU = randn 1e-3 with a fifth of its rows, all edges of one source node and all edges into one
-             destination exactly zero"""
+             destination exactly zero
+    init     one extra cell per family at the module's own initialisation (every Linear weight N(0, 1e-3), as EGNN.__init__ leaves it):
+             z is then b1 + O(1e-2), SiLU(z) ~ 0.05 and dz ~ 1e-3 |gU| -- a training run's first steps, two orders below what the fixed
+             up-scales of the kernel (DZ_UP, A_UP) were sized on.  Held to the same 5e-6 of scale, WITHOUT the absolute 1e-12"""
 import functools
 import zlib
 from collections import namedtuple
@@ -205,6 +208,12 @@ def _build_cells():
     # at least 35 rounds with one round per slab: two slab groups, the second partial
     add(1, "pair", False, False, 32, 9, 1, n=70, s_pick=0, extra="groups")
     add(2, "w2", False, True, 32, 13, 1, n=70, mostly_fourier=True, extra="groups")
+    # the module's own initialisation, one cell per family
+    add(1, "w2", False, True, 16, 8, 8, extra="init")
+    add(3, "ss", False, False, 40, 9, 8, mostly_fourier=True, extra="init")
+    add(2, "pair", False, False, 24, 2, 8, extra="init")
+    add(4, "none", False, False, 5, 13, 8, extra="init")
+    add(0, "both", False, False, 33, 8, 8, extra="init")
     return cells
 
 
@@ -234,7 +243,7 @@ def prepare(cid):
         torch.manual_seed(cell.seed)
         layer = EGNN(**cell.kw)
         for mod in layer.modules():
-            if isinstance(mod, torch.nn.Linear):
+            if isinstance(mod, torch.nn.Linear) and cell.extra != "init":
                 torch.nn.init.xavier_normal_(mod.weight)
     p.layer = layer
     g = torch.Generator().manual_seed(cell.seed + 1)

@@ -9,7 +9,8 @@ process of the per-lane REDUCE kernel (its switch is read once per process).
 Bars (`tail_bars`, `bar_f32`): 8 x the error torch fp32 makes on the same specification and inputs + 16 x 2^-24 of the output's scale
 (tests/_plain_variants.py), behind split-f16 MFMAs + 2^-20 sum |a| |b| of the products on the path, and never above what the older
 test of the same output allows (2e-6 per edge, 2e-5 sums, 3e-5 node_mlp_fused): min(derived, older).  Nothing here looks at a
-kernel's output."""
+kernel's output.  The tail cells named `init_*` take coors_mlp, the gate and CoorsNorm.scale as EGNN.__init__ draws them (weights
+N(0, 1e-3)) and are held to the same bars on the same four kernels."""
 import functools
 import os
 import sys
@@ -30,7 +31,7 @@ EPS = 1e-8                                       # CoorsNorm.eps
 
 # ================================================================================================ the tail: cells
 _TAIL = dict(b=2, n=8, k=5, dense=False, m=16, mask="none", clamp="mid", norm=True, scale=1.7, dup=True, gate="span", w3=1.5, u="n1",
-             drop=None, eid0=0, seed=0)
+             drop=None, eid0=0, seed=0, init=False, gm=1.0, gco="randn")
 TAIL_MODES = ("plain", "mfma", "scalar")         # kernels a cell without dropout runs on; with dropout: "mfma_drop" only
 
 
@@ -63,6 +64,21 @@ TAIL_CELLS += [_tc("drop_dense_e200", drop=(0.5, 31), eid0=200, b=2, n=10, k=10,
 TAIL_CELLS += [_tc("combo_dense_mask_m7", b=2, n=9, k=9, dense=True, m=7, mask="ragged", seed=90),
                _tc("combo_drop_mask_sat_m13", drop=(0.5, 77), eid0=160, b=4, m=13, mask="node", gate="sat", u="n4", seed=91),
                _tc("combo_e257_mask_nogate", b=1, n=257, k=1, mask="scattered", gate=None, norm=False, seed=92)]
+# the module's own initialisation (`init`): coors_mlp, the gate and CoorsNorm.scale as EGNN.__init__ draws them -- every Linear weight
+# N(0, 1e-3), biases U(+-1 / sqrt(fan_in)), scale 1e-2 -- instead of `_tail_params`' scaling.  q = W4 SiLU'(hid) is then ~5e-4 and W3 m
+# ~1e-3 against b3 ~0.25: the operands of a training run's first steps.  No clamp (every edge's weight is b4 to seven digits: no value
+# separates them), no planted duplicates; gm = 0: g_msum = 0, so that gU is the coordinate branch alone and does not hide behind the
+# pooled messages' pass-through, which is six orders above it (one cell keeps g_msum); gco = "coors": g_coors_out = x + randn / 2, the
+# cotangent of a quadratic loss.  With a3 the same on every edge to three digits, d/d W4 = a3 sum g_w, and under a zero-mean cotangent
+# sum g_w cancels to 1e-3 ... 0.1 of sum |g_w|, draw by draw: below the rounding of ANY fp32 sum of 257 such terms relative to the
+# older test's cap (2e-5 of the group's largest |sum|), which `tail_bars` never exceeds.  The cells keep that cap and get a cotangent
+# under which the sum is a sum (`_init_conditions`)
+_INIT = dict(init=True, clamp=None, dup=False, gate="init", gm=0.0, gco="coors")
+TAIL_CELLS += [_tc("init_e80", seed=130, **_INIT), _tc("init_e80_nogate_nonorm", seed=131, **dict(_INIT, gate=None, norm=False)),
+               _tc("init_e257_nonorm", b=1, n=257, k=1, seed=132, **dict(_INIT, norm=False)),
+               _tc("init_e257_nogate", b=1, n=257, k=1, seed=133, **dict(_INIT, gate=None)),
+               _tc("init_e80_pooled", seed=134, **dict(_INIT, gm=1.0)),
+               _tc("init_drop_e80", drop=(0.1, 41), eid0=80, seed=135, **_INIT)]
 TAIL_BY_ID = {c.id: c for c in TAIL_CELLS}
 assert len(TAIL_BY_ID) == len(TAIL_CELLS)
 
@@ -116,9 +132,26 @@ def _make_layer(p, m, c, w, dtype):
     return layer
 
 
+def _init_params(p, m):
+    """coors_mlp, the gate and CoorsNorm.scale as the module draws them under the cell's seed (fp32 values)"""
+    from egnn_pytorch_amd import EGNN
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(7000 + p["seed"])
+        layer = EGNN(dim=4, m_dim=m, norm_coors=p["norm"], soft_edges=p["gate"] is not None)
+    t = lambda v: v.detach().double()                                             # noqa: E731
+    w = dict(W3=t(layer.coors_mlp[0].weight), b3=t(layer.coors_mlp[0].bias), W4=t(layer.coors_mlp[3].weight[0]), b4=t(layer.coors_mlp[3].bias))
+    if p["norm"]:
+        w["scale"] = t(layer.coors_norm.scale).reshape(1)
+    if p["gate"] is not None:
+        w["gate_w"], w["gate_b"] = t(layer.edge_gate[0].weight[0]), t(layer.edge_gate[0].bias)
+    return w
+
+
 def _tail_params(p, u, raw):
     """coors_mlp, the gate and CoorsNorm.scale for a cell, every tensor scaled from the float64 forward of the tensors before it"""
     m, e = u.shape[-1], u[..., 0].numel()
+    if p["init"]:
+        return _init_params(p, m)
     w = {}
     m0 = torch.nn.functional.silu(u)
     mm = m0
@@ -144,8 +177,9 @@ def _tail_params(p, u, raw):
     flat_w = p["w3"] <= 1e-20 or e == 1                                          # W3 = 0: every edge has the same coordinate weight
     qs = pre_w.reshape(-1).sort().values
     sd = float(pre_w.abs().max()) if flat_w else float(qs[(3 * e) // 4] - qs[e // 4]) / 1.349          # (the quartiles' estimate of the deviation)
-    # deviation of w = 1, but max |W4| never below 2^-3: q = W4 SiLU'(hid) is an fp16 (hi, lo) operand of the matrix-core kernel, and
-    # operands in fp16's subnormal range are not this table's subject (at max |W3| = 3 * 2^10 the activations are ~1e3 and w ~ 1e2)
+    # deviation of w = 1, but max |W4| never below 2^-3 (at max |W3| = 3 * 2^10 the activations are ~1e3 and w ~ 1e2): these cells keep
+    # q = W4 SiLU'(hid), an fp16 (hi, lo) operand of the matrix-core kernel, at O(1).  The small end -- W4 ~ 1e-3, q's lo half in fp16's
+    # subnormal range unless the kernel scales it -- is the `init` cells'
     w["W4"] = _f32(raw["w4"] * max(1.0 / max(sd, 1e-30), 0.125 / float(raw["w4"].abs().max()))).double()
     srt = (a3 @ w["W4"]).reshape(-1).sort().values
     w["b4"] = torch.tensor([0.3], dtype=torch.float32).double() if flat_w else _f32(-(srt[e // 2 - 1] + srt[e // 2]).reshape(1) / 2).double()
@@ -193,7 +227,9 @@ def prepare(cid):
             if p["mask"] == "node":
                 pm[:, min(3, n - 1)] = False
     u, coors = _f32(u).double(), _f32(coors).double()
-    g_co, g_msum = _f32(rnd(b, n, 3)).double(), _f32(rnd(b, n, m)).double()
+    g_co, g_msum = _f32(rnd(b, n, 3)).double(), _f32(rnd(b, n, m)).double() * p["gm"]
+    if p["gco"] == "coors":
+        g_co = _f32(coors + 0.5 * g_co).double()
     raw = dict(gw=rnd(m), w3=rnd(4 * m, m), b3=rnd(4 * m), w4=rnd(4 * m))
     w = _tail_params(p, u, raw)
     # ---- coincident non-self edges carry d/d rel = w_c g scale / eps: 1e8 times the rounding error of their coordinate weight.  They get
@@ -325,6 +361,8 @@ def tail_spec_drop(layer, u, coors, idx, pair_mask, g_coors_out, g_msum, keep, i
 def _tail_conditions(d):
     """The cell conditions, on the float64 reference alone (and the torch-fp32 evaluation for the decision margin)."""
     p, ref, e = d.p, d.ref, d.e
+    if p["init"]:
+        return _init_conditions(d)
     live = d.pm.reshape(-1) if d.pm is not None else torch.ones(e, dtype=torch.bool)
     wide = int(live.sum()) >= 40                                                 # fractions are asserted where there are edges to count
     w, rn = ref["w"].reshape(-1), ref["rn"]
@@ -379,6 +417,40 @@ def _tail_conditions(d):
         frac = float(ref["keep"].float().mean())
         assert abs(frac - (1 - d.drop[0])) < 0.08, (d.cell.id, frac)
         assert d.eid0 + e <= 2 ** 32 - 1
+
+
+def _init_conditions(d):
+    """The cells at the module's own initialisation, on the reference alone: the weights are the module's draw (std within 30 % of 1e-3;
+    the gate's sixteen within 50 %), q = W4 SiLU'(hid) lies where an unscaled fp16 (hi, lo) pair loses its lo half to the subnormals
+    (|q| <= 2^-8: lo <= 2^-19, resolved to 2^-24), W3 m is bias-dominated, and nothing compared is 0 == 0."""
+    p, ref, w = d.p, d.ref, d.w
+    d.margin = None
+    assert d.clamp is None and d.pm is None and not bool(d.coinc.any()), d.cell.id
+    for name in ("W3", "W4"):
+        assert 0.7e-3 <= float(w[name].std()) <= 1.3e-3, (d.cell.id, name, float(w[name].std()))
+    if p["gate"] is not None:
+        assert 0.5e-3 <= float(w["gate_w"].std()) <= 1.5e-3, (d.cell.id, float(w["gate_w"].std()))
+    if p["norm"]:
+        assert float(w["scale"]) == float(torch.tensor(1e-2, dtype=torch.float32)), d.cell.id
+    ik = 1.0 if d.drop is None else 1.0 / (1.0 - d.drop[0])
+    hid = (ref["m"] @ w["W3"].t() + w["b3"]) * ik
+    sg = torch.sigmoid(hid)
+    q = w["W4"] * (sg * (1 + hid * (1 - sg))) * ik
+    assert 0 < float(q.abs().max()) <= 2.0 ** -8, (d.cell.id, float(q.abs().max()))
+    assert float((ref["m"] @ w["W3"].t()).abs().max()) < 0.1 * float(w["b3"].abs().max()), d.cell.id
+    assert bool(((ref["rn"] == 0) == d.self_pair).all()), d.cell.id
+    for name in ("g_u", "g_rel", "g_hid", "g_w"):
+        assert float(ref[name].abs().max()) > 0, (d.cell.id, name)
+    # d/d W4 and d/d b4 are sums, not cancellations: an fp32 sum of E terms is good to a few 2^-24 sum |g_w| (3e-7 of it over 257 terms
+    # taken one after the other), the cap allows 2e-5 |sum g_w|, and 8 x the former has to fit under the latter
+    assert float(ref["g_w"].sum().abs()) >= 0.12 * float(ref["g_w"].abs().sum()), (d.cell.id, float(ref["g_w"].sum()), float(ref["g_w"].abs().sum()))
+    if p["gm"] == 0.0:
+        assert not bool(d.g_msum.any())
+        # gU is the coordinate branch alone: g_w W3^T q through the gate and SiLU'(u)
+        assert float(ref["g_u"].abs().max()) < 1e-4 * float(ref["g_w"].abs().max()), d.cell.id
+    if d.drop is not None:
+        frac = float(ref["keep"].float().mean())
+        assert abs(frac - (1 - d.drop[0])) < 0.08, (d.cell.id, frac)
 
 
 def tail_sums(r, m, hid3):

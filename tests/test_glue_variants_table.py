@@ -57,6 +57,11 @@ def test_every_tail_cell_meets_its_conditions_on_the_reference():
     assert {V.TAIL_BY_ID[k].p["w3"] for k in V.TAIL_BY_ID} >= {0.0, 2.0 ** -8, 1.0, 3072.0, 1e-30, 1.5}
     assert V.TAIL_BY_ID["clamp_zero"].p["clamp"] == 0.0 and V.TAIL_BY_ID["clamp_none"].p["clamp"] is None
     assert float(V.prepare("norm_nodup").w["scale"]) != 1.0 and float(V.prepare("base_e80").w["scale"]) != 1.0
+    # the module's own initialisation: E = 80 and 257, with and without the gate and CoorsNorm, one with dropout, one with pooled messages
+    init = [c for c in V.TAIL_CELLS if c.p["init"]]
+    assert {(V.prepare(c.id).e, c.p["gate"] is not None, c.p["norm"]) for c in init} == {(80, True, True), (80, False, False), (257, True, False), (257, False, True)}
+    assert sum(c.p["drop"] is not None for c in init) == 1 and sum(c.p["gm"] != 0.0 for c in init) == 1 and len(init) == 6
+    assert all(V.tail_modes(c) == (("mfma_drop",) if c.p["drop"] else V.TAIL_MODES) for c in init)
     print(dict(seen))
 
 

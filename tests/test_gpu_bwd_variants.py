@@ -3,7 +3,8 @@
 
   the bar        every output the variant produces -- the per-key sums of its partial rows, d/d W_s, d/d scalars, d/d W_2 -- within
                  5e-6 max|reference| + 1e-12 (the bar of tests/test_gpu_kernels.py::test_edge_bwd_pass_contractions_match_float64), with and
-                 without dropout: at p = 0.5 the factor 2 is exact, at p = 0.2 the factor 1.25 costs one fp32 rounding of z
+                 without dropout: at p = 0.5 the factor 2 is exact, at p = 0.2 the factor 1.25 costs one fp32 rounding of z; the cells
+                 at the module's own initialisation (`init`) without the 1e-12: their scales are asserted > 0 on the host
   exact zeros    pad columns h >= H of the rows, of d/d W_s and of d/d W_2; rows c >= m_dim of d/d W_2; d/d s of every edge whose gU row
                  is zero; the partial rows of a key whose entries all carry gU = 0, and of the list's padding tiles
   no NaN         allocations are poisoned under test (tests/conftest.py): a forgotten element, chunk or slab shows
@@ -161,7 +162,7 @@ def _check(cell, s, o):
         r = ref[name]
         scale = float(r.abs().max())
         err = float((got[name] - r).abs().max())
-        tol = 5e-6 * scale + 1e-12
+        tol = 5e-6 * scale + (0.0 if cell.extra == "init" else 1e-12)     # (at the module's own initialisation the floor would be the bar)
         ratios[NAMES[name]] = err / tol
         if os.environ.get("EGNN_TEST_VERBOSE"):
             print(f"{cell.id:70s} {NAMES[name]:5s} err {err:.3e} bar {tol:.3e} ratio {err / tol:.3f}")

@@ -56,7 +56,7 @@ def _neighbour_count(kw):
     return kw.get("num_nearest_neighbors") or None
 
 
-def _make_layer(kw, seed, path, state=None):
+def _make_layer(kw, seed, path, state=None, device="cuda"):
     from egnn_pytorch_amd import EGNN
     torch.manual_seed(seed % (2 ** 31))
     layer = EGNN(**kw)
@@ -77,12 +77,15 @@ def _make_layer(kw, seed, path, state=None):
                     p.mul_(40.0)                               # away from the vacuous default init (std 1e-3), as elsewhere
     if path == "double":
         layer = layer.double()
-    return layer.cuda()
+    return layer.to(device)
 
 
-def _build(row, pattern, seed, n=None, with_edges=None, dropout=0.0, kw_extra=None):
+def _build(row, pattern, seed, n=None, with_edges=None, dropout=0.0, kw_extra=None, make_layer=None, device="cuda", centre_clamp=True):
     """One case: layer, inputs, mask, cotangents (zero on padded rows).  with_edges: None = as the row says; True / False = the layer
-    with / without per-pair edge features (the seeded walk draws it)."""
+    with / without per-pair edge features (the seeded walk draws it).  make_layer: another layer factory with `_make_layer`'s signature
+    (tests/_default_init.py: the module's own initialisation, where no clamp can be centred: centre_clamp=False); device: "cpu" for the host table tests,
+    which supply a host forward."""
+    make_layer = make_layer or _make_layer
     kw, n0, cdim, path = ROWS[row]
     kw = dict(kw, **(kw_extra or {}))
     if with_edges is True and not kw.get("edge_dim"):
@@ -97,10 +100,10 @@ def _build(row, pattern, seed, n=None, with_edges=None, dropout=0.0, kw_extra=No
     c.k = _neighbour_count(kw)
     dt = torch.float64 if path == "double" else torch.float32
     c.dtype = dt
-    c.mask = torch.from_numpy(mask_pattern(pattern, B, n, c.k, np.random.default_rng(seed))).cuda()
+    c.mask = torch.from_numpy(mask_pattern(pattern, B, n, c.k, np.random.default_rng(seed))).to(device)
     g = torch.Generator().manual_seed(seed + 1)
     dim = kw["dim"]
-    mk = lambda *shape: torch.randn(*shape, generator=g).to(dt).cuda()          # noqa: E731  (float32 values, also for a float64 module)
+    mk = lambda *shape: torch.randn(*shape, generator=g).to(dt).to(device)         # noqa: E731  (float32 values, also for a float64 module)
     # coors_out = x_i + sum over K neighbours of w_ij (x_i - x_j), with |w_ij| up to ~7 from coors_mlp's scaled last bias: K |w| |x| has to
     # stay at a few tens for fp32 (ulp(64) = 7.6e-6) to resolve the absolute forward bar of 1e-4 at all -- coordinates of scale 8 / K
     kk = n if c.k is None else c.k
@@ -110,18 +113,18 @@ def _build(row, pattern, seed, n=None, with_edges=None, dropout=0.0, kw_extra=No
     c.adj = None
     if kw.get("only_sparse_neighbors"):
         i = torch.arange(n)
-        c.adj = ((i[:, None] - i[None, :]).abs() <= BAND).cuda()
-    c.layer = _make_layer(kw, seed, path)
-    if kw.get("coor_weights_clamp_value"):
+        c.adj = ((i[:, None] - i[None, :]).abs() <= BAND).to(device)
+    c.layer = make_layer(kw, seed, path, device=device)
+    if kw.get("coor_weights_clamp_value") and centre_clamp:
         _centre_clamp(c)
     if row == "radius":
         # valid_radius = the median distance over the selected pairs that pass the node masks: half of them fall to the radius
         with torch.no_grad():
             idx, rank = c.layer._forward_hip_checked(c.feats, c.coors, c.edges, c.mask, c.adj, None)[3:5]
-        bi = torch.arange(B, device="cuda")[:, None, None]
+        bi = torch.arange(B, device=device)[:, None, None]
         live = c.mask[:, :, None] & c.mask[bi, idx.long()]
         radius = float(rank[live].median())
-        c.layer = _make_layer(dict(kw, valid_radius=radius), seed, path, state=c.layer.state_dict())
+        c.layer = make_layer(dict(kw, valid_radius=radius), seed, path, state=c.layer.state_dict(), device=device)
         c.kw = dict(kw, valid_radius=radius)
     return c
 
@@ -236,9 +239,11 @@ def _float64(c, drop=None, src=None):
     return node.detach(), co.detach(), grads
 
 
-def _compare(c, got, ref, what, real_rows_only=False):
+def _compare(c, got, ref, what, real_rows_only=False, structural_zero=()):
     """The bars of the module docstring + what must hold exactly: finite everywhere, padded rows of d/d feats and d/d coors 0.0, padded
-    rows of coors_out the input bits.  Returns {gradient name: error / scale}."""
+    rows of coors_out the input bits.  Returns {gradient name: error / scale}.  structural_zero: names whose reference gradient is zero
+    by the form of the loss (an output with a zero cotangent): there the reference must be exactly zero and the result None or exactly
+    zero; every other name keeps the scale > 0 condition."""
     node, co, grads = got
     rnode, rco, rgrads = ref
     f64 = c.path == "double"
@@ -253,6 +258,10 @@ def _compare(c, got, ref, what, real_rows_only=False):
     assert len(grads) == len(rgrads) == len(names)
     worst = {}
     for nm, g, r in zip(names, grads, rgrads):
+        if nm in structural_zero:
+            assert r is None or not bool(r.any()), (what, nm, "the reference gradient is not structurally zero")
+            assert g is None or not bool(g.any()), (what, nm, "a gradient where the loss cannot reach")
+            continue
         assert (g is None) == (r is None), (what, nm)
         if g is None:
             continue
