@@ -33,6 +33,11 @@ constexpr int KNN_PREFIX_BITS = EGNN_KNN_BITS;   // key bits resolved by the pru
 constexpr int KNN_SURVIVORS = 128;               // ... and survivors the fast path ranks directly (two per lane)
 constexpr int KNN_THREADS = 256;
 constexpr int KNN_WAVES = KNN_THREADS / 64;
+// Two nodes can be at a squared distance of exactly 0.0 without sharing a coordinate: the sum of squares rounds to 0.0 when every
+// |x_j[c] - x_i[c]| < 2^-75 (each square below half the smallest subnormal, 2^-150), or < 2^-63 in a build that flushes subnormals
+// (each square below 2^-126).  The adjacency-decided route therefore treats first coordinates closer than 2^-60 as equal: from the
+// arithmetic, conservative for both, and far below the spacing of real coordinates (exact equality, infinities included, stays a hit).
+constexpr float KNN_TIE_EPS = 0x1p-60f;
 
 // CDM: 3 = the fast path (C == 3, distance bit-exact as ((dx^2 + dy^2) + dz^2)); 8 = any 1 <= C <= 8 at run time.
 template <int CPL, int CDM>
@@ -90,9 +95,10 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(
     const uint64_t lt_mask = (1ull << lane) - 1ull;
 
 #if EGNN_KNN_ADJ_FAST
-    // bit r: some OTHER node has the first coordinate of this workgroup's row r (then a non-adjacent node could sit at distance exactly
-    // 0.0 and tie with the adjacent ones: the row takes the general path) -- once per workgroup, every thread its <= 8 candidates
-    // against the <= 32 rows (branch-free; per row and wave it was two thirds of a decided row's instructions)
+    // bit r: some OTHER node's first coordinate is within KNN_TIE_EPS of this workgroup's row r's (then a non-adjacent node could sit at
+    // a squared distance that ROUNDS to exactly 0.0 and tie with the adjacent ones: the row takes the general path) -- once per
+    // workgroup, every thread its <= 8 candidates against the <= 32 rows (branch-free; per row and wave it was two thirds of a decided
+    // row's instructions)
     uint32_t* const dupflags = reinterpret_cast<uint32_t*>(selall + (size_t)KNN_WAVES * Kpad);
     if constexpr (CPL % 4 == 0 && CPL <= 32) {
         if (adj) {                                                       // (uniform)
@@ -114,7 +120,8 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(
 #pragma unroll
                     for (int t = 0; t < PT; ++t) {
                         const int j = tid + KNN_THREADS * t;
-                        hit |= (uint32_t)(xc[t] == xi) & (uint32_t)(j != i) & (uint32_t)(j < N);
+                        const uint32_t near = (uint32_t)(xc[t] == xi) | (uint32_t)(fabsf(xc[t] - xi) < KNN_TIE_EPS);
+                        hit |= near & (uint32_t)(j != i) & (uint32_t)(j < N);
                     }
                     if (r < rows_per_wg && i < N) m |= hit << r;         // (uniform)
                 }
@@ -241,7 +248,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(
         // every adjacent node and a distance >= 0 (or 1e5) for the others (:255-256), and ties go by ascending index: a row with at
         // least K - 1 adjacent nodes is [i, its first K - 1 adjacent nodes in index order] with ranks -1, 0, 0, ... whatever the
         // coordinates are -- unless a NON-adjacent node sits at distance exactly 0.0 and ties with them, which a row rules out by
-        // finding no candidate with the query's first coordinate (checked conservatively: any j != i; only rows of unmasked nodes can
+        // finding no candidate whose first coordinate is within KNN_TIE_EPS of the query's (checked conservatively: any j != i; only rows of unmasked nodes can
         // have such a tie, a masked row's non-adjacent pairs are all 1e5).  The chain adjacency of BASELINE.json's c4 (K = 3,
         // N = 2048): every interior row, 2046 of 2048 -- no distance, no key, no threshold search for them.
         // Adjacent nodes are counted from whole-line loads of the row's 0 / 1 bytes with one wave scan for the positions -- no per-chunk
@@ -280,7 +287,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(
                 const int tot = __builtin_amdgcn_readlane(incl, 63);
                 const int total0 = tot & 0xffff, total = total0 + (tot >> 16);
                 bool decided = total >= K - 1;                            // wave-uniform
-                if (decided && mi) decided = ((*dupflags >> r) & 1u) == 0u;      // (no other node with this row's first coordinate)
+                if (decided && mi) decided = ((*dupflags >> r) & 1u) == 0u;      // (no other node near this row's first coordinate)
 #if defined(EGNN_KNN_ABL) && (EGNN_KNN_ABL & 2)
                 if (decided || total == 12345) continue;                   // timing-only ablation: no emission, no general rows
 #endif
